@@ -23,6 +23,10 @@ Everything else — the 4 M-body HBM roofline, fused ticks, n-body, sparse edges
 whole-world StableHLO ticks, build times — lives in tools/bench_legs.py and runs only under `--extras`, into a sidecar file
 (`--extras-out`); a leg that fails there makes this script exit non-zero.
 
+`--dump-outputs DIR` writes what the last timed step computed — rank 0's world_pos / world_vel / world_accel / force, float64,
+a seeded sample of rows past 64 MB — as DIR/<name>.npy, so two builds can be compared output for output (the inputs are the
+seeded workload of workloads.independent_bodies: identical for identical arguments).
+
 `--dry-run` (CPU, no GPU, fake timings; the line says so in `data`) exercises argument handling, the process group, the
 max-over-ranks and the composition of the line: it is what the CPU tests parse.
 """
@@ -327,6 +331,34 @@ def fit_line(out):
     return text
 
 
+DUMP_COLUMNS = ("world_pos", "world_vel", "world_accel", "force")     # what HipExec.download() hands a caller of the step
+DUMP_LIMIT_BYTES = 64_000_000        # 64 MB in all, on disk: the .npy headers count too
+DUMP_HEADER_BYTES = 1024             # budget per file for its .npy header (128 B for these 1-D / 2-D float64 arrays)
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, columns, limit=DUMP_LIMIT_BYTES):
+    """Write the step's result columns as DIR/<name>.npy (float64), at most `limit` bytes of files in all.  When the whole
+    columns would not fit, a fixed, seeded sample of rows is written instead (the same rows for the same entity count), with
+    the row indices as `rows.npy`."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    cols = {k: np.asarray(v, dtype=np.float64) for k, v in columns.items()}
+    n = next(iter(cols.values())).shape[0]
+    row_bytes = sum(a[:1].nbytes for a in cols.values())
+    if n * row_bytes + len(cols) * DUMP_HEADER_BYTES > limit:
+        keep = (limit - (len(cols) + 1) * DUMP_HEADER_BYTES) // (row_bytes + 8)     # + 8 B per kept row for its index
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        cols = {k: a[rows] for k, a in cols.items()}
+        cols["rows"] = rows.astype(np.float64)
+    for name, a in cols.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
+    total = sum((out / f"{name}.npy").stat().st_size for name in cols)
+    if total > limit:
+        raise RuntimeError(f"bench.py --dump-outputs: {total} bytes written, over the {limit} byte limit")
+    return sorted(cols)
+
+
 def extras_path(args):
     if args.extras_out:
         return Path(args.extras_out)
@@ -359,7 +391,15 @@ def main(argv=None):
                     help="with --campaign: `strong` = BASELINE's rollout total (8,192 / 32,768) split over the ranks; `weak` = that "
                          "count per GPU")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: fake timings through the same process-group and line code (CPU tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the columns they computed (rank 0's shard) as DIR/<name>.npy, float64")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and (args.campaign or args.dry_run):
+        ap.error("--dump-outputs writes the step's columns: not with --campaign or --dry-run")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -450,6 +490,11 @@ def main(argv=None):
         elapsed = shard.max_over_ranks(elapsed, device=rank_device)        # MAX over ranks
         elapsed_incl = shard.max_over_ranks(elapsed_incl, device=rank_device)
     tmd = {"launches": int(tm.launches), "graph_launches": int(tm.graph_launches), "kernel_device_ms": float(tm.kernel_device_ms)}
+    if args.dump_outputs and rank == 0:     # the state after the last timed step, before anything below steps the executor again
+        ex.download()
+        names = dump_outputs(args.dump_outputs, {c: getattr(ex, c) for c in DUMP_COLUMNS})
+        print(f"bench.py: {', '.join(names)} of rank 0 (rows [0, {n}) of the {n * world}-row world) written to {args.dump_outputs}",
+              file=sys.stderr, flush=True)
 
     roofline = None
     if rank == 0:

@@ -1,6 +1,6 @@
 """examples/falcon9/sim.py — the plant of BASELINE configs[4]'s example — imported UNMODIFIED under elodin_amd.compat and built
 the way the reference's own tests build it (test_propulsion.py:111-124: `build_powered(..., extra_systems=script)` with a
-tick-driven open-loop command script written as an @el.system over el.SimulationTick).  Build container only.
+tick-driven open-loop command script written as an @el.system over el.SimulationTick).  Needs the reference checkout (tests/reference.py).
 
 The windows, their spawn states, campaign knobs and command scripts are those of tests/golden/falcon9_plant.json, i.e. of the
 trajectories the reference's own system functions flew under tests/golden/refshim.py (tests/golden/make_falcon9_fixtures.py):
@@ -8,17 +8,20 @@ the same fixtures that pin this repo's own model of the vehicle (tests/test_falc
 makes of the reference's script.  TEST INFRASTRUCTURE."""
 import importlib.util
 import sys
-from pathlib import Path
 
 import numpy as np
 
-REF = Path("/root/reference/examples/falcon9")
+from tests import reference
+
+REF = reference.under("examples", "falcon9")
 
 
 def load_sim():
     """sim.py (and the modules it imports from its directory) under an installed compat layer."""
     if "ref_falcon9_sim" in sys.modules:
         return sys.modules["ref_falcon9_sim"]
+    if REF is None:
+        raise RuntimeError(f"examples/falcon9/sim.py cannot be imported: {reference.SKIP_REASON}")
     sys.path.insert(0, str(REF))
     spec = importlib.util.spec_from_file_location("ref_falcon9_sim", REF / "sim.py")
     sim = importlib.util.module_from_spec(spec)

@@ -26,3 +26,23 @@ for mission in ("crs12",):
         for row in zip(*cols):
             f.write(",".join(repr(float(v)) for v in row) + "\n")
     print(out, len(cols[0]), "rows")
+
+# What tests/test_falcon9_fsw_oracle.py checks the shipped table against: tests/golden/falcon9_crs12_stage1_raw.json, the raw
+# profile the flight software reads (stage1_raw.json, verbatim), and tests/golden/falcon9_crs12_interp.json, at four grid points
+# i the nine samples around t = i x 0.5 s that the reference's own interpolation (examples/falcon9/reference.py `_interp`, the
+# stage profile.rs shares) returns.
+import importlib.util  # noqa: E402
+import shutil  # noqa: E402
+
+raw = json.loads((REF / "examples" / "falcon9" / "data" / "crs12" / "stage1_raw.json").read_text())
+spec = importlib.util.spec_from_file_location("f9_reference", REF / "examples" / "falcon9" / "reference.py")
+ref = importlib.util.module_from_spec(spec)
+sys.modules["f9_reference"] = ref         # dataclasses looks the module up while reference.py defines `Reference`
+spec.loader.exec_module(ref)
+t_raw, v_raw = [float(x) for x in raw["time"]], [float(x) for x in raw["velocity"]]
+interp = {str(i): [ref._interp(k * 0.5, t_raw, v_raw) for k in range(i - 4, i + 5)] for i in (10, 200, 500, 900)}
+shutil.copyfile(REF / "examples" / "falcon9" / "data" / "crs12" / "stage1_raw.json", ROOT / "tests" / "golden" / "falcon9_crs12_stage1_raw.json")
+out = ROOT / "tests" / "golden" / "falcon9_crs12_interp.json"
+out.write_text(json.dumps({"source": "examples/falcon9/reference.py _interp over examples/falcon9/data/crs12/stage1_raw.json",
+                           "samples": interp}, indent=1) + "\n")
+print(out)

@@ -13,6 +13,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -157,3 +158,37 @@ def test_a_rank_failing_alone_in_the_campaign_leg_does_not_cost_the_headline(fau
     assert doc["value"] > 0 and doc["rccl"]["world_size"] == 2
     assert "error" in doc["campaigns"] or "closing_barrier_error" in doc["campaigns"], doc["campaigns"]
     assert "campaign" in r.stderr
+
+
+def test_dump_outputs_writes_the_columns_and_samples_past_the_limit(tmp_path):
+    """--dump-outputs: the step's columns as <name>.npy in float64; past the byte limit a fixed, seeded sample of rows."""
+    g = np.random.default_rng(0)
+    cols = {c: g.normal(size=(1000, 7 if c == "world_pos" else 6)) for c in bench.DUMP_COLUMNS}
+    assert bench.dump_outputs(tmp_path / "all", cols) == sorted(bench.DUMP_COLUMNS)
+    for c, a in cols.items():
+        got = np.load(tmp_path / "all" / f"{c}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    limit = 50_000
+    names = bench.dump_outputs(tmp_path / "a", cols, limit=limit)
+    bench.dump_outputs(tmp_path / "b", cols, limit=limit)
+    assert names == sorted(bench.DUMP_COLUMNS + ("rows",))
+    assert sum((tmp_path / "a" / f"{c}.npy").stat().st_size for c in names) <= limit      # the files as they are on disk
+    rows = np.load(tmp_path / "a" / "rows.npy").astype(np.int64)
+    assert len(rows) > 0 and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))       # the same rows every time
+    for c, a in cols.items():
+        assert np.array_equal(np.load(tmp_path / "a" / f"{c}.npy"), a[rows])
+
+
+def test_steps_below_one_are_refused():
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "0", "--warmup", "5", "--dry-run"],
+                       capture_output=True, text=True, timeout=600, env=_env(), cwd=str(ROOT))
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_stays_within_64_mb_on_disk(tmp_path):
+    """Past the default limit (64,000,000 bytes of files, headers included) the sample fills the budget without exceeding it."""
+    n = 400_000
+    cols = {c: np.zeros((n, 7 if c == "world_pos" else 6)) for c in bench.DUMP_COLUMNS}
+    names = bench.dump_outputs(tmp_path, cols)
+    total = sum((tmp_path / f"{c}.npy").stat().st_size for c in names)
+    assert "rows" in names and 63_900_000 < total <= 64_000_000, total

@@ -7,7 +7,7 @@ models/apollo.run_campaign) — is written with elodin_amd.campaign; then
       (lib.rs:2264-2277, 1335-1347; run_hook.py:12-58), and
   (2) the reference's own hook runner, libs/nox-py/python/elodin/monte_carlo/run_hook.py, is run as a subprocess on the
       context files this repo wrote,
-and both must accept the directory and agree.  Needs /root/reference (build container); skipped elsewhere."""
+and both must accept the directory and agree.  Needs the reference checkout (tests/reference.py); skipped elsewhere."""
 import csv
 import json
 import subprocess
@@ -21,11 +21,12 @@ from elodin_amd import campaign as cp
 from elodin_amd import monte_carlo as mc
 from elodin_amd.models import apollo
 from oracle.apollo import ApolloOracle
+from tests import reference
 
-REF = Path("/root/reference")
-HOOKS = REF / "examples" / "apollo-lander" / "hooks"
-RUN_HOOK = REF / "libs" / "nox-py" / "python" / "elodin" / "monte_carlo" / "run_hook.py"
-pytestmark = pytest.mark.skipif(not HOOKS.exists(), reason="needs the reference checkout (build container only)")
+REF = reference.root()
+HOOKS = REF and REF / "examples" / "apollo-lander" / "hooks"
+RUN_HOOK = REF and REF / "libs" / "nox-py" / "python" / "elodin" / "monte_carlo" / "run_hook.py"
+pytestmark = pytest.mark.skipif(REF is None, reason=reference.SKIP_REASON)
 
 
 @pytest.fixture(scope="module")

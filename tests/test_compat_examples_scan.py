@@ -10,9 +10,11 @@ from pathlib import Path
 
 import pytest
 
-REF = Path("/root/reference/examples")
+from tests import reference
+
+REF = reference.under("examples")
 ROOT = Path(__file__).resolve().parents[1]
-pytestmark = pytest.mark.skipif(not REF.exists(), reason="needs the reference checkout (build container only)")
+pytestmark = pytest.mark.skipif(REF is None, reason=reference.SKIP_REASON)
 
 ONE = r'''
 import sys, importlib.util, os

@@ -1,6 +1,6 @@
 """Reference scripts run UNMODIFIED under elodin_amd.compat (`import elodin`, `import jax`, `from jax import numpy, lax,
 random`, `jax.numpy.linalg`, `jax.scipy.linalg` resolve to this package's front-end).  Build container only — the scripts are
-read from /root/reference and never copied:
+read from the checkout ELODIN_REFERENCE names (tests/reference.py) and never copied:
 
   examples/ball/sim.py         generates the SAME HIP source, byte for byte, as the respelling examples/ball.py, whose GPU
                                flight lands on the reference's ball baseline (tests/test_gpu_examples.py, test_gpu_frontend.py)
@@ -39,9 +39,11 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-REF = Path("/root/reference")
+from tests import reference
+
+REF = reference.root()
 ROOT = Path(__file__).resolve().parents[1]
-pytestmark = pytest.mark.skipif(not REF.exists(), reason="needs the reference checkout (build container only)")
+pytestmark = pytest.mark.skipif(REF is None, reason=reference.SKIP_REASON)
 
 
 def _load(path, name):

@@ -15,11 +15,11 @@ import pytest
 
 from elodin_amd import monte_carlo as mc
 from elodin_amd import vectorize
-from tests import dsl_numpy
+from tests import dsl_numpy, reference
 
 ROOT = Path(__file__).resolve().parents[1]
 GOLDEN = ROOT / "tests" / "golden"
-REF = Path("/root/reference/examples/monte-carlo")
+REF = reference.under("examples", "monte-carlo")
 
 
 def example(probe_rows=0, grid=4096):
@@ -59,7 +59,7 @@ def test_numpy_walk_of_the_campaign_program_lands_on_the_reference_runs(probe_ro
         assert abs(comps["position"][k, 0] - r["result"]["final_position"]) < 1e-12 * max(1.0, abs(r["result"]["final_position"]))
 
 
-@pytest.mark.skipif(not REF.exists(), reason="needs the reference checkout (build container only)")
+@pytest.mark.skipif(REF is None, reason=reference.SKIP_REASON)
 @pytest.mark.parametrize("probe_rows", [0, 64])
 def test_unmodified_script_generates_the_program_of_the_respelling(probe_rows):
     ex = example(probe_rows)
