@@ -107,9 +107,6 @@ struct sixdof_handle {
     std::vector<uint64_t> custom_aux;      // read-only [n,1..3] columns of a generated effector pipe
     std::vector<uint64_t> custom_model;    // read/write [n,1..16] component columns of a generated program
     bool custom_tick_free = false;          // the generated program never looks at the absolute tick (layout bit 17): replayable
-    std::vector<hipStream_t> split_streams;  // side streams of a replay graph split into row-block chains (SIXDOF_GRAPH_SPLIT)
-    std::vector<hipEvent_t> split_joins;
-    hipEvent_t split_fork = nullptr;
     int pair_only_small = -1;               // what the installed pair object was generated for (-1: both launch shapes)
     unsigned custom_rows_multiple = 1;      // rows a world of the generated program occupies (lane mode): the joined row count must be a multiple
     // telemetry ring
@@ -296,9 +293,6 @@ void sixdof_destroy(sixdof_handle* h) try {
     }
     for (void* p : h->pinned_user) (void)hipHostUnregister(p);
     if (h->copy_stream) hipStreamDestroy(h->copy_stream);
-    for (auto st : h->split_streams) hipStreamDestroy(st);
-    for (auto ev : h->split_joins) hipEventDestroy(ev);
-    if (h->split_fork) hipEventDestroy(h->split_fork);
     if (h->ev_snap) hipEventDestroy(h->ev_snap);
     if (h->ev_copied) hipEventDestroy(h->ev_copied);
     if (h->d_csr_start) hipFree(h->d_csr_start);
@@ -1262,10 +1256,9 @@ int sixdof_upload_column(sixdof_handle* h, uint64_t component_id) try {
 
 // Launches per replayed chain.  A long chain amortises the gap between two replays (4,096 launches: 4.96 -> 4.83 us each with
 // 128-launch chains) but starts later (100 launches as one chain: 8 % slower than 32 + 32 + 32 + 4), so a batch OPENS with a
-// 32-launch chain and, when at least four fit, continues with 128-launch ones (profiles/r02_graph_len_ab.txt).  SIXDOF_GRAPH_LONG=<n> overrides the
-// long length for A/B runs (n <= 32: short chains only).
+// 32-launch chain and, when at least four fit, continues with 128-launch ones (profiles/r02_graph_len_ab.txt).
 constexpr uint32_t kGraphLen = 32;
-static const uint32_t kGraphLong = [] { const char* e = std::getenv("SIXDOF_GRAPH_LONG"); const int v = e ? std::atoi(e) : 128; return v > 32 ? static_cast<uint32_t>(v) : 0u; }();
+constexpr uint32_t kGraphLong = 128;
 
 bool graph_eligible(const sixdof_handle* h) {
     return (h->desc.flags & SIXDOF_FLAG_USE_GRAPH) && !(h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) && !h->hist_ring &&
@@ -1274,6 +1267,29 @@ bool graph_eligible(const sixdof_handle* h) {
 
 constexpr uint32_t kGraphMinLen = 4;   // shorter chains are launched eagerly (a replay costs ~10-16 us of host time)
 constexpr size_t kGraphCacheMax = 8;
+
+// What a batch of `full` K-tick launches replays, in this order: an opening 32-launch chain (long batches only: 200
+// launches as 32 + 128 + 40 measured 5 % slower), `n_long` 128-launch chains, `n_short` further 32-launch chains, and one
+// chain of the `tail` launches left (0 when fewer than kGraphMinLen: those run eagerly).  A short batch as a whole, e.g.
+// 20 launches, is its tail — so a short timed region is steady-state device work too, not eager launches racing the host.
+struct ChainPlan {
+    bool open = false;
+    uint64_t n_long = 0, n_short = 0;
+    uint32_t tail = 0;
+    uint64_t launches() const { return (open ? kGraphLen : 0) + n_long * kGraphLong + n_short * kGraphLen + tail; }
+};
+
+static ChainPlan plan_chains(uint64_t full) {
+    ChainPlan c;
+    if (full >= kGraphLen + 4 * kGraphLong) {
+        c.open = true;
+        c.n_long = (full - kGraphLen) / kGraphLong;
+        full -= kGraphLen + c.n_long * kGraphLong;
+    }
+    c.n_short = full / kGraphLen;
+    if (full % kGraphLen >= kGraphMinLen) c.tail = static_cast<uint32_t>(full % kGraphLen);
+    return c;
+}
 
 // Everything a captured launch bakes in: the whole argument block (column pointers, n, both time steps, effector ops
 // and their column pointers, cache policy) plus integrator and dtype.  Any change re-captures — e.g. sixdof_tick
@@ -1294,31 +1310,6 @@ uint64_t step_signature(const sixdof_handle* h, StepParams P, uint32_t K) {
     return sig;
 }
 
-// Row blocks a replayed chain is split into (ensure_graph): SIXDOF_GRAPH_SPLIT=<S>, default 1.  Hand-written pipes only (a
-// generated program's columns have widths of their own), no recording, and at least 4,096 rows per block.
-static const uint32_t kGraphSplit = [] { const char* e = std::getenv("SIXDOF_GRAPH_SPLIT"); const int v = e ? std::atoi(e) : 1; return static_cast<uint32_t>(v < 1 ? 1 : (v > 16 ? 16 : v)); }();
-
-uint32_t graph_split_for(const sixdof_handle* h, const StepParams& P) {
-    if (kGraphSplit <= 1 || h->custom_launch || P.hist_ring || P.n < kGraphSplit * 4096u) return 1;
-    return kGraphSplit;
-}
-
-// The argument block of rows [row0, row0 + rows) of a launch: every column pointer moved to the block's first row.
-StepParams row_block(const sixdof_handle* h, const StepParams& P, uint32_t row0, uint32_t rows) {
-    StepParams Q = P;
-    const size_t es = h->elem_size();
-    auto at = [&](const void* p, size_t width) { return p ? static_cast<const char*>(p) + static_cast<size_t>(row0) * width * es : nullptr; };
-    Q.pos = const_cast<char*>(at(P.pos, 7));
-    Q.vel = const_cast<char*>(at(P.vel, 6));
-    Q.accel = const_cast<char*>(at(P.accel, 6));
-    Q.force = const_cast<char*>(at(P.force, 6));
-    Q.inertia = at(P.inertia, 7);
-    for (uint32_t k = 0; k < P.n_ops && k < static_cast<uint32_t>(kMaxOps); k++)
-        Q.ops[k].aux = at(P.ops[k].aux, P.ops[k].aux_width ? P.ops[k].aux_width : 3);
-    Q.n = rows;
-    return Q;
-}
-
 // An executable graph of `len` identical launches of the step kernel (cached per chain length; all cached graphs share
 // one signature and are dropped together when it changes).
 int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t K, uint32_t len, hipGraphExec_t* out) {
@@ -1329,7 +1320,7 @@ int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t K, uint32_t len
         *out = it->second;
         return SIXDOF_OK;
     }
-    if (h->graphs.size() >= kGraphCacheMax) {   // many distinct batch lengths: keep the long chain, drop the rest
+    if (h->graphs.size() >= kGraphCacheMax) {   // many distinct batch lengths: keep the 32- and 128-launch chains, drop the rest
         for (auto g = h->graphs.begin(); g != h->graphs.end();) {
             if (g->first == kGraphLen || g->first == kGraphLong) { ++g; continue; }
             hipGraphExecDestroy(g->second);
@@ -1337,41 +1328,9 @@ int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t K, uint32_t len
         }
     }
     hipGraph_t g = nullptr;
-    const uint32_t S = graph_split_for(h, P);
-    if (S > 1) {      // the side streams and the fork / join events exist before the capture starts
-        while (h->split_streams.size() < S - 1) {
-            hipStream_t s = nullptr;
-            HIP_TRY(h, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-            h->split_streams.push_back(s);
-            hipEvent_t e = nullptr;
-            HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            h->split_joins.push_back(e);
-        }
-        if (!h->split_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->split_fork, hipEventDisableTiming));
-    }
     HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     hipError_t le = hipSuccess;
-    if (S <= 1) {
-        for (uint32_t i = 0; i < len && le == hipSuccess; i++) le = launch_any(h, P);
-    } else {
-        // ROW-BLOCK CHAINS.  Rows are independent and a launch of this path exchanges nothing, so tick k + 1 of a row block
-        // depends on tick k of THAT block only: the replayed graph is S parallel chains of `len` launches, one per contiguous
-        // row block, forked from and joined back into the handle's stream once per replay.  Same kernel, same rows per wave,
-        // same arithmetic -> the same bits; what changes is that one block's end-of-kernel write-back and dispatch gap overlap
-        // another block's loads and math (profiles/r06_k1_floor.md).
-        const uint32_t block = ((P.n + S - 1) / S + 255u) & ~255u;      // whole 256-row groups: every wave shape divides it
-        le = hipEventRecord(h->split_fork, h->stream);
-        for (uint32_t s = 0; s < S && le == hipSuccess; s++) {
-            const uint32_t row0 = s * block;
-            if (row0 >= P.n) break;
-            hipStream_t st = s == 0 ? h->stream : h->split_streams[s - 1];
-            if (s > 0) le = hipStreamWaitEvent(st, h->split_fork, 0);
-            const StepParams Ps = row_block(h, P, row0, std::min(block, P.n - row0));
-            for (uint32_t i = 0; i < len && le == hipSuccess; i++) le = launch_step(Ps, h->desc.integrator, h->desc.dtype, st);
-            if (s > 0 && le == hipSuccess) le = hipEventRecord(h->split_joins[s - 1], st);
-            if (s > 0 && le == hipSuccess) le = hipStreamWaitEvent(h->stream, h->split_joins[s - 1], 0);
-        }
-    }
+    for (uint32_t i = 0; i < len && le == hipSuccess; i++) le = launch_any(h, P);
     hipError_t ce = hipStreamEndCapture(h->stream, &g);
     if (le != hipSuccess) return h->hip_fail(le, "launch_step (capture)");
     if (ce != hipSuccess) return h->hip_fail(ce, "hipStreamEndCapture");
@@ -1385,6 +1344,16 @@ int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t K, uint32_t len
     h->graph_sig = sig;
     *out = exec;
     return SIXDOF_OK;
+}
+
+// The graphs a plan replays, from the cache or captured now: g[0] the 32-launch chain, g[1] the 128-launch one, g[2] the
+// tail.  The tail comes last, so a cache eviction it triggers (which keeps the 32- and 128-launch chains) drops none of them.
+static int ensure_plan_graphs(sixdof_handle* h, const StepParams& P, uint32_t K, const ChainPlan& c, hipGraphExec_t g[3]) {
+    int rc = SIXDOF_OK;
+    if (c.open || c.n_short) rc = ensure_graph(h, P, K, kGraphLen, &g[0]);
+    if (rc == SIXDOF_OK && c.n_long) rc = ensure_graph(h, P, K, kGraphLong, &g[1]);
+    if (rc == SIXDOF_OK && c.tail) rc = ensure_graph(h, P, K, c.tail, &g[2]);
+    return rc;
 }
 
 // Build the replay graph ahead of the first long batch (called when the columns become resident and when the batch
@@ -1411,35 +1380,131 @@ int sixdof_prepare_step(sixdof_handle* h, uint64_t n_ticks) try {
     if (rc != SIXDOF_OK) return rc;
     const uint32_t K = h->desc.ticks_per_launch;
     P.n_ticks = K;
-    // the chains a batch of `full` K-tick launches replays (the same arithmetic as sixdof_step)
-    auto prepare = [&](uint64_t full) -> int {
-        hipGraphExec_t unused = nullptr;
-        int prc;
-        if (full >= kGraphLen && (prc = ensure_graph(h, P, K, kGraphLen, &unused)) != SIXDOF_OK) return prc;
-        if (kGraphLong && full >= kGraphLen + 4 * kGraphLong) {
-            if ((prc = ensure_graph(h, P, K, kGraphLong, &unused)) != SIXDOF_OK) return prc;
-            full = (full - kGraphLen) % kGraphLong;     // what the opening chain and the long ones leave
-        }
-        const uint32_t tail_len = static_cast<uint32_t>(full % kGraphLen);
-        if (full >= kGraphMinLen && tail_len >= kGraphMinLen && (prc = ensure_graph(h, P, K, tail_len, &unused)) != SIXDOF_OK) return prc;
-        return SIXDOF_OK;
-    };
+    hipGraphExec_t unused[3] = {};
     const uint64_t full = n_ticks / K;
-    if ((rc = prepare(full)) != SIXDOF_OK) return rc;
-    // the first RK4 step after an upload takes one eager launch out of `full` (sixdof_step: accel_in_check), so that
+    if ((rc = ensure_plan_graphs(h, P, K, plan_chains(full), unused)) != SIXDOF_OK) return rc;
+    // the first RK4 step after an upload takes one eager launch out of `full` (step_rigid: accel_in_check), so that
     // batch replays `full - 1` launches; whether the batch being prepared is that one the library cannot know (a warm-up
     // may come first), so both shapes are captured
-    if (h->accel_is_host_data && h->desc.integrator == SIXDOF_INTEGRATOR_RK4 && full > 0 && (rc = prepare(full - 1)) != SIXDOF_OK) return rc;
+    if (h->accel_is_host_data && h->desc.integrator == SIXDOF_INTEGRATOR_RK4 && full > 0 &&
+        (rc = ensure_plan_graphs(h, P, K, plan_chains(full - 1), unused)) != SIXDOF_OK)
+        return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
+
+// Pair effectors: one launch call per K ticks.  The multi-kernel path's batch is ONE pack launch, then fold + integrate
+// per tick (the integrate kernel writes the next tick's pack rows); with a telemetry ring the batch is cut at every tick
+// for the snapshot, the pack rows carry over all the same.
+static int step_pair(sixdof_handle* h, uint64_t n_ticks, uint64_t* launches) {
+    if (h->desc.dtype != SIXDOF_F64) return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: pair effectors are f64 only");
+    PairParams P;
+    int rc = fill_pair_params(h, &P);
+    if (rc != SIXDOF_OK) return rc;
+    const char* no_small = std::getenv("SIXDOF_PAIR_SMALL");   // "0": force the multi-kernel path (tests)
+    const bool custom = P.pair_kind == SIXDOF_EFF_EDGE_CUSTOM;
+    bool small = P.n <= kPairSmallMax && !(no_small && no_small[0] == '0');   // small graphs: ticks_per_launch ticks per launch
+    if (custom) {
+        if (!h->pair_launch) return h->fail(SIXDOF_ERR_BACKEND, "step: custom pair op without sixdof_set_custom_pair");
+        if (h->pair_only_small >= 0) small = h->pair_only_small == 1;
+        if (small && P.n > kPairSmallMax)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "step: the pair object was generated for the one-launch small-graph kernel (<= " +
+                           std::to_string(kPairSmallMax) + " rows) but the joined graph has " + std::to_string(P.n) + " rows");
+    }
+    const uint32_t K = h->hist_ring ? 1u : (small ? h->desc.ticks_per_launch : 1u << 20);
+    // the integrate kernel leaves the next tick's pack rows (this call only: PairParams::packed); the built-in small-graph
+    // kernel packs in-launch
+    const bool sets_packed = custom || !small;
+    for (uint64_t done = 0; done < n_ticks;) {
+        const uint32_t k = static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks - done));
+        if (custom) {
+            hipError_t e = static_cast<hipError_t>(h->pair_launch(&P, h->desc.integrator, k, small ? 1 : 0, h->stream, launches));
+            if (e != hipSuccess) return h->hip_fail(e, "custom pair launch");
+        } else if (small) {
+            hipError_t e = launch_pair_small(P, h->desc.integrator, k, h->stream, launches);
+            if (e != hipSuccess) return h->hip_fail(e, "launch_pair_small");
+        } else {
+            hipError_t e = launch_pair_ticks(P, h->desc.integrator, k, h->stream, launches);
+            if (e != hipSuccess) return h->hip_fail(e, "launch_pair_ticks");
+        }
+        done += k;
+        if (sets_packed) P.packed = 1;
+        if (int src = snapshot_tick_to_ring(h, h->tick + done); src != SIXDOF_OK) return src;
+    }
+    return SIXDOF_OK;
+}
+
+// The step kernel: K ticks per launch, long batches replayed from hipGraphs (launch-bound regime: a 65,536-entity tick is
+// a few microseconds of device time), the rest launched eagerly.
+static int step_rigid(sixdof_handle* h, uint64_t n_ticks, uint64_t* launches) {
+    StepParams P;
+    int rc = fill_step_params(h, &P);
+    if (rc != SIXDOF_OK) return rc;
+    const uint32_t K = h->desc.ticks_per_launch;
+    uint64_t full = n_ticks / K;
+    uint32_t rem = static_cast<uint32_t>(n_ticks % K);
+    P.n_ticks = K;
+    const bool time_each = (h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) != 0;
+    if (time_each) {
+        const uint64_t need = 2 * (full + (rem ? 1 : 0));
+        if (need > 8192) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "step: TIME_EACH_LAUNCH supports <= 4096 launches per call");
+        while (h->launch_events.size() < need) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(h, hipEventCreate(&e));
+            h->launch_events.push_back(e);
+        }
+    }
+    // one eager launch of `ticks` ticks; every launch before it ran K ticks
+    auto eager = [&](StepParams Q, uint32_t ticks) -> int {
+        Q.n_ticks = ticks;
+        Q.tick0 = Q.hist_slot0 = h->tick + *launches * K;
+        if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * *launches], h->stream));
+        hipError_t e = launch_any(h, Q);
+        if (e != hipSuccess) return h->hip_fail(e, "launch_step");
+        if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * *launches + 1], h->stream));
+        ++*launches;
+        return SIXDOF_OK;
+    };
+    if (h->accel_is_host_data && n_ticks > 0) {
+        // First launch after an upload: the world_accel column holds whatever the host put there.  The reference's RK4
+        // forms v_s = v0 + 0 * a_in on stage 0 (rk4.rs:96-100), so a non-finite row poisons that tick; this one launch
+        // reads the column to do the same (step_kernel.hpp).  Every later a_in is this kernel's own output and is
+        // already folded into v0.  A launch of its own, eager, so the replay graphs never carry the flag.
+        h->accel_is_host_data = false;
+        if (h->desc.integrator == SIXDOF_INTEGRATOR_RK4) {
+            StepParams P1 = P;
+            P1.accel_in_check = 1;
+            if ((rc = eager(P1, static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks)))) != SIXDOF_OK) return rc;
+            if (n_ticks >= K) full -= 1;   // that launch was one of the K-tick launches ...
+            else rem = 0;                  // ... or the whole (short) batch
+        }
+    }
+    uint64_t graph_launches = 0;
+    const ChainPlan c = graph_eligible(h) ? plan_chains(full) : ChainPlan{};
+    if (c.launches()) {
+        hipGraphExec_t g[3] = {};
+        if ((rc = ensure_plan_graphs(h, P, K, c, g)) != SIXDOF_OK) return rc;
+        // a capture may just have happened after ev0 was recorded: re-record so the pair brackets real work only
+        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        const std::pair<hipGraphExec_t, uint64_t> replays[4] = {{g[0], c.open ? 1 : 0}, {g[1], c.n_long}, {g[0], c.n_short}, {g[2], c.tail ? 1 : 0}};
+        for (const auto& [graph, times] : replays)
+            for (uint64_t i = 0; i < times; i++) HIP_TRY(h, hipGraphLaunch(graph, h->stream));
+        graph_launches = c.launches();
+        *launches += graph_launches;
+        full -= graph_launches;
+    }
+    h->last.graph_launches = graph_launches;
+    for (uint64_t i = 0; i < full; i++)
+        if ((rc = eager(P, K)) != SIXDOF_OK) return rc;
+    if (rem && (rc = eager(P, rem)) != SIXDOF_OK) return rc;
+    return SIXDOF_OK;
+}
 
 int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "step: no columns bound");
     HIP_TRY(h, hipSetDevice(h->device));
     const double t0 = now_ms();
-    uint64_t launches = 0;
     const bool async_step = (h->desc.flags & SIXDOF_FLAG_ASYNC_STEP) != 0;
     if (h->step_pending || h->prev_pending) {
         // asynchronous batches alternate between two event pairs, so the host may enqueue batch i+1 while batch i
@@ -1466,165 +1531,11 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     if (h->desc.integrator == SIXDOF_INTEGRATOR_NONE && (!h->custom_launch || h->model != 0 || h->has_pair_op()))
         return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: SIXDOF_INTEGRATOR_NONE runs generated system programs only (sixdof_set_custom_pipe)");
-    if (h->model == 1) {
-        int rc = step_apollo(h, n_ticks, &launches);
-        if (rc != SIXDOF_OK) return rc;
-    } else if (h->has_pair_op()) {
-        if (h->desc.dtype != SIXDOF_F64) return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: pair effectors are f64 only");
-        PairParams P;
-        int rc = fill_pair_params(h, &P);
-        if (rc != SIXDOF_OK) return rc;
-        const char* no_small = std::getenv("SIXDOF_PAIR_SMALL");   // "0": force the multi-kernel path (tests)
-        if (P.pair_kind == SIXDOF_EFF_EDGE_CUSTOM) {
-            if (!h->pair_launch) return h->fail(SIXDOF_ERR_BACKEND, "step: custom pair op without sixdof_set_custom_pair");
-            const bool small = h->pair_only_small >= 0 ? h->pair_only_small == 1 : (P.n <= kPairSmallMax && !(no_small && no_small[0] == '0'));
-            if (small && P.n > kPairSmallMax)
-                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "step: the pair object was generated for the one-launch small-graph kernel (<= " +
-                               std::to_string(kPairSmallMax) + " rows) but the joined graph has " + std::to_string(P.n) + " rows");
-            const uint32_t K = h->hist_ring ? 1u : (small ? h->desc.ticks_per_launch : 1u << 20);
-            for (uint64_t done = 0; done < n_ticks;) {
-                const uint32_t k = static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks - done));
-                hipError_t e = static_cast<hipError_t>(h->pair_launch(&P, h->desc.integrator, k, small ? 1 : 0, h->stream, &launches));
-                if (e != hipSuccess) return h->hip_fail(e, "custom pair launch");
-                done += k;
-                P.packed = 1;      // the integrate kernel left the next tick's pack rows (this call only: PairParams::packed)
-                if (int src = snapshot_tick_to_ring(h, h->tick + done); src != SIXDOF_OK) return src;
-            }
-        } else if (P.n <= kPairSmallMax && !(no_small && no_small[0] == '0')) {   // small graphs: ticks_per_launch ticks per launch
-            const uint32_t K = h->hist_ring ? 1u : h->desc.ticks_per_launch;
-            for (uint64_t done = 0; done < n_ticks;) {
-                const uint32_t k = static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks - done));
-                hipError_t e = launch_pair_small(P, h->desc.integrator, k, h->stream, &launches);
-                if (e != hipSuccess) return h->hip_fail(e, "launch_pair_small");
-                done += k;
-                if (int src = snapshot_tick_to_ring(h, h->tick + done); src != SIXDOF_OK) return src;
-            }
-        } else {
-            // a batch is ONE pack launch, then fold + integrate per tick (the integrate kernel writes the next tick's pack rows);
-            // with a telemetry ring the batch is cut at every tick for the snapshot, the pack rows carry over all the same
-            const uint32_t K = h->hist_ring ? 1u : 1u << 20;
-            for (uint64_t done = 0; done < n_ticks;) {
-                const uint32_t k = static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks - done));
-                hipError_t e = launch_pair_ticks(P, h->desc.integrator, k, h->stream, &launches);
-                if (e != hipSuccess) return h->hip_fail(e, "launch_pair_ticks");
-                done += k;
-                P.packed = 1;
-                if (int src = snapshot_tick_to_ring(h, h->tick + done); src != SIXDOF_OK) return src;
-            }
-        }
-    } else {
-        StepParams P;
-        int rc = fill_step_params(h, &P);
-        if (rc != SIXDOF_OK) return rc;
-        const uint32_t K = h->desc.ticks_per_launch;
-        uint64_t full = n_ticks / K;
-        const uint32_t rem = static_cast<uint32_t>(n_ticks % K);
-        uint32_t rem_left = rem;
-        P.n_ticks = K;
-        // Long batches of identical launches replay from a hipGraph (launch-bound regime:
-        // a 65,536-entity tick is a few microseconds of device time).
-        const bool time_each = (h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) != 0;
-        if (time_each) {
-            const uint64_t need = 2 * (full + (rem ? 1 : 0));
-            if (need > 8192) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "step: TIME_EACH_LAUNCH supports <= 4096 launches per call");
-            while (h->launch_events.size() < need) {
-                hipEvent_t e = nullptr;
-                HIP_TRY(h, hipEventCreate(&e));
-                h->launch_events.push_back(e);
-            }
-        }
-        uint64_t ticks_issued = 0;   // history slot of a launch's first tick = ticks done before it
-        uint64_t graph_launches = 0;
-        if (h->accel_is_host_data && n_ticks > 0) {
-            // First launch after an upload: the world_accel column holds whatever the host put there.  The reference's RK4
-            // forms v_s = v0 + 0 * a_in on stage 0 (rk4.rs:96-100), so a non-finite row poisons that tick; this one launch
-            // reads the column to do the same (step_kernel.hpp).  Every later a_in is this kernel's own output and is
-            // already folded into v0.  A launch of its own, eager, so the replay graphs never carry the flag.
-            h->accel_is_host_data = false;
-            if (h->desc.integrator == SIXDOF_INTEGRATOR_RK4) {
-                StepParams P1 = P;
-                P1.accel_in_check = 1;
-                P1.n_ticks = static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks));
-                P1.hist_slot0 = h->tick;
-                P1.tick0 = h->tick;
-                if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[0], h->stream));
-                hipError_t e = launch_any(h, P1);
-                if (e != hipSuccess) return h->hip_fail(e, "launch_step");
-                if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[1], h->stream));
-                launches = 1;
-                if (n_ticks >= K) full -= 1;   // that launch was one of the K-tick launches ...
-                else rem_left = 0;             // ... or the whole (short) batch
-            }
-        }
-        if (graph_eligible(h) && full >= kGraphMinLen) {
-            // long batches replay 32-launch chains; what is left (or a short batch as a whole, e.g. 20 ticks) replays as
-            // ONE chain of exactly that length, captured on first use and cached — so a short timed region is
-            // steady-state device work too, not eager launches racing the host.
-            hipGraphExec_t big = nullptr, tail = nullptr, longer = nullptr;
-            uint64_t n_long = 0;
-            const uint64_t eager_before = launches;
-            if (kGraphLong && full >= kGraphLen + 4 * kGraphLong) {   // open with one short chain, then long ones (long batches only:
-                                                                    // 200 launches as 32 + 128 + 40 measured 5 % slower)
-                int grc = ensure_graph(h, P, K, kGraphLong, &longer);
-                if (grc != SIXDOF_OK) return grc;
-                n_long = (full - kGraphLen) / kGraphLong;
-            }
-            const uint32_t tail_len = static_cast<uint32_t>((full - n_long * kGraphLong) % kGraphLen);
-            if (full >= kGraphLen) {
-                int grc = ensure_graph(h, P, K, kGraphLen, &big);
-                if (grc != SIXDOF_OK) return grc;
-            }
-            if (tail_len >= kGraphMinLen) {
-                int grc = ensure_graph(h, P, K, tail_len, &tail);
-                if (grc != SIXDOF_OK) return grc;
-            }
-            // a capture may just have happened after ev0 was recorded: re-record so the pair brackets real work only
-            HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-            if (n_long) {
-                HIP_TRY(h, hipGraphLaunch(big, h->stream));
-                full -= kGraphLen;
-                launches += kGraphLen;
-                for (uint64_t i = 0; i < n_long; i++) {
-                    HIP_TRY(h, hipGraphLaunch(longer, h->stream));
-                    full -= kGraphLong;
-                    launches += kGraphLong;
-                }
-            }
-            while (full >= kGraphLen) {
-                HIP_TRY(h, hipGraphLaunch(big, h->stream));
-                full -= kGraphLen;
-                launches += kGraphLen;
-            }
-            if (tail) {
-                HIP_TRY(h, hipGraphLaunch(tail, h->stream));
-                full -= tail_len;
-                launches += tail_len;
-            }
-            graph_launches = launches - eager_before;
-        }
-        h->last.graph_launches = graph_launches;
-        ticks_issued = launches * K;
-        for (uint64_t i = 0; i < full; i++) {
-            if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * launches], h->stream));
-            P.hist_slot0 = h->tick + ticks_issued;
-            P.tick0 = h->tick + ticks_issued;
-            ticks_issued += K;
-            hipError_t e = launch_any(h, P);
-            if (e != hipSuccess) return h->hip_fail(e, "launch_step");
-            if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * launches + 1], h->stream));
-            launches++;
-        }
-        if (rem_left) {
-            P.n_ticks = rem_left;
-            P.hist_slot0 = h->tick + ticks_issued;
-            P.tick0 = h->tick + ticks_issued;
-            if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * launches], h->stream));
-            hipError_t e = launch_any(h, P);
-            if (e != hipSuccess) return h->hip_fail(e, "launch_step");
-            if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * launches + 1], h->stream));
-            launches++;
-        }
-    }
+    uint64_t launches = 0;
+    const int rc = h->model == 1 ? step_apollo(h, n_ticks, &launches)
+                   : h->has_pair_op() ? step_pair(h, n_ticks, &launches)
+                                      : step_rigid(h, n_ticks, &launches);
+    if (rc != SIXDOF_OK) return rc;
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     if (!async_step) {
         // short batches finish in tens of microseconds: poll for that long before paying a blocking wait's wake-up
@@ -1638,34 +1549,22 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
     }
     h->tick += n_ticks;  // increment_sim_tick (globals.rs:42-44), once per tick
     h->step_pending = async_step;
-    {
-        if (!async_step) {
-            float ms0 = 0.f;
-            hipEventElapsedTime(&ms0, h->ev0, h->ev1);
-            h->last.kernel_device_ms = ms0;
-        }
-        h->last.kernel_invoke_ms = now_ms() - t0;
-        h->last.launches = launches;
-        h->last.ticks = n_ticks;
+    if (!async_step) {
+        float ms0 = 0.f;
+        hipEventElapsedTime(&ms0, h->ev0, h->ev1);
+        h->last.kernel_device_ms = ms0;
     }
-    if (tm) {
-        tm->h2d_upload_ms = h->last.h2d_upload_ms;
-        tm->d2h_download_ms = h->last.d2h_download_ms;
-        tm->kernel_device_ms = h->last.kernel_device_ms;
-        tm->kernel_invoke_ms = h->last.kernel_invoke_ms;
-        tm->launches = launches;
-        tm->ticks = n_ticks;
-        tm->kernel_sum_ms = 0.0;
-        tm->graph_launches = h->last.graph_launches;
-        if ((h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) && !h->has_pair_op()) {
-            double sum = 0.0;
-            for (uint64_t i = 0; i < launches && 2 * i + 1 < h->launch_events.size(); i++) {
-                float one = 0.f;
-                if (hipEventElapsedTime(&one, h->launch_events[2 * i], h->launch_events[2 * i + 1]) == hipSuccess) sum += one;
-            }
-            tm->kernel_sum_ms = sum;
+    h->last.kernel_invoke_ms = now_ms() - t0;
+    h->last.launches = launches;
+    h->last.ticks = n_ticks;
+    h->last.kernel_sum_ms = 0.0;
+    if ((h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) && !h->has_pair_op()) {
+        for (uint64_t i = 0; i < launches && 2 * i + 1 < h->launch_events.size(); i++) {
+            float one = 0.f;
+            if (hipEventElapsedTime(&one, h->launch_events[2 * i], h->launch_events[2 * i + 1]) == hipSuccess) h->last.kernel_sum_ms += one;
         }
     }
+    if (tm) *tm = h->last;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
