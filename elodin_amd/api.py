@@ -367,10 +367,11 @@ class World:
         to = np.array([b for _, b in pairs], dtype=np.uint64)
         return (to, frm) if reverse else (frm, to)
 
-    def generated_sources(self, system, simulation_rate: float = 120.0, dtype: str = "float64") -> Dict[str, str]:
+    def generated_sources(self, system, simulation_rate: float = 120.0, dtype: str = "float64", policy: Optional[int] = None) -> Dict[str, str]:
         """The HIP sources World.build would generate for `system` (kernel name -> text), without touching a device: what a
         user script compiles to.  Two scripts that build the same program produce the same text (tests compare a reference
-        script imported under elodin_amd.compat with its respelling this way).  Built-in effector ops generate nothing."""
+        script imported under elodin_amd.compat with its respelling this way).  Built-in effector ops generate nothing.
+        policy: the step kernel for this one cache policy (codegen.generate_source); None = all three."""
         plan = self.build(system, simulation_rate=simulation_rate, _dry=True)
         from . import codegen, dsl as _dsl
         out = {}
@@ -381,7 +382,7 @@ class World:
             cols = plan["columns"] or {}
             widths = {k: (tuple(int(x) for x in np.shape(v)[1:]) if np.ndim(v) == 3 else int(np.atleast_2d(np.asarray(v)).shape[-1]))
                       for k, v in cols.items() if v is not None}
-            out["step"] = codegen.generate_source(effs.trace(widths), dtype, plan["integrator"])
+            out["step"] = codegen.generate_source(effs.trace(widths), dtype, plan["integrator"], policy=policy)
         else:
             for e in effs:
                 if isinstance(e, _dsl.EdgeFold):

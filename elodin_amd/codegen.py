@@ -13,6 +13,7 @@ from __future__ import annotations
 import hashlib
 import os
 import subprocess
+from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Optional, Dict, List, Sequence
 
@@ -56,7 +57,56 @@ _SYSTEM_LEAVES = {"qi": "q.i", "qj": "q.j", "qk": "q.k", "qw": "q.w", "px": "p.x
                   "aax": "accel.ang.x", "aay": "accel.ang.y", "aaz": "accel.ang.z", "alx": "accel.lin.x", "aly": "accel.lin.y", "alz": "accel.lin.z"}
 
 
-def _leaf_ref(name: str, table: Dict[str, str]) -> str:
+@dataclass
+class _Unit:
+    """What one translation unit is emitted under, handed down explicitly: its switches (_unit: the generator's arguments and the
+    A/B environment knobs) and the constant tables its code refers to, filled while emitting it."""
+    column_soa: bool = False        # program columns element-major on the device (COLUMN_SOA_MIN_ROWS)
+    window_soa: bool = False        # window columns element-major on the device (WINDOW_SOA_MIN_ROWS)
+    guard_selects: bool = False     # opt-in: see _Emitter.block, "GUARDED SELECT"
+    # Fast-math builds fold single-use products into the sums that consume them (see _Emitter.block, "FUSED MULTIPLY-ADD");
+    # SIXDOF_FUSE_FMA=0 keeps them apart (A/B).  Exact builds never fuse: a reference evaluates every node to a rounded value.
+    fuse_fma: bool = False
+    relaxed: bool = False           # programs traced under dsl.relaxed_arithmetic (TracedProgram.fp_contract): see _Emitter.block `m_rcp_relaxed`
+    # Order in which a block's nodes are emitted: "program" = the order the user's code created them (see _Emitter.block),
+    # "demand" = depth-first from the outputs, each value right before its first use, "pressure" = _pressure_order.  Program
+    # order is tried first; a machine-generated DAG with no meaningful creation order (the fuzzer's random programs) can do
+    # better on demand.
+    order: str = "program"
+    # Fallback layout of a program whose state does not fit a wave's 512 registers (the f64 Falcon 9 closed loop: ~250 doubles
+    # of component state + the temporaries of 20 systems): the register image `Regs` is declared `volatile`, i.e. it lives in
+    # the lane's private (scratch) memory and every access is a real load / store — deliberate, compiler-independent placement
+    # instead of register-allocator spills (a spilling build miscomputed on gfx950 before, see _compile).  The launch-level
+    # column load / store and the cold-column scheme stay as they are.  Costs scratch traffic (L1 / L2 resident) on every
+    # access: a parity build, not a fast one.  build() switches to it by itself when no register-resident build is spill-free.
+    # (Tried first: keeping every column in HBM and wrapping each system in loads / stores — the optimiser forwards the stored
+    # values to the next system's loads and the live set stays where it was: 150+ spills with every flag set.)
+    memory_columns: bool = False
+    # Last resort: the tick body compiled as a real function (step_kernel.hpp SIXDOF_TICK_OUT_OF_LINE) — for programs whose
+    # TEMPORARIES, not state, overflow the register file (a fuzz program of 200 inlined f64 libm calls: 43 values live in source
+    # order, 650 registers after LLVM's allocation across its 600 basic blocks, whatever the flags).
+    tick_out_of_line: bool = False
+    policy: Optional[int] = None    # the one cache policy the step kernel is instantiated for (build(policy=...)); None: all three
+    estimate: Optional[Dict[str, int]] = None     # build(): peak live values per emission order, recorded by _pressure_order
+    tables: Dict[tuple, str] = field(default_factory=dict)        # (xp, fp) -> C++ symbol stem
+    gathers: Dict[str, str] = field(default_factory=dict)         # dsl gather-table key -> C++ symbol of its __device__ const array
+    lane_tables: Dict[tuple, str] = field(default_factory=dict)   # (stride, source entity per entity index) of a lane_read in a world of 32 / 64 rows -> symbol
+    windows: Dict[int, tuple] = field(default_factory=dict)       # window slot -> (rows, width, head slot) (dsl.Window)
+
+
+def _unit(tp, variant: str = "program", fast_math: bool = False, window_soa: bool = False, column_soa: bool = False,
+          guard_selects: Optional[bool] = None, policy: Optional[int] = None, estimate: bool = False) -> _Unit:
+    """The context of one generation of `tp` as `variant` (VARIANTS); the environment knobs are read here, once per source."""
+    return _Unit(column_soa=bool(column_soa), window_soa=bool(window_soa),
+                 guard_selects=(os.environ.get("SIXDOF_GUARD_SELECTS", "") == "1") if guard_selects is None else bool(guard_selects),
+                 fuse_fma=bool(fast_math) and os.environ.get("SIXDOF_FUSE_FMA", "1") != "0",
+                 relaxed=(isinstance(tp, dsl.TracedProgram) and bool(getattr(tp, "fp_contract", False))
+                          and os.environ.get("SIXDOF_RELAXED_IEEE_RCP", "") != "1"),      # A/B: the shared reciprocals as IEEE divides
+                 order=variant if variant in ("demand", "pressure") else "program", memory_columns=variant == "memory",
+                 tick_out_of_line=variant == "out_of_line", policy=policy, estimate={} if estimate else None)
+
+
+def _leaf_ref(u: _Unit, name: str, table: Dict[str, str]) -> str:
     if name in table:
         return table[name]
     if name.startswith("aux"):
@@ -67,40 +117,34 @@ def _leaf_ref(name: str, table: Dict[str, str]) -> str:
         return f"r.c{slot}[{k}]"
     if name.startswith("wst"):      # window push: row `head` (the oldest) of the ring; `@w_act@`: store only from lanes that own a row
         slot, j = (int(x) for x in name[3:].split("_"))
-        _, width, head_slot = _WINDOWS[slot]
+        _, width, head_slot = u.windows[slot]
         return f"@w_act@W{slot}[(size_t)(static_cast<int>(r.c{head_slot}[0]) * {width} + {j}) * w_n]"
     raise KeyError(name)
 
 
-_TABLES: Dict[tuple, str] = {}    # (xp, fp) -> C++ symbol stem, filled while emitting one translation unit
-_GATHERS: Dict[str, str] = {}     # dsl gather-table key -> C++ symbol of its __device__ const array, same lifetime
-_LANE_TABLES: Dict[tuple, str] = {}    # (stride, source entity per entity index) of a lane_read in a world of 32 / 64 rows -> symbol, same lifetime
-_WINDOWS: Dict[int, tuple] = {}    # window slot -> (rows, width, head slot) of the program being emitted (dsl.Window)
 # Device layout of a window column by executor size, fixed when the program is built (HipExec knows its row count; the object
 # says which one it was built for, bit 30 of sixdof_custom_column_widths): from this many entities on it is ELEMENT-major, [rows*width][n] — a wave reads 512 contiguous bytes per element (65,536 rockets:
 # 0.221 -> 0.158 ms per tick, 4.8 TB/s of window traffic); below, each entity's window is contiguous like in the reference's
 # column — a small batch is a chain of dependent loads per lane and the neighbouring elements it finds in cache matter more
 # (8,192 rockets: 0.070 ms per tick against 0.088 element-major).
 WINDOW_SOA_MIN_ROWS = 32768
-_WINDOW_SOA = [False]                # layout of the program being emitted
 # Register columns of a program on the device: [n][w] (the reference's rows: a lane reads its w values at a stride of w
 # elements, so every load instruction of a wave touches w times the cache lines it uses) or ELEMENT-MAJOR [w][n] (a wave's
 # load of element j is 64 consecutive values: two full 128-byte lines per f32 instruction).  The generator owns this layout
 # (include/sixdof_hip.h: the object exports it, bit 29 of its column widths); executors of COLUMN_SOA_MIN_ROWS rows or more
 # without entity-set joins / folds use the element-major one (exec.py transposes at upload / download).
 COLUMN_SOA_MIN_ROWS = 32768
-_COLUMN_SOA = [False]
 
 
-def _col_ptr(k: int, w: int, row: str, const: bool = True) -> str:
-    """`g` such that element j of this lane's row of program column k is `g[_col_idx(j)]`."""
+def _col_ptr(u: _Unit, k: int, w: int, row: str, const: bool = True) -> str:
+    """`g` such that element j of this lane's row of program column k is `g[_col_idx(u, j)]`."""
     ty = "const T*" if const else "T*"
     cast = f"static_cast<{ty}>(P.model_cols[{k}])"
-    return f"{ty} g = {cast} + (size_t){row}" + ("" if _COLUMN_SOA[0] else f" * {w}") + ";"
+    return f"{ty} g = {cast} + (size_t){row}" + ("" if u.column_soa else f" * {w}") + ";"
 
 
-def _col_idx(j: int) -> str:
-    return f"(size_t){j} * P.n" if _COLUMN_SOA[0] else str(j)
+def _col_idx(u: _Unit, j: int) -> str:
+    return f"(size_t){j} * P.n" if u.column_soa else str(j)
 
 
 
@@ -110,8 +154,8 @@ class _Emitter:
     blocks of one function as long as none of the leaves they read has been written in between (two systems that both
     convert the same position to geodetic coordinates share the conversion)."""
 
-    def __init__(self, leaves: Dict[str, str]):
-        self.leaves = leaves
+    def __init__(self, u: _Unit, leaves: Dict[str, str]):
+        self.u, self.leaves = u, leaves
         self.names: Dict[int, str] = {}      # id(Expr) -> C++ temporary holding it
         self.keep: Dict[int, dsl.Expr] = {}   # keeps the Exprs alive so ids stay unique
         self.deps: Dict[int, frozenset] = {}
@@ -157,11 +201,12 @@ class _Emitter:
     def block(self, assign, indent: str = "        ", written: Sequence[str] = (), scoped: bool = False) -> List[str]:
         """assign: [(lvalue, Expr)]; written: the leaf names those lvalues correspond to (invalidates dependants);
         scoped: the block sits inside a conditional — temporaries created in it must not be reused outside."""
+        u = self.u
         lines: List[str] = []
         before = set(self.names)
         outer = {"parent": None, "names": self.names, "lines": lines, "vars": {}, "varset": frozenset(), "indent": indent}
         guards: Dict[int, tuple] = {}      # id(select) -> (guarded arm index, member node ids, selects of the group): _plan_guards
-        fused: Dict[int, int] = {}         # id(add / sub) -> which argument is the product folded into it (_FUSE_FMA)
+        fused: Dict[int, int] = {}         # id(add / sub) -> which argument is the product folded into it (_Unit.fuse_fma)
 
         def rhs_of(e: dsl.Expr, a: List[str]) -> str:
             if e.op == "div":
@@ -177,7 +222,7 @@ class _Emitter:
             if e.op == "select":
                 return f"{a[0]} ? {a[1]} : {a[2]}"
             if e.op == "interp":
-                stem = _TABLES.setdefault(e.value, f"tab{len(_TABLES)}")
+                stem = u.tables.setdefault(e.value, f"tab{len(u.tables)}")
                 xs = e.value[0]
                 step = (xs[-1] - xs[0]) / (len(xs) - 1)
                 uniform = len(xs) > 32 and step > 0 and all(abs((b - a_) - step) <= 1e-9 * step for a_, b in zip(xs, xs[1:]))
@@ -186,7 +231,7 @@ class _Emitter:
                 return f"m_interp<T, {len(xs)}>({a[0]}, {stem}_x, {stem}_f)"
             if e.op == "gather":    # constant table in device memory (dsl.gather): jax's index normalisation + clamp in m_gather
                 key, col, n, w = e.value
-                stem = _GATHERS.setdefault(key, f"gtab{len(_GATHERS)}")
+                stem = u.gathers.setdefault(key, f"gtab{len(u.gathers)}")
                 return f"m_gather<T>({stem}, {a[0]}, {n}, {w}, {col})"
             if e.op == "wload":     # logical row a[1] of the ring whose oldest row sits at physical row a[0]
                 slot, rows, width, j, _ = e.value
@@ -201,7 +246,7 @@ class _Emitter:
                 if len(set(table)) == 1:
                     src = f"static_cast<int>((threadIdx.x & ~{stride - 1}u) + {table[0]}u)"
                 elif stride > 16:       # worlds of 32 or 64 rows: a byte per entity in constant memory (one cached load per read)
-                    stem = _LANE_TABLES.setdefault((int(stride), tuple(int(j) for j in table)), f"ltab{len(_LANE_TABLES)}")
+                    stem = u.lane_tables.setdefault((int(stride), tuple(int(j) for j in table)), f"ltab{len(u.lane_tables)}")
                     src = f"static_cast<int>((threadIdx.x & ~{stride - 1}u) + {stem}[threadIdx.x & {stride - 1}u])"
                 else:
                     packed = sum((int(j) & 15) << (4 * i) for i, j in enumerate(table))
@@ -211,7 +256,7 @@ class _Emitter:
                 # edge slot: stablehlo.py _LaneEval._pick): slot-major bytes in constant memory
                 stride, tables = e.value
                 flat = tuple(int(j) for t in tables for j in t)
-                stem = _LANE_TABLES.setdefault((int(stride), flat), f"ltab{len(_LANE_TABLES)}")
+                stem = u.lane_tables.setdefault((int(stride), flat), f"ltab{len(u.lane_tables)}")
                 return (f"__shfl({a[0]}, static_cast<int>((threadIdx.x & ~{stride - 1}u) + {stem}[static_cast<int>({a[1]}) * {stride} + "
                         f"static_cast<int>(threadIdx.x & {stride - 1}u)]), 64)")
             if e.op == "fbits":     # one 32-bit word of a double's bit pattern (stablehlo.bitcast_convert f64 -> ui64): 1 = high
@@ -286,7 +331,7 @@ class _Emitter:
                     if e.name in s_["vars"]:
                         return s_["vars"][e.name]
                     s_ = s_["parent"]
-                return _leaf_ref(e.name, self.leaves)
+                return _leaf_ref(self.u, e.name, self.leaves)
             # a node that does not depend on this loop's carried values (or, in a guarded region, is not one of its members)
             # belongs to the enclosing scope
             while sc["parent"] is not None and not ((self._deps(e) & sc["varset"]) or id(e) in sc.get("members", ())):
@@ -307,7 +352,7 @@ class _Emitter:
                 self._deps(e)
                 return name
             if e.op == "select" and id(e) in guards:
-                # GUARDED SELECT (opt-in, _GUARD_SELECTS): `where(c, expensive, cheap)` whose expensive arm nobody else needs —
+                # GUARDED SELECT (opt-in, _Unit.guard_selects): `where(c, expensive, cheap)` whose expensive arm nobody else needs —
                 # a sensor's noise draw behind its sample-time test, as a script written for JAX spells a cadence.  The arm's
                 # nodes are emitted inside `if (any lane of the wave wants them)`; the value is the same select.
                 arm, members, group = guards[id(e)]
@@ -332,7 +377,7 @@ class _Emitter:
                 sc["lines"].append(f"{sc['indent']}}}")
                 return sc["names"][id(e)]
             wide = self._is_wide(e)
-            if _RELAXED_EMIT[0] and not wide and e.op == "div" and e.args[0].is_const(1.0):
+            if u.relaxed and not wide and e.op == "div" and e.args[0].is_const(1.0):
                 # RELAXED ARITHMETIC (dsl.relaxed_arithmetic): the shared reciprocal of a denominator is v_rcp_f64 + two Newton steps
                 # (7 instructions against the 11 of an IEEE divide, 1 ulp), and 1 / sqrt(s) the hardware seed + one cubic correction
                 # (spatial.hpp rsqrt_pos: 5 against a library sqrt and a divide)
@@ -348,7 +393,7 @@ class _Emitter:
                 sc["lines"].append(f"{sc['indent']}const T {name} = {rhs};")
                 return name
             if id(e) in fused:
-                # FUSED MULTIPLY-ADD (fast-math builds, _FUSE_FMA): a product whose only use is this sum never becomes a value of
+                # FUSED MULTIPLY-ADD (fast-math builds, _Unit.fuse_fma): a product whose only use is this sum never becomes a value of
                 # its own.  Decided here, per node, so every copy of the tick body the compiler makes rounds the same way (the
                 # compiler's own "fast" contraction fuses whatever lands in one basic block: kernels.hpp).
                 k = fused[id(e)]
@@ -385,7 +430,7 @@ class _Emitter:
         # nodes the outputs need are emitted in the order the user's program created them (`Expr.seq`; arguments always
         # precede their users), which is the order a person would have written the code in: the same step then peaks at a
         # few matrices' worth of registers.  (Nodes inside loop bodies keep their own scopes and are emitted with their loop.)
-        need, stack = {}, ([e for _, e in assign] if (_EMIT_ORDER[0] in ("program", "pressure") or _GUARD_SELECTS[0] or _FUSE_FMA[0]) else [])
+        need, stack = {}, ([e for _, e in assign] if (u.order in ("program", "pressure") or u.guard_selects or u.fuse_fma) else [])
         while stack:
             x = stack.pop()
             if id(x) in need or x.op in ("const", "leaf"):
@@ -395,11 +440,11 @@ class _Emitter:
                 continue
             need[id(x)] = x
             stack.extend(x.args)
-        if _GUARD_SELECTS[0]:
+        if u.guard_selects:
             guards.update(_plan_guards(need, [e for _, e in assign], set(self.names)))
         guarded = set().union(*[g[1] for g in guards.values()]) if guards else set()
         folded = set()
-        if _FUSE_FMA[0]:
+        if u.fuse_fma:
             n_users: Dict[int, int] = {}
             for n_ in need.values():
                 for a_ in n_.args:
@@ -414,12 +459,12 @@ class _Emitter:
                             fused[id(n_)] = k
                             folded.add(id(m))
                             break
-        if _ESTIMATE[0] is not None and _EMIT_ORDER[0] != "pressure" and need:
-            _pressure_order(need, [e for _, e in assign])          # for its estimates only
-        if _EMIT_ORDER[0] == "pressure":
-            ordered = _pressure_order(need, [e for _, e in assign])
+        if u.estimate is not None and u.order != "pressure" and need:
+            _pressure_order(u, need, [e for _, e in assign])          # for its estimates only
+        if u.order == "pressure":
+            ordered = _pressure_order(u, need, [e for _, e in assign])
         else:
-            ordered = sorted(need.values(), key=lambda n_: n_.seq) if _EMIT_ORDER[0] == "program" else ()
+            ordered = sorted(need.values(), key=lambda n_: n_.seq) if u.order == "program" else ()
         for x in ordered:
             if id(x) not in guarded and id(x) not in folded:
                 ref(x)
@@ -442,7 +487,7 @@ class _Emitter:
         return lines
 
 
-def _pressure_order(need: Dict[int, "dsl.Expr"], roots: Sequence["dsl.Expr"]) -> List["dsl.Expr"]:
+def _pressure_order(u: _Unit, need: Dict[int, "dsl.Expr"], roots: Sequence["dsl.Expr"]) -> List["dsl.Expr"]:
     """REGISTER-PRESSURE ORDER.  Greedy list scheduling of a block's nodes: among the nodes whose arguments exist, the one that
     ends the most live ranges comes next (the last user of an argument frees its register); ties go to the node the DEMAND order
     (depth-first from the outputs) would reach first, so nothing that ends no range is started before something needs it.
@@ -483,11 +528,11 @@ def _pressure_order(need: Dict[int, "dsl.Expr"], roots: Sequence["dsl.Expr"]) ->
                 pos[id(n_)] = len(pos)
     for i in need:
         pos.setdefault(i, len(pos))
-    if _ESTIMATE[0] is not None:       # build(): how many values each emission order keeps live at its worst in this block
+    if u.estimate is not None:       # build(): how many values each emission order keeps live at its worst in this block
         by_seq = sorted(need.values(), key=lambda n_: n_.seq)
         by_pos = sorted(need.values(), key=lambda n_: pos[id(n_)])
         for name_, order_ in (("program", by_seq), ("demand", by_pos)):
-            _ESTIMATE[0][name_] = max(_ESTIMATE[0].get(name_, 0), _peak_live(order_, deps, dict(users)))
+            u.estimate[name_] = max(u.estimate.get(name_, 0), _peak_live(order_, deps, dict(users)))
 
     def score(i):
         return sum(1 for a in {id(a) for a in deps(need[i])} if users[a] == 1)
@@ -504,7 +549,7 @@ def _pressure_order(need: Dict[int, "dsl.Expr"], roots: Sequence["dsl.Expr"]) ->
             pending[c] -= 1
             if pending[c] == 0:
                 ready.add(c)
-    if _ESTIMATE[0] is not None:
+    if u.estimate is not None:
         users2: Dict[int, int] = {}
         for i, x in need.items():
             for a in {id(a) for a in deps(x)}:
@@ -512,12 +557,8 @@ def _pressure_order(need: Dict[int, "dsl.Expr"], roots: Sequence["dsl.Expr"]) ->
         for r in roots:
             if id(r) in need:
                 users2[id(r)] = users2.get(id(r), 0) + 1
-        _ESTIMATE[0]["pressure"] = max(_ESTIMATE[0].get("pressure", 0), _peak_live(order, deps, users2))
+        u.estimate["pressure"] = max(u.estimate.get("pressure", 0), _peak_live(order, deps, users2))
     return order
-
-
-_ESTIMATE: List[Optional[Dict[str, int]]] = [None]
-_EXPECT_SCRATCH = [False]      # the variant being compiled keeps state in private memory by design ("memory")
 
 
 def _peak_live(order, deps, users: Dict[int, int]) -> int:
@@ -534,13 +575,6 @@ def _peak_live(order, deps, users: Dict[int, int]) -> int:
     return peak
 
 
-# Opt-in (codegen.generate_source(..., guard_selects=True) / SIXDOF_GUARD_SELECTS=1): see _Emitter.block, "GUARDED SELECT".
-_GUARD_SELECTS = [False]
-# Fast-math builds fold single-use products into the sums that consume them (see _Emitter.block, "FUSED MULTIPLY-ADD");
-# SIXDOF_FUSE_FMA=0 keeps them apart (A/B).  Exact builds never fuse: a reference evaluates every node to a rounded value.
-_FUSE_FMA = [False]
-# programs traced under dsl.relaxed_arithmetic (TracedProgram.fp_contract): see _Emitter.block `m_rcp_relaxed`
-_RELAXED_EMIT = [False]
 _GUARD_MIN_COST = 40
 _NODE_COST = {"lane_read": 8, "lane_read_dyn": 10, "threefry": 90, "erfinv": 120, "sin": 12, "cos": 12, "tan": 20, "exp": 10, "log": 10, "pow": 25, "atan2": 27, "asin": 20,
               "acos": 20, "hypot": 12, "div": 4, "sqrt": 4, "interp": 30, "cbrt": 20, "sinh": 20, "cosh": 20, "erfc": 40, "log1p": 15,
@@ -642,32 +676,13 @@ def _plan_guards(need: Dict[int, "dsl.Expr"], roots: Sequence["dsl.Expr"], avail
     return out
 
 
-def emit_block(assign, leaves: Dict[str, str], indent: str = "        ") -> List[str]:
-    return _Emitter(leaves).block(assign, indent)
+def emit_block(u: _Unit, assign, leaves: Dict[str, str], indent: str = "        ") -> List[str]:
+    return _Emitter(u, leaves).block(assign, indent)
 
 
-def emit_apply(tp: dsl.TracedPipe) -> List[str]:
+def emit_apply(u: _Unit, tp: dsl.TracedPipe) -> List[str]:
     names = ["F.tau_w.x", "F.tau_w.y", "F.tau_w.z", "F.f.x", "F.f.y", "F.f.z", "F.tau_b.x", "F.tau_b.y", "F.tau_b.z"]
-    return emit_block(list(zip(names, tp.outputs)), _APPLY_LEAVES)
-
-
-# Fallback layout of a program whose state does not fit a wave's 512 registers (the f64 Falcon 9 closed loop: ~250 doubles
-# of component state + the temporaries of 20 systems): the register image `Regs` is declared `volatile`, i.e. it lives in
-# the lane's private (scratch) memory and every access is a real load / store — deliberate, compiler-independent placement
-# instead of register-allocator spills (a spilling build miscomputed on gfx950 before, see _compile).  The launch-level
-# column load / store and the cold-column scheme stay as they are.  Costs scratch traffic (L1 / L2 resident) on every
-# access: a parity build, not a fast one.  build() switches to it by itself when no register-resident build is spill-free.
-# (Tried first: keeping every column in HBM and wrapping each system in loads / stores — the optimiser forwards the stored
-# values to the next system's loads and the live set stays where it was: 150+ spills with every flag set.)
-_MEMORY_COLUMNS = [False]
-# Order in which a block's nodes are emitted: "program" = the order the user's code created them (see _Emitter.block),
-# "demand" = depth-first from the outputs, each value right before its first use.  Program order is tried first; a
-# machine-generated DAG with no meaningful creation order (the fuzzer's random programs) can do better on demand.
-_EMIT_ORDER = ["program"]
-# Last resort: the tick body compiled as a real function (step_kernel.hpp SIXDOF_TICK_OUT_OF_LINE) — for programs whose
-# TEMPORARIES, not state, overflow the register file (a fuzz program of 200 inlined f64 libm calls: 43 values live in source
-# order, 650 registers after LLVM's allocation across its 600 basic blocks, whatever the flags).
-_TICK_OUT_OF_LINE = [False]
+    return emit_block(u, list(zip(names, tp.outputs)), _APPLY_LEAVES)
 
 
 def _col_slots(names) -> set:
@@ -732,9 +747,9 @@ def _store_only_slots(pipe_tp, pre, post, transient) -> Dict[int, int]:
     return {k: w for k, w in transient.items() if k not in read}
 
 
-def _emit_systems(systems, cold: Optional[Dict[int, int]] = None, store_only: Optional[Dict[int, int]] = None) -> str:
+def _emit_systems(u: _Unit, systems, cold: Optional[Dict[int, int]] = None, store_only: Optional[Dict[int, int]] = None) -> str:
     out = []
-    em = _Emitter(_SYSTEM_LEAVES)
+    em = _Emitter(u, _SYSTEM_LEAVES)
     cold = cold or {}
     store_only = store_only or {}
     cadence = lambda s: f"tick % {s.every}ull == {s.phase}ull" + (f" || tick == {s.also_at}ull" if s.also_at is not None else "")
@@ -750,17 +765,17 @@ def _emit_systems(systems, cold: Optional[Dict[int, int]] = None, store_only: Op
             ahead[cadence(s)][0].append(s.name)
             ahead[cadence(s)][1].update(reads_of(s))
     for cond, (names, slots) in ahead.items():
-        ld = "".join(f"            if (c_act) {{ {_col_ptr(k, cold[k], 'c_row')} "
-                     + " ".join(f"r.c{k}[{j}] = g[{_col_idx(j)}];" for j in range(cold[k])) + " }\n" for k in sorted(slots))
+        ld = "".join(f"            if (c_act) {{ {_col_ptr(u, k, cold[k], 'c_row')} "
+                     + " ".join(f"r.c{k}[{j}] = g[{_col_idx(u, j)}];" for j in range(cold[k])) + " }\n" for k in sorted(slots))
         out.append(f"        if ({cond}) {{  // cold columns of {', '.join(names)}\n{ld}        }}")
     for s in systems:
-        assign = [(_leaf_ref(t, _SYSTEM_LEAVES), e) for t, e in s.assign]
+        assign = [(_leaf_ref(u, t, _SYSTEM_LEAVES), e) for t, e in s.assign]
         written = [t for t, _ in s.assign]
         if s.every > 1:     # wave-uniform cadence branch: its temporaries stay inside
             body = "\n".join(em.block(assign, "            ", written, scoped=True))
             w_slots = sorted(_col_slots(written) & set(cold))
-            st = "".join(f"\n            if (c_act) {{ {_col_ptr(k, cold[k], 'c_row', False)} "
-                         + " ".join(f"g[{_col_idx(j)}] = r.c{k}[{j}];" for j in range(cold[k])) + " }" for k in w_slots)
+            st = "".join(f"\n            if (c_act) {{ {_col_ptr(u, k, cold[k], 'c_row', False)} "
+                         + " ".join(f"g[{_col_idx(u, j)}] = r.c{k}[{j}];" for j in range(cold[k])) + " }" for k in w_slots)
             out.append(f"        if ({cadence(s)}) {{  // {s.name}\n{body}{st}\n        }}")
         else:
             late = [(t, e) for t, e in s.assign if _col_slots([t]) & set(store_only)]
@@ -772,17 +787,17 @@ def _emit_systems(systems, cold: Optional[Dict[int, int]] = None, store_only: Op
                 # columns' own P.model_hist pointers costs a scalar load and its wait per block and tick)
                 lazy = (f"        if (tick == P.tick0 + P.n_ticks || P.hist_ring != 0u) {{"
                         f"  // store-only columns of {s.name}\n"
-                        + "\n".join(em.block([(_leaf_ref(t, _SYSTEM_LEAVES), e) for t, e in late], "            ", [t for t, _ in late], scoped=True))
+                        + "\n".join(em.block([(_leaf_ref(u, t, _SYSTEM_LEAVES), e) for t, e in late], "            ", [t for t, _ in late], scoped=True))
                         + "\n        }\n")
-                assign = [(_leaf_ref(t, _SYSTEM_LEAVES), e) for t, e in s.assign if not (_col_slots([t]) & set(store_only))]
+                assign = [(_leaf_ref(u, t, _SYSTEM_LEAVES), e) for t, e in s.assign if not (_col_slots([t]) & set(store_only))]
                 written = [t for t, _ in s.assign if not (_col_slots([t]) & set(store_only))]
             body = lazy + "\n".join(em.block(assign, "        ", written))
             w_slots = sorted(_col_slots(written) & set(cold))
             r_slots = sorted((_col_slots(dsl._leaves_of([e for _, e in s.assign])) | set(w_slots)) & set(cold))
-            ld = "".join(f"        if (c_act) {{ {_col_ptr(k, cold[k], 'c_row')} "
-                         + " ".join(f"r.c{k}[{j}] = g[{_col_idx(j)}];" for j in range(cold[k])) + " }\n" for k in r_slots)
-            st = "".join(f"\n        if (c_act) {{ {_col_ptr(k, cold[k], 'c_row', False)} "
-                         + " ".join(f"g[{_col_idx(j)}] = r.c{k}[{j}];" for j in range(cold[k])) + " }" for k in w_slots)
+            ld = "".join(f"        if (c_act) {{ {_col_ptr(u, k, cold[k], 'c_row')} "
+                         + " ".join(f"r.c{k}[{j}] = g[{_col_idx(u, j)}];" for j in range(cold[k])) + " }\n" for k in r_slots)
+            st = "".join(f"\n        if (c_act) {{ {_col_ptr(u, k, cold[k], 'c_row', False)} "
+                         + " ".join(f"g[{_col_idx(u, j)}] = r.c{k}[{j}];" for j in range(cold[k])) + " }" for k in w_slots)
             out.append(f"        // {s.name}\n{ld}{body}{st}")
     return "\n".join(out)
 
@@ -957,14 +972,14 @@ __device__ __forceinline__ T m_interp_uniform(T x, const double (&xp)[N], const 
 '''
 
 
-def _emit_tables() -> str:
+def _emit_tables(u: _Unit) -> str:
     out = []
-    for key, stem in _GATHERS.items():      # row-major [rows, cols], doubles whatever the program's dtype (read through m_gather)
+    for key, stem in u.gathers.items():      # row-major [rows, cols], doubles whatever the program's dtype (read through m_gather)
         t = dsl._GATHER_TABLES[key]
         out.append(f"__device__ const double {stem}[{t.size}] = {{{', '.join(repr(float(v)) for v in t.reshape(-1))}}};")
-    for (stride, table), stem in _LANE_TABLES.items():
+    for (stride, table), stem in u.lane_tables.items():
         out.append(f"__device__ const unsigned char {stem}[{len(table)}] = {{{', '.join(str(j) for j in table)}}};")
-    for (xs, fs), stem in _TABLES.items():
+    for (xs, fs), stem in u.tables.items():
         out.append(f"__device__ const double {stem}_x[{len(xs)}] = {{{', '.join(repr(v) for v in xs)}}};")
         out.append(f"__device__ const double {stem}_f[{len(fs)}] = {{{', '.join(repr(v) for v in fs)}}};")
     return "\n".join(out)
@@ -1003,46 +1018,46 @@ def _slots_of(systems, extra_exprs=()) -> set:
     return {int(n[1:].split("_")[0]) for n in names if n[0] == "c" and "_" in n and n[1:].split("_")[0].isdigit()}
 
 
-def _emit_pipe_struct(name: str, tp, pipe_tp, pre, post, used: Optional[set], pre_reads_accel: bool, n_aux: int, body_dead: bool = False) -> str:
+def _emit_pipe_struct(u: _Unit, name: str, tp, pipe_tp, pre, post, used: Optional[set], pre_reads_accel: bool, n_aux: int, body_dead: bool = False) -> str:
     """One PIPE struct of csrc/step_kernel.hpp: effector stage from `pipe_tp` (None: no effectors), `pre` / `post` hooks from
     traced systems.  `used`: the program column slots this struct keeps in registers (None: all of tp.columns)."""
-    body = "\n".join(emit_apply(pipe_tp)) if pipe_tp is not None else ""
+    body = "\n".join(emit_apply(u, pipe_tp)) if pipe_tp is not None else ""
     apply_loads = ""
     model = ""
     is_prog = tp is not None and isinstance(tp, dsl.TracedProgram)
     win_setup = ""
     if is_prog:
         cols = tp.columns
-        reg_cols = [(k, w) for k, (_, w) in enumerate(cols) if k not in _WINDOWS and (used is None or k in used)]     # windows stay in HBM
+        reg_cols = [(k, w) for k, (_, w) in enumerate(cols) if k not in u.windows and (used is None or k in used)]     # windows stay in HBM
         written = sorted(_slots_of(pre + post) & {int(t[1:].split("_")[0]) for s_ in pre + post for t in s_.written if t[0] == "c"}) \
             if used is not None else list(tp.written_slots)
         cold = _cold_slots(tp, pipe_tp, pre, post, reg_cols)
         transient = _transient_slots(pipe_tp, pre, post, reg_cols, cold) if used is None else {}
         store_only = _store_only_slots(pipe_tp, pre, post, transient)
-        vol = "volatile " if _MEMORY_COLUMNS[0] else ""
+        vol = "volatile " if u.memory_columns else ""
         regs = "\n".join(f"        {vol}T c{k}[{w}];" + ("   // cold: lives in its HBM column between cadence blocks" if k in cold else "") for k, w in reg_cols)
         # wave-uniform columns (TracedProgram.uniform_slots): every lane reads the first row of the wavefront's block — one line per
         # wave instead of one value per row; stores stay per row, so every row keeps holding the value
         uni = set(getattr(tp, "uniform_slots", ()) or ()) if used is None else set()       # (either device layout: the row index alone changes)
         loads = "\n".join(
-            f"            {{ {_col_ptr(k, w, '(row & ~uint32_t(kWave - 1))' if k in uni else 'row')} "
-            + " ".join(f"r.c{k}[{j}] = col_ld<POL>(g + {_col_idx(j)});" for j in range(w)) + " }" for k, w in reg_cols if k not in cold and k not in transient)
+            f"            {{ {_col_ptr(u, k, w, '(row & ~uint32_t(kWave - 1))' if k in uni else 'row')} "
+            + " ".join(f"r.c{k}[{j}] = col_ld<POL>(g + {_col_idx(u, j)});" for j in range(w)) + " }" for k, w in reg_cols if k not in cold and k not in transient)
         # element by element, not a loop: a loop the optimiser does not unroll (-O1, the low-register-pressure fallback build)
         # indexes the array dynamically, which pins the whole register file image in scratch memory
         zero = " ".join(" ".join(f"r.c{k}[{j}] = T(0);" for j in range(w)) for k, w in reg_cols)
         stores = "\n".join(
-            f"        {{ {_col_ptr(k, cols[k][1], 'row', False)} "
-            + " ".join(f"col_st<POL>(g + {_col_idx(j)}, r.c{k}[{j}]);" for j in range(cols[k][1])) + " }" for k in written if k not in cold and k not in transient)
+            f"        {{ {_col_ptr(u, k, cols[k][1], 'row', False)} "
+            + " ".join(f"col_st<POL>(g + {_col_idx(u, j)}, r.c{k}[{j}]);" for j in range(cols[k][1])) + " }" for k in written if k not in cold and k not in transient)
         transient_stores = ""
         if transient:
             transient_stores = ("\n        if (tick == P.tick0 + P.n_ticks && c_act) {   // last tick of the launch: the per-tick (transient) columns\n"
-                                + "".join(f"            {{ {_col_ptr(k, w, 'c_row', False)} " + " ".join(f"g[{_col_idx(j)}] = r.c{k}[{j}];" for j in range(w)) + " }\n"
+                                + "".join(f"            {{ {_col_ptr(u, k, w, 'c_row', False)} " + " ".join(f"g[{_col_idx(u, j)}] = r.c{k}[{j}];" for j in range(w)) + " }\n"
                                           for k, w in sorted(transient.items()))
                                 + "        }")
         records = "\n".join(
             (f"        if (P.model_hist[{k}]) {{ T* g = static_cast<T*>(P.model_hist[{k}]) + (slot * P.n + row) * {w}; "
-             f"const T* g0 = static_cast<const T*>(P.model_cols[{k}]) + (size_t)row" + ("" if _COLUMN_SOA[0] else f" * {w}") + "; "
-             + " ".join(f"g[{j}] = g0[{_col_idx(j)}];" for j in range(w)) + " }") if k in cold else
+             f"const T* g0 = static_cast<const T*>(P.model_cols[{k}]) + (size_t)row" + ("" if u.column_soa else f" * {w}") + "; "
+             + " ".join(f"g[{j}] = g0[{_col_idx(u, j)}];" for j in range(w)) + " }") if k in cold else
             (f"        if (P.model_hist[{k}]) {{ T* g = static_cast<T*>(P.model_hist[{k}]) + (slot * P.n + row) * {w}; "
              + " ".join(f"g[{j}] = r.c{k}[{j}];" for j in range(w)) + " }") for k, w in reg_cols)
         cold_setup = ("        const uint32_t c_row = blockIdx.x * kWave + threadIdx.x;\n        const bool c_act = c_row < P.n;\n" if (cold or transient) else "")
@@ -1050,18 +1065,18 @@ def _emit_pipe_struct(name: str, tp, pipe_tp, pre, post, used: Optional[set], pr
             a_slots = sorted(_col_slots(dsl._leaves_of(list(pipe_tp.outputs))) & set(cold))
             if a_slots:      # memory-resident columns the effector stage reads (`r` is the kernel's own register image)
                 apply_loads = (cold_setup + "        auto& rw = const_cast<R&>(r);\n" + "".join(
-                    f"        if (c_act) {{ {_col_ptr(k, cold[k], 'c_row')} "
-                    + " ".join(f"rw.c{k}[{j}] = g[{_col_idx(j)}];" for j in range(cold[k])) + " }\n" for k in a_slots))
-        if _WINDOWS:
+                    f"        if (c_act) {{ {_col_ptr(u, k, cold[k], 'c_row')} "
+                    + " ".join(f"rw.c{k}[{j}] = g[{_col_idx(u, j)}];" for j in range(cold[k])) + " }\n" for k in a_slots))
+        if u.windows:
             # one lane = one entity, a workgroup is one wave (step_kernel.hpp).  Element e of this lane's window sits at
             # W[e * w_n]: w_n = n for the element-major layout of large executors, 1 (a compile-time constant, so the addresses
             # fold) for the entity-major one (see WINDOW_SOA_MIN_ROWS).  Lanes past the last row read the last row's elements and store nothing.
             win_setup = ("        const uint32_t w_row = blockIdx.x * kWave + threadIdx.x;\n"
                          "        const bool w_act = w_row < P.n;\n"
-                         + ("        const size_t w_n = P.n;                    // element-major: stride between two elements of one entity\n" if _WINDOW_SOA[0]
+                         + ("        const size_t w_n = P.n;                    // element-major: stride between two elements of one entity\n" if u.window_soa
                             else "        constexpr size_t w_n = 1;                  // entity-major: an entity's window is contiguous\n")
-                         + "".join(f"        T* const W{k} = static_cast<T*>(P.model_cols[{k}]) + (size_t)(w_act ? w_row : P.n - 1) * (size_t){1 if _WINDOW_SOA[0] else rows * width};\n"
-                                   for k, (rows, width, _) in _WINDOWS.items()))
+                         + "".join(f"        T* const W{k} = static_cast<T*>(P.model_cols[{k}]) + (size_t)(w_act ? w_row : P.n - 1) * (size_t){1 if u.window_soa else rows * width};\n"
+                                   for k, (rows, width, _) in u.windows.items()))
         writes_inertia = any(s_.writes_inertia for s_ in pre + post)
         model = f'''
     static constexpr bool kHasModel = true;
@@ -1090,13 +1105,13 @@ def _emit_pipe_struct(name: str, tp, pipe_tp, pre, post, used: Optional[set], pr
     __device__ static __forceinline__ void pre(const StepParams& P, uint64_t tick, Regs<T>& r, Quat<T>& q, Vec3<T>& p,
                                                Spatial<T>& v, Vec3<T>& I, T& mass, const Spatial<T>& accel) {{
         (void)P; (void)tick; (void)accel;
-{win_setup}{cold_setup}{_emit_systems(pre, cold, store_only)}
+{win_setup}{cold_setup}{_emit_systems(u, pre, cold, store_only)}
     }}
     template <class T>
     __device__ static __forceinline__ void post(const StepParams& P, uint64_t tick, Regs<T>& r, Quat<T>& q, Vec3<T>& p,
                                                 Spatial<T>& v, Vec3<T>& I, T& mass, const Spatial<T>& accel) {{
         (void)P; (void)tick; (void)accel;
-{win_setup}{cold_setup}{_emit_systems(post, cold, store_only)}{transient_stores}
+{win_setup}{cold_setup}{_emit_systems(u, post, cold, store_only)}{transient_stores}
     }}'''
     wt = pipe_tp.world_torque if pipe_tp is not None else False
     bt = pipe_tp.body_torque if pipe_tp is not None else False
@@ -1140,7 +1155,7 @@ def _graph_fold_kinds(outputs, w: int):
     return kinds
 
 
-def _emit_fold_stage(fs: "dsl.TracedFoldStage") -> str:
+def _emit_fold_stage(u: _Unit, fs: "dsl.TracedFoldStage") -> str:
     """A stand-alone fold inside a program (dsl.TracedFoldStage): one lane per SOURCE folds its out-edges in spawn order into
     the scratch column, a second kernel commits scratch -> out on source rows (every fold reads the values from before it
     ran).  Components come from the program's columns (P.model_cols) or the Body columns; the CSR is baked in."""
@@ -1163,7 +1178,7 @@ def _emit_fold_stage(fs: "dsl.TracedFoldStage") -> str:
         for k in range(wn):
             leaves[f"b{i}_{k}"] = f"b{i}[{k}]"
         loads_b.append(f"        const T* b{i} = {ptr(n, slot)} + (size_t)(base + {dst_of('e')}) * {wn};")
-    body = "\n".join(emit_block([(f"acc[{k}]", e) for k, e in enumerate(fs.traced.outputs)], leaves, indent="        "))
+    body = "\n".join(emit_block(u, [(f"acc[{k}]", e) for k, e in enumerate(fs.traced.outputs)], leaves, indent="        "))
     init = ", ".join(f"T({v!r})" for v in f.init)
     nl = "\n"
     # One lane per source folds its out-edges in order: a chain of dependent gathers, ~350 ns a trip with nothing to hide it behind
@@ -1318,25 +1333,21 @@ __device__ __forceinline__ double m_erfinv_fast(double u) {
 
 
 def generate_source(tp, dtype: str, integrator: int, fast_math: bool = False, window_soa: bool = False,
-                    column_soa: bool = False, guard_selects: Optional[bool] = None) -> str:
+                    column_soa: bool = False, guard_selects: Optional[bool] = None, policy: Optional[int] = None) -> str:
     """tp: dsl.TracedPipe (effectors only) or dsl.TracedProgram (pre | six_dof(effectors) | post).
     fast_math: f32 only — hardware transcendentals / reciprocal division in the generated user code (see _PRELUDE).
     window_soa: window columns are element-major on the device (executors of WINDOW_SOA_MIN_ROWS entities or more).
     guard_selects: expensive `where` arms nobody else needs are computed behind a wave-level branch (_Emitter.block);
-    None = the SIXDOF_GUARD_SELECTS environment switch (off unless "1")."""
-    _GUARD_SELECTS[0] = (os.environ.get("SIXDOF_GUARD_SELECTS", "") == "1") if guard_selects is None else bool(guard_selects)
-    _FUSE_FMA[0] = bool(fast_math) and os.environ.get("SIXDOF_FUSE_FMA", "1") != "0"
-    _RELAXED_EMIT[0] = (isinstance(tp, dsl.TracedProgram) and bool(getattr(tp, "fp_contract", False))
-                        and os.environ.get("SIXDOF_RELAXED_IEEE_RCP", "") != "1")      # A/B: the shared reciprocals as IEEE divides
-    _WINDOW_SOA[0] = bool(window_soa)
-    _COLUMN_SOA[0] = bool(column_soa)
-    if column_soa and isinstance(tp, dsl.TracedProgram) and tp.fold_stages:
+    None = the SIXDOF_GUARD_SELECTS environment switch (off unless "1").
+    policy: instantiate the step kernel for this cache policy only (0, 1 or 9: policy_for); None = all three."""
+    return _source(tp, dtype, integrator, fast_math, _unit(tp, "program", fast_math, window_soa, column_soa, guard_selects, policy))
+
+
+def _source(tp, dtype: str, integrator: int, fast_math: bool, u: _Unit) -> str:
+    if u.column_soa and isinstance(tp, dsl.TracedProgram) and tp.fold_stages:
         raise ValueError("element-major program columns are not available for programs with stand-alone folds")
     if fast_math and dtype != "float32":
         raise ValueError("fast_math applies to float32 programs only")
-    _TABLES.clear()
-    _GATHERS.clear()
-    _LANE_TABLES.clear()
     T = {"float64": "double", "float32": "float"}[dtype]
     integ = {0: "kRk4", 1: "kSemiImplicit", 2: "kNone"}[integrator]
     is_prog = isinstance(tp, dsl.TracedProgram)
@@ -1350,19 +1361,17 @@ def generate_source(tp, dtype: str, integrator: int, fast_math: bool = False, wi
     rows_multiple = lane_stride(tp) if is_prog else 1
     rows_export = (f"// a world of this program is {rows_multiple} consecutive rows (its entities exchange data inside the wavefront)\n"
                    f'extern "C" unsigned sixdof_custom_rows_multiple() {{ return {rows_multiple}u; }}\n\n') if rows_multiple > 1 else ""
-    _WINDOWS.clear()
     col_widths = "{0u}"
     if is_prog:
         names_ = [c for c, _ in tp.columns]
         for wname, (wslot, wrows, wwidth) in tp.windows.items():
-            _WINDOWS[wslot] = (wrows, wwidth, names_.index(wname + "#head"))
-        col_widths = "{" + ", ".join(f"{w}u" + ((" | 0x80000000u" + (" | 0x40000000u" if window_soa else "")) if k in _WINDOWS else
-                                                 (" | 0x20000000u" if column_soa else ""))
+            u.windows[wslot] = (wrows, wwidth, names_.index(wname + "#head"))
+        col_widths = "{" + ", ".join(f"{w}u" + ((" | 0x80000000u" + (" | 0x40000000u" if u.window_soa else "")) if k in u.windows else
+                                                 (" | 0x20000000u" if u.column_soa else ""))
                                       for k, (_, w) in enumerate(tp.columns)) + "}"
     names = ", ".join(e.__name__ for e in pipe_tp.effectors)
     fast = "#define SIXDOF_FAST_MATH 1\n" if fast_math else ""
-    only = _ONLY_POLICY[0]
-    if only is None:
+    if u.policy is None:
         launch_k = lambda pipe, ig, params: (
             f"    if (({params}.streaming & 255u) == kPolNt) hipLaunchKernelGGL((sixdof_step_kernel<{T}, {ig}, {pipe}, kPolNt>), grid, dim3(kWave), 0, s, {params});\n"
             f"    else if (({params}.streaming & 255u) == kPolNtStores || ({params}.streaming & 255u) == kPolSc1Stores) hipLaunchKernelGGL((sixdof_step_kernel<{T}, {ig}, {pipe}, kPolNtStores>), grid, dim3(kWave), 0, s, {params});\n"
@@ -1371,7 +1380,7 @@ def generate_source(tp, dtype: str, integrator: int, fast_math: bool = False, wi
         # ONE cache-policy instantiation (build(policy=...)): the executor's size class is known when its program is built, a
         # policy only changes cache hints (never values), and each instantiation of the step kernel costs a third of the device
         # compile — so an object built for an executor carries the one it will be launched with
-        pname = {0: "kPolPlain", 1: "kPolNtStores", 9: "kPolNt"}[only]
+        pname = {0: "kPolPlain", 1: "kPolNtStores", 9: "kPolNt"}[u.policy]
         launch_k = lambda pipe, ig, params: (
             f"    hipLaunchKernelGGL((sixdof_step_kernel<{T}, {ig}, {pipe}, {pname}>), grid, dim3(kWave), 0, s, {params});   // built for this executor's cache policy only\n")
     staged = is_prog and bool(tp.fold_stages)
@@ -1408,7 +1417,7 @@ def generate_source(tp, dtype: str, integrator: int, fast_math: bool = False, wi
         tick_free = ("tick" not in dsl._leaves_of(exprs_) and all(s_.every == 1 and s_.also_at is None for s_ in systems_))
     tick_free_bit = " | (1u << 17)" if tick_free else ""
     if not staged:
-        structs = _emit_pipe_struct("PipeCustom", tp if is_prog else None, pipe_tp, tp.pre if is_prog else [], tp.post if is_prog else [],
+        structs = _emit_pipe_struct(u, "PipeCustom", tp if is_prog else None, pipe_tp, tp.pre if is_prog else [], tp.post if is_prog else [],
                                     None, tp.pre_reads_accel if is_prog else False, n_aux, body_dead)
         launch = launch_k("PipeCustom", integ, "(*p)")
         stage_comment = ""
@@ -1444,7 +1453,7 @@ def generate_source(tp, dtype: str, integrator: int, fast_math: bool = False, wi
         for i, c in enumerate(chain):
             if c[0] == "fold":
                 fs = c[1]
-                parts.append(_emit_fold_stage(fs))
+                parts.append(_emit_fold_stage(u, fs))
                 nb = (len(fs.src_rows) * (fs.replicas[0] if fs.replicas else 1) + 63) // 64
                 waves = (getattr(fs.traced.fold, "wave_fold", False) and _graph_fold_kinds(fs.traced.outputs, fs.out[2]) is not None)
                 nk = len(fs.src_rows) * (fs.replicas[0] if fs.replicas else 1) if waves else nb      # one wave per source, or one lane
@@ -1458,7 +1467,7 @@ def generate_source(tp, dtype: str, integrator: int, fast_math: bool = False, wi
             if i == last_seg:       # the link that records the tick into the history ring holds every column
                 used = set(range(len(tp.columns)))
             reads_accel = any(s_.reads_accel for s_ in pre)
-            parts.append(_emit_pipe_struct(f"PipeSeg{i}", tp, pipe_tp if six else None, pre, post, used, reads_accel, 0, body_dead))
+            parts.append(_emit_pipe_struct(u, f"PipeSeg{i}", tp, pipe_tp if six else None, pre, post, used, reads_accel, 0, body_dead))
             ig = integ if six else "kNone"
             tweak = "" if i == last_seg else " qs.hist_ring = 0; qs.hist_pos = qs.hist_vel = qs.hist_accel = qs.hist_force = nullptr;"          # only the last link records the tick
             tweak += "" if six else " qs.accel_in_check = 0;"
@@ -1469,7 +1478,7 @@ def generate_source(tp, dtype: str, integrator: int, fast_math: bool = False, wi
                   "        StepParams q = *p;\n        q.n_ticks = 1;\n        q.tick0 = p->tick0 + t;\n        q.hist_slot0 = p->hist_slot0 + t;\n"
                   "        if (t) q.accel_in_check = 0;\n"
                   + "\n".join(calls) + "\n    }\n")
-    tables = _emit_tables()
+    tables = _emit_tables(u)
     if any(f"m_{k}(" in structs for k in ("bxor", "bor", "band", "shl", "shr", "bits2f", "fbits", "bits2f32", "f32bits")):      # only programs that use them carry this text
         structs = _BITWISE + structs
     fast_erfinv = ""
@@ -1484,7 +1493,7 @@ def generate_source(tp, dtype: str, integrator: int, fast_math: bool = False, wi
     if relaxed:      # only relaxed programs carry (and are keyed on) this text
         structs = _RELAXED_PRELUDE + structs
     return f'''// generated by elodin_amd/codegen.py — do not edit.  Effectors: {names}
-{stage_comment}{fast}{"#define SIXDOF_TICK_OUT_OF_LINE" + chr(10) if _TICK_OUT_OF_LINE[0] else ""}#include "step_kernel.hpp"
+{stage_comment}{fast}{"#define SIXDOF_TICK_OUT_OF_LINE" + chr(10) if u.tick_out_of_line else ""}#include "step_kernel.hpp"
 
 namespace sixdof {{
 
@@ -1547,12 +1556,9 @@ def generate_pair_source(tf: "dsl.TracedFold", integrator: Optional[int] = None,
     if only_i not in (-1, 0, 1):
         raise ValueError(f"edge_fold effectors step under RK4 or the semi-implicit integrator, not integrator {integrator}")
     only_s = -1 if small is None else int(bool(small))
-    _GUARD_SELECTS[0], _FUSE_FMA[0], _RELAXED_EMIT[0] = False, False, False      # switches of generate_source: exact arithmetic here
-    _TABLES.clear()
-    _GATHERS.clear()
-    _LANE_TABLES.clear()
-    body = "\n".join(emit_block([(f"acc[{k}]", e) for k, e in enumerate(tf.outputs)], _PAIR_LEAVES))
-    tables = _emit_tables()
+    u = _Unit()      # every switch off: exact arithmetic in program order
+    body = "\n".join(emit_block(u, [(f"acc[{k}]", e) for k, e in enumerate(tf.outputs)], _PAIR_LEAVES))
+    tables = _emit_tables(u)
     additive = _fold_is_additive(tf)
     # an object built for ONE of the two launch shapes says so, and the library follows the object rather than re-deriving the choice
     # from the row count and the environment at step time (only specialised objects carry the export: other texts are unchanged)
@@ -1609,10 +1615,7 @@ def generate_graph_fold_source(tf: "dsl.TracedGraphFold") -> str:
     """A stand-alone GraphQuery.edge_fold over arbitrary components: one lane per source entity folds its out-edges
     (CSR by source, spawn order) into a scratch row; a second kernel moves the rows into the output component, so every
     fold sees the component values from before the system ran."""
-    _GUARD_SELECTS[0], _FUSE_FMA[0], _RELAXED_EMIT[0] = False, False, False      # switches of generate_source: exact arithmetic here
-    _TABLES.clear()
-    _GATHERS.clear()
-    _LANE_TABLES.clear()
+    u = _Unit()      # every switch off: exact arithmetic in program order
     f = tf.fold
     leaves = {f"acc_{k}": f"acc[{k}]" for k in range(tf.widths[f.out])}
     loads_a, loads_b = [], []
@@ -1625,7 +1628,7 @@ def generate_graph_fold_source(tf: "dsl.TracedGraphFold") -> str:
             leaves[f"b{i}_{k}"] = f"b{i}[{k}]"
         loads_b.append(f"        const double* b{i} = P.right[{i}] + (size_t)P.dst[e] * {tf.widths[n]};")
     w = tf.widths[f.out]
-    body = "\n".join(emit_block([(f"acc[{k}]", e) for k, e in enumerate(tf.outputs)], leaves, indent="        "))
+    body = "\n".join(emit_block(u, [(f"acc[{k}]", e) for k, e in enumerate(tf.outputs)], leaves, indent="        "))
     init = ", ".join(repr(v) for v in f.init)
     nl = "\n"
     return f'''// generated by elodin_amd/codegen.py — do not edit.  stand-alone edge_fold system: {f.__name__}
@@ -1636,7 +1639,7 @@ namespace sixdof {{
 __device__ __forceinline__ double fast_sqrt(double x) {{ return sqrt(x); }}
 __device__ __forceinline__ float fast_sqrt(float x) {{ return sqrtf(x); }}
 {_PRELUDE}
-{_emit_tables()}
+{_emit_tables(u)}
 struct GraphFoldParams {{
     const double* left[8];
     const double* right[8];
@@ -1696,9 +1699,6 @@ def _headers_digest() -> str:
     return h.hexdigest()
 
 
-_ONLY_POLICY: List[Optional[int]] = [None]      # build(policy=...): the one cache policy the object is generated for (None: all three)
-
-
 def policy_for(n_rows: int, row_elems: int, elem_bytes: int) -> Optional[int]:
     """The cache policy csrc/sixdof_capi.cpp fill_step_params picks for an executor of this size (plain loads + nt stores up to
     768 MiB of state, nt both ways beyond), or None when an environment override may pick another at run time (A/B tooling)."""
@@ -1710,16 +1710,9 @@ def policy_for(n_rows: int, row_elems: int, elem_bytes: int) -> Optional[int]:
 def build(tp: dsl.TracedPipe, dtype: str = "float64", integrator: int = 0, fast_math: bool = False, window_soa: bool = False,
           column_soa: bool = False, guard_selects: Optional[bool] = None, policy: Optional[int] = None) -> Path:
     """Generate + compile (cached by content hash).  Returns the .so path.  A program that no flag set builds without VGPR
-    spills is generated again with its columns memory-resident (_MEMORY_COLUMNS) before giving up.
+    spills is generated again with its columns memory-resident (the "memory" variant) before giving up.
     policy: instantiate the step kernel for this cache policy only (policy_for); None = all three, selectable at launch."""
-    _ONLY_POLICY[0] = policy if policy in (0, 1, 9) else None
-    try:
-        return _build(tp, dtype, integrator, fast_math, window_soa, column_soa, guard_selects)
-    finally:
-        _ONLY_POLICY[0] = None
-
-
-def _build(tp, dtype, integrator, fast_math, window_soa, column_soa, guard_selects) -> Path:
+    policy = policy if policy in (0, 1, 9) else None
     if getattr(tp, "prebuilt_so", None) is not None:        # dsl.FrozenProgram(prebuilt_so=...): the object exists (stablehlo CLI)
         if not Path(tp.prebuilt_so).exists():
             raise FileNotFoundError(tp.prebuilt_so)
@@ -1736,12 +1729,9 @@ def _build(tp, dtype, integrator, fast_math, window_soa, column_soa, guard_selec
         # a tick that keeps more values live than a wave has registers (a whole-world module: every stage vector of its RK4 waits
         # for the final sum) would fail the first variants one hipcc run after another: estimate each emission order's peak of live
         # values from the DAG and, only when creation order is over budget, try the orders from the leanest up
-        _ESTIMATE[0] = {}
-        try:
-            first_src = generate_variant(tp, variants[0], dtype, integrator, fast_math, window_soa, column_soa, guard_selects)
-            est = dict(_ESTIMATE[0])
-        finally:
-            _ESTIMATE[0] = None
+        u = _unit(tp, variants[0], fast_math, window_soa, column_soa, guard_selects, policy, estimate=True)
+        first_src = _source(tp, dtype, integrator, fast_math, u)
+        est = u.estimate
         regs_per_value = 2 if dtype == "float64" else 1
         held = sum(int(w_) for _, w_ in tp.columns)
         if est and (est.get("program", 0) + held) * regs_per_value > PRESSURE_BUDGET_REGS:
@@ -1752,12 +1742,9 @@ def _build(tp, dtype, integrator, fast_math, window_soa, column_soa, guard_selec
         last_estimate.update(est)
     for k, variant in enumerate(variants):
         try:
-            src_k = first_src if (k == 0 and first_src is not None) else generate_variant(tp, variant, dtype, integrator, fast_math, window_soa, column_soa, guard_selects)
-            _EXPECT_SCRATCH[0] = variant == "memory"
-            try:
-                so = _compile(src_k, "pipe")
-            finally:
-                _EXPECT_SCRATCH[0] = False
+            src_k = first_src if (k == 0 and first_src is not None) else \
+                generate_variant(tp, variant, dtype, integrator, fast_math, window_soa, column_soa, guard_selects, policy)
+            so = _compile(src_k, "pipe", expect_scratch=variant == "memory")
             last_variant[0] = variant
             return so
         except SpillError:
@@ -1767,7 +1754,7 @@ def _build(tp, dtype, integrator, fast_math, window_soa, column_soa, guard_selec
 
 # What build() tries, in order, until a build has no VGPR spills: the tick body emitted in the user's program order; in demand
 # order (each value right before its first use); in register-pressure order (_pressure_order: the node that ends the most live
-# ranges next); with the columns in a memory image instead of registers (_MEMORY_COLUMNS);
+# ranges next); with the columns in a memory image instead of registers (_Unit.memory_columns);
 # with the tick body out of line (SIXDOF_TICK_OUT_OF_LINE).
 VARIANTS = ("program", "demand", "pressure", "memory", "out_of_line")
 PRESSURE_BUDGET_REGS = 440       # (estimated live values + column values) x registers per value above which build() reorders its variants
@@ -1776,16 +1763,10 @@ last_variant = ["program"]      # the variant the last build() settled on (fixtu
 
 
 def generate_variant(tp, variant: str, dtype: str = "float64", integrator: int = 0, fast_math: bool = False, window_soa: bool = False,
-                     column_soa: bool = False, guard_selects: Optional[bool] = None) -> str:
+                     column_soa: bool = False, guard_selects: Optional[bool] = None, policy: Optional[int] = None) -> str:
     if variant not in VARIANTS:
         raise ValueError(f"variant must be one of {VARIANTS}")
-    _EMIT_ORDER[0] = variant if variant in ("demand", "pressure") else "program"
-    _MEMORY_COLUMNS[0] = variant == "memory"
-    _TICK_OUT_OF_LINE[0] = variant == "out_of_line"
-    try:
-        return generate_source(tp, dtype, integrator, fast_math, window_soa, column_soa, guard_selects)
-    finally:
-        _EMIT_ORDER[0], _MEMORY_COLUMNS[0], _TICK_OUT_OF_LINE[0] = "program", False, False
+    return _source(tp, dtype, integrator, fast_math, _unit(tp, variant, fast_math, window_soa, column_soa, guard_selects, policy))
 
 
 # Generated programs are one long straight-line tick body inside the kernel's tick loop.  Left alone, LLVM's MachineLICM
@@ -2097,7 +2078,8 @@ def _spill_message(name: str, used: Dict[str, int]) -> str:
             "split it or narrow its columns")
 
 
-def _compile(src: str, stem: str) -> Path:
+def _compile(src: str, stem: str, expect_scratch: bool = False) -> Path:
+    """expect_scratch: the source keeps state in private memory by design (the "memory" variant)."""
     import json
     import tempfile
     import warnings
@@ -2194,7 +2176,7 @@ def _compile(src: str, stem: str) -> Path:
                 # fewest VGPR spills first, then least scratch: a build without VGPR spills may still keep something in scratch
                 # memory (SGPR spill carriers), and a later flag set that needs none is the better object
                 # (the memory-image variant keeps its columns in scratch on purpose: there only the spill count decides)
-                by_design = _EXPECT_SCRATCH[0] or "        volatile T c" in src          # (a frozen text of that variant says so itself)
+                by_design = expect_scratch or "        volatile T c" in src          # (a frozen text of that variant says so itself)
                 # ... compared between attempts at the SAME optimisation level only: legitimate scratch (a program's private arrays)
                 # must not let the -O1 object — a slower kernel — displace a spill-free -O3 one
                 level = lambda u: 1 if u["flags"].startswith("-O1") else 0

@@ -2320,7 +2320,7 @@ def system(text: str, inputs: Sequence[str], outputs: Sequence[str], name: str =
     import inspect
     fn.__signature__ = inspect.Signature([inspect.Parameter(p, inspect.Parameter.KEYWORD_ONLY) for p in params])
     out = _dsl.system(fn, every=every, **widths)
-    out.float32_refused = float32_hazards(funcs)      # a float32 build of a program holding this system is refused (codegen._build)
+    out.float32_refused = float32_hazards(funcs)      # a float32 build of a program holding this system is refused (codegen.build)
     return out
 
 

@@ -595,8 +595,8 @@ def test_polars_subset_over_pandas_builds_the_rocket_examples_grid():
 
 
 def test_fast_math_builds_fold_single_use_products_into_their_sums():
-    """codegen._FUSE_FMA: in a fast-math program `a * b + c`, `a * b - c` and `c - a * b` become one m_fma each when the product
-    has no other use; a product used twice, a block output and every exact build stay apart."""
+    """codegen's FMA fusion (_Unit.fuse_fma): in a fast-math program `a * b + c`, `a * b - c` and `c - a * b` become one m_fma
+    each when the product has no other use; a product used twice, a block output and every exact build stay apart."""
     import re
 
     @dsl.system(x=3, y=5)

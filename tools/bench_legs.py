@@ -408,12 +408,8 @@ def build_times_leg(device):
             w, sys_ = (mod.world(), mod.system()) if mod_name == "ball" else mod.world_and_system()
             def build():
                 dsl.Expr.fresh()
-                codegen._ONLY_POLICY[0] = 1          # as exec.HipExec builds it: the one cache policy its row count selects
-                try:
-                    srcs = w.generated_sources(sys_, simulation_rate=120.0)
-                    return [codegen._compile(src, kind) for kind, src in srcs.items()]
-                finally:
-                    codegen._ONLY_POLICY[0] = None
+                srcs = w.generated_sources(sys_, simulation_rate=120.0, policy=1)      # as exec.HipExec builds it: the one cache policy its row count selects
+                return [codegen._compile(src, kind) for kind, src in srcs.items()]
             return build
         return make
     timed("three_body_fold", example("three_body"))
