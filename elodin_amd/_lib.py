@@ -86,6 +86,7 @@ SYMBOLS = {
                                        C.POINTER(C.c_size_t)]),
     "sixdof_upload": (C.c_int, [_H]),
     "sixdof_prepare_step": (C.c_int, [_H, C.c_uint64]),
+    "sixdof_step_path": (C.c_char_p, [_H]),
     "sixdof_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "sixdof_comm_init": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int]),
     "sixdof_comm_destroy": (None, [C.c_void_p]),

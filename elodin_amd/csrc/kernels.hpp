@@ -60,8 +60,18 @@ struct StepParams {
 
 enum : int { kRk4 = 0, kSemiImplicit = 1, kNone = 2 };   // kNone: a pipe of systems without six_dof (generated programs only)
 
+// One launch of the built-in step kernel: the instantiation's host stub (null: nothing to launch) and its grid of
+// kWave-thread workgroups.
+struct StepKernel {
+    const void* fn = nullptr;
+    dim3 grid;
+};
+
+// The instantiation launch_step runs for `p` (built-in pipes only).
+StepKernel select_step(const StepParams& p, int integrator, int dtype);
+
 // Fused clear_forces | effectors | calc_accel | integrator over n entities, n_ticks ticks.
-// dtype: 0 = f64, 1 = f32.  Returns hipGetLastError() of the launch.
+// dtype: 0 = f64, 1 = f32.  Returns the launch's error.
 hipError_t launch_step(const StepParams& p, int integrator, int dtype, hipStream_t stream);
 
 // Entry points of a run-time generated effector pipe (elodin_amd/codegen.py), resolved with dlsym.

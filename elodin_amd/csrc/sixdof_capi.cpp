@@ -28,6 +28,7 @@
 #include "../../include/sixdof_apollo.h"
 #include "kernels.hpp"
 #include "abi_guard.hpp"
+#include "aql_chain.hpp"
 
 using namespace sixdof;
 
@@ -62,6 +63,8 @@ double now_ms() {
 }
 
 uint64_t cid(const char* s) { return sixdof_component_id(s); }
+
+constexpr uint32_t kAqlSlots = 8;   // argument blocks of AQL chains per handle (sixdof_handle::aql_args)
 
 }  // namespace
 
@@ -128,6 +131,17 @@ struct sixdof_handle {
     std::map<uint32_t, hipGraphExec_t> graphs;   // replay graphs by chain length (launches per replay), one StepParams signature
     uint32_t graph_k = 0;
     uint64_t graph_sig = 0;
+    // AQL chains (aql_chain.hpp): graph-eligible batches of a built-in pipe as pre-built dispatch packets
+    bool aql_off = false;                   // SIXDOF_AQL=0 when the handle was created: keep the hipGraph path
+    aql::Device* aql_dev = nullptr;
+    std::string aql_why;                    // why AQL setup failed (the hipGraph path then stays); not retried
+    std::string aql_fault;                  // a chain failed on the queue: every later step fails with this
+    void* aql_args = nullptr;               // device arena of argument blocks (kAqlSlots)
+    std::map<uint64_t, aql::Run> aql_runs;  // by (accel_in_check, n_ticks): kernel, argument block, grid; of aql_params
+    uint64_t aql_slot_key[kAqlSlots] = {};  // the key whose block each spare slot (2 ..) holds, ~0: none
+    uint32_t aql_next_spare = 2;            // the spare slot the next new key takes
+    StepParams aql_params{};                // the batch parameters the argument blocks were built from (tick0 = 0)
+    std::string path;                       // sixdof_step_path's answer
     mutable std::string err;
 
     uint64_t id_pos, id_vel, id_accel, id_force, id_inertia, id_tick, id_dt;
@@ -260,6 +274,8 @@ int sixdof_create(const sixdof_desc* d, sixdof_handle** out) try {
     auto* h = new sixdof_handle();
     h->desc = *d;
     if (h->desc.ticks_per_launch == 0) h->desc.ticks_per_launch = 1;
+    const char* aql_env = std::getenv("SIXDOF_AQL");   // "0": hipGraph replay instead of AQL chains (A/B runs)
+    h->aql_off = aql_env && aql_env[0] == '0';
     h->device = d->device_ordinal;
     h->id_pos = cid("world_pos");
     h->id_vel = cid("world_vel");
@@ -306,6 +322,8 @@ void sixdof_destroy(sixdof_handle* h) try {
     if (h->custom_dl) dlclose(h->custom_dl);
     if (h->pair_dl) dlclose(h->pair_dl);
     for (hipEvent_t e : h->launch_events) hipEventDestroy(e);
+    if (h->aql_args && h->aql_fault.empty()) hipFree(h->aql_args);   // after a failed chain a dispatch may still read it
+    aql::release(h->aql_dev);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->evp0) hipEventDestroy(h->evp0);
@@ -1356,11 +1374,142 @@ static int ensure_plan_graphs(sixdof_handle* h, const StepParams& P, uint32_t K,
     return rc;
 }
 
+// ---- AQL chains ------------------------------------------------------------------------------------------------
+// A graph-eligible batch of a built-in pipe is written into the process's own HSA queue as dispatch packets of the same
+// kernel objects HIP launches (select_step), with argument blocks built ahead of the batch.  plan_chains stays the
+// accounting: what it would replay counts as graph_launches, the launches it leaves (and the accel-check launch) as eager.
+
+constexpr size_t kAqlSlotBytes = (sizeof(StepParams) + 255) / 256 * 256;
+constexpr double kAqlStallS = 60.0;     // no packet of a chain started or finished for this long: the queue is stuck
+constexpr int kAqlFallback = 1;         // step_aql: nothing submitted, take the hipGraph path
+
+// Why a batch of this handle cannot take the AQL path, or null.
+static const char* aql_ineligible(const sixdof_handle* h) {
+    if (h->aql_off) return "SIXDOF_AQL=0";
+    if (!graph_eligible(h)) return "not graph-eligible";
+    if (h->custom_launch) return "generated pipe";
+    if (h->desc.flags & SIXDOF_FLAG_ASYNC_STEP) return "ASYNC_STEP";
+    if (h->desc.n_entities == 0) return "no rows";
+    return nullptr;
+}
+
+// The packet run of one launch of `P` with `check` / `ticks` (its kernel and argument block, count 0), built on first use.
+// The argument blocks of the K-tick launches keep slots 0 (plain) and 1 (accel check) for as long as the parameters hold.
+// Any other block (a remainder, or a batch shorter than K) takes the next spare slot, evicting whichever block was there:
+// a batch holds at most one such block (aql_batch), so no block a batch is about to run can be overwritten by its own
+// later lookups, and nothing is in flight between two batches.
+static bool aql_run(sixdof_handle* h, const StepParams& P, uint32_t check, uint32_t ticks, aql::Run* out) {
+    const uint64_t key = uint64_t(check) << 32 | ticks;
+    if (auto it = h->aql_runs.find(key); it != h->aql_runs.end()) return *out = it->second, true;
+    uint32_t slot_index = check;
+    if (ticks != h->desc.ticks_per_launch) {
+        slot_index = h->aql_next_spare;
+        h->aql_next_spare = slot_index + 1 == kAqlSlots ? 2 : slot_index + 1;
+        h->aql_runs.erase(h->aql_slot_key[slot_index]);
+        h->aql_slot_key[slot_index] = ~0ull;
+    }
+    StepParams Q = P;
+    Q.accel_in_check = check;
+    Q.n_ticks = ticks;
+    Q.tick0 = Q.hist_slot0 = 0;   // read only by generated and history-ring pipes, which never take this path
+    const StepKernel k = select_step(Q, h->desc.integrator, h->desc.dtype);
+    if (!k.fn) return h->aql_why = "no built-in kernel for this launch", false;
+    aql::Run r;
+    if (!aql::kernel_code(h->aql_dev, k.fn, sizeof(StepParams), &r.code, &h->aql_why)) return false;
+    if (r.code.kernarg_align > 256) return h->aql_why = "kernarg alignment above 256 bytes", false;
+    char* slot = static_cast<char*>(h->aql_args) + slot_index * kAqlSlotBytes;
+    hipError_t e = hipMemcpy(slot, &Q, sizeof(Q), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return h->aql_why = std::string("hipMemcpy (argument block): ") + hipGetErrorString(e), false;
+    r.kernarg = slot;
+    r.blocks = k.grid.x;
+    h->aql_runs[key] = r;
+    if (slot_index >= 2) h->aql_slot_key[slot_index] = key;
+    return *out = r, true;
+}
+
+// Whether the next batch takes the AQL path; sets the queue and the batch's argument blocks up on first use.  `P`: the
+// batch's parameters (K ticks per launch).  A faulted handle answers yes: step_aql then reports the fault.
+static bool aql_ready(sixdof_handle* h, StepParams* P) {
+    if (aql_ineligible(h) || !h->aql_why.empty()) return false;
+    if (!h->aql_fault.empty()) return true;
+    if (fill_step_params(h, P) != SIXDOF_OK) return false;
+    const uint32_t K = h->desc.ticks_per_launch;
+    P->n_ticks = K;
+    if (!h->aql_dev) {
+        if (!(h->aql_dev = aql::acquire(h->device, &h->aql_why))) return false;
+        hipError_t e = hipMalloc(&h->aql_args, kAqlSlots * kAqlSlotBytes);
+        if (e != hipSuccess) return h->aql_args = nullptr, h->aql_why = std::string("hipMalloc: ") + hipGetErrorString(e), false;
+    }
+    // what step_signature hashes for the graph cache, compared whole (integrator and dtype are fixed per handle)
+    StepParams key = *P;
+    key.tick0 = key.hist_slot0 = 0;
+    if (std::memcmp(&key, &h->aql_params, sizeof(key)) != 0) {
+        h->aql_runs.clear();
+        std::fill(std::begin(h->aql_slot_key), std::end(h->aql_slot_key), ~0ull);
+        h->aql_next_spare = 2;
+        h->aql_params = key;
+    }
+    aql::Run r;
+    if (!aql_run(h, *P, 0, K, &r)) return false;
+    // the first RK4 batch after an upload opens with the accel-check launch (step_rigid)
+    if (h->accel_is_host_data && h->desc.integrator == SIXDOF_INTEGRATOR_RK4 && !aql_run(h, *P, 1, K, &r)) return false;
+    return true;
+}
+
+// The launches of a batch of `n_ticks`, as step_rigid makes them: the accel-check launch when `check`, the K-tick launches
+// (what plan_chains replays and the eager ones it leaves are the same packets: one run), the remainder.  *full: the K-tick
+// launches.  Apart from the two K-tick blocks, the runs hold at most one block: a remainder needs n_ticks >= K, and then the
+// check launch runs K ticks.
+static bool aql_batch(sixdof_handle* h, const StepParams& P, uint64_t n_ticks, bool check, aql::Run runs[3], uint64_t* full) {
+    const uint32_t K = h->desc.ticks_per_launch;
+    *full = n_ticks / K;
+    uint32_t rem = static_cast<uint32_t>(n_ticks % K);
+    const uint32_t check_ticks = static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks));
+    if (check) {
+        if (n_ticks >= K) *full -= 1;
+        else rem = 0;
+    }
+    if ((check && !aql_run(h, P, 1, check_ticks, &runs[0])) || (*full && !aql_run(h, P, 0, K, &runs[1])) ||
+        (rem && !aql_run(h, P, 0, rem, &runs[2])))
+        return false;
+    runs[0].count = check ? 1 : 0;
+    runs[1].count = *full;
+    runs[2].count = rem ? 1 : 0;
+    return true;
+}
+
+static bool aql_check_launch(const sixdof_handle* h, uint64_t n_ticks) {
+    return h->accel_is_host_data && n_ticks > 0 && h->desc.integrator == SIXDOF_INTEGRATOR_RK4;
+}
+
+// step_rigid as one AQL chain: the same launches, counted the same way, then a spin on the last packet.
+static int step_aql(sixdof_handle* h, const StepParams& P, uint64_t n_ticks, uint64_t* launches) {
+    if (!h->aql_fault.empty()) return h->fail(SIXDOF_ERR_BACKEND, h->aql_fault);
+    aql::Run runs[3];
+    uint64_t full = 0;
+    if (!aql_batch(h, P, n_ticks, aql_check_launch(h, n_ticks), runs, &full)) return kAqlFallback;
+    // the chain bypasses the HIP stream: let what was enqueued there (and on the null stream it waits for) finish first
+    for (hipStream_t s : {h->stream, static_cast<hipStream_t>(nullptr)}) {
+        const hipError_t q = hipStreamQuery(s);
+        if (q == hipErrorNotReady) HIP_TRY(h, hipStreamSynchronize(s));
+        else if (q != hipSuccess) return h->hip_fail(q, "hipStreamQuery");
+    }
+    double device_ms = 0.0;
+    if (!aql::run_chain(h->aql_dev, runs, 3, kAqlStallS, &device_ms, &h->aql_fault))
+        return h->fail(SIXDOF_ERR_BACKEND, h->aql_fault);
+    if (n_ticks > 0) h->accel_is_host_data = false;
+    *launches = runs[0].count + runs[1].count + runs[2].count;
+    h->last.graph_launches = plan_chains(full).launches();
+    h->last.kernel_device_ms = device_ms;
+    return SIXDOF_OK;
+}
+
 // Build the replay graph ahead of the first long batch (called when the columns become resident and when the batch
 // shape changes), so that no step call pays for capture + instantiation.
 int prepare_graph(sixdof_handle* h) {
     if (!h->bound || !graph_eligible(h)) return SIXDOF_OK;
     StepParams P;
+    if (aql_ready(h, &P)) return SIXDOF_OK;
     int rc = fill_step_params(h, &P);
     if (rc != SIXDOF_OK) return SIXDOF_OK;     // not steppable yet (columns missing): the step call will report it
     P.n_ticks = h->desc.ticks_per_launch;
@@ -1376,6 +1525,15 @@ int sixdof_prepare_step(sixdof_handle* h, uint64_t n_ticks) try {
     if (!graph_eligible(h)) return SIXDOF_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     StepParams P;
+    if (aql_ready(h, &P)) {
+        // nothing to capture: build the argument blocks the batch needs, with and without the accel-check launch (whether
+        // a warm-up batch takes it first the library cannot know)
+        aql::Run runs[3];
+        uint64_t full = 0;
+        for (bool check : {false, aql_check_launch(h, n_ticks)})
+            if (!aql_batch(h, P, n_ticks, check, runs, &full)) break;   // the step falls back and reports why
+        return SIXDOF_OK;
+    }
     int rc = fill_step_params(h, &P);
     if (rc != SIXDOF_OK) return rc;
     const uint32_t K = h->desc.ticks_per_launch;
@@ -1392,6 +1550,22 @@ int sixdof_prepare_step(sixdof_handle* h, uint64_t n_ticks) try {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
+
+const char* sixdof_step_path(sixdof_handle* h) try {
+    if (!h) return "invalid handle";
+    (void)hipSetDevice(h->device);
+    StepParams P;
+    if (h->model == 1) h->path = "apollo";
+    else if (h->has_pair_op()) h->path = "pair";
+    else if (!h->aql_fault.empty()) h->path = "aql (failed: " + h->aql_fault + ")";
+    else if (h->bound && h->resident && aql_ready(h, &P)) h->path = "aql";
+    else {
+        const char* why = aql_ineligible(h);
+        h->path = std::string(graph_eligible(h) ? "hipgraph: " : "eager: ") +
+                  (why ? why : !h->aql_why.empty() ? h->aql_why.c_str() : "columns not uploaded yet");
+    }
+    return h->path.c_str();
+} SIXDOF_ABI_CATCH_VALUE(err_of(h), nullptr)
 
 // Pair effectors: one launch call per K ticks.  The multi-kernel path's batch is ONE pack launch, then fold + integrate
 // per tick (the integrate kernel writes the next tick's pack rows); with a telemetry ring the batch is cut at every tick
@@ -1528,16 +1702,22 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
         const bool overlap = n_ticks + in_flight > ring || gap_ab < std::min<uint64_t>(n_ticks, ring) || gap_ba < in_flight;
         if (overlap) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied, 0));
     }
-    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     if (h->desc.integrator == SIXDOF_INTEGRATOR_NONE && (!h->custom_launch || h->model != 0 || h->has_pair_op()))
         return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: SIXDOF_INTEGRATOR_NONE runs generated system programs only (sixdof_set_custom_pipe)");
     uint64_t launches = 0;
-    const int rc = h->model == 1 ? step_apollo(h, n_ticks, &launches)
-                   : h->has_pair_op() ? step_pair(h, n_ticks, &launches)
-                                      : step_rigid(h, n_ticks, &launches);
+    StepParams P;
+    // an AQL chain waits for itself and times itself from its packets: no event pair on the HIP stream
+    int rc = h->model == 0 && !h->has_pair_op() && aql_ready(h, &P) ? step_aql(h, P, n_ticks, &launches) : kAqlFallback;
+    const bool aql = rc != kAqlFallback;
+    if (!aql) {
+        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        rc = h->model == 1 ? step_apollo(h, n_ticks, &launches)
+             : h->has_pair_op() ? step_pair(h, n_ticks, &launches)
+                                : step_rigid(h, n_ticks, &launches);
+    }
     if (rc != SIXDOF_OK) return rc;
-    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-    if (!async_step) {
+    if (!aql) HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    if (!async_step && !aql) {
         // short batches finish in tens of microseconds: poll for that long before paying a blocking wait's wake-up
         const double spin_until = now_ms() + 0.25;
         hipError_t q = hipEventQuery(h->ev1);
@@ -1549,7 +1729,7 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
     }
     h->tick += n_ticks;  // increment_sim_tick (globals.rs:42-44), once per tick
     h->step_pending = async_step;
-    if (!async_step) {
+    if (!async_step && !aql) {
         float ms0 = 0.f;
         hipEventElapsedTime(&ms0, h->ev0, h->ev1);
         h->last.kernel_device_ms = ms0;

@@ -471,65 +471,66 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
     flush6(l_force, g_force, kLive);
 }
 
-// ---- launch helpers (shared with generated translation units) ----------------------------------------------
+// ---- kernel selection ----------------------------------------------------------------------------------------
 
+// Which instantiation of the step kernel a launch of `p` runs.  launch_step launches it; the AQL chain (aql_chain.hpp)
+// looks the same host stub up in the library's own code object, so the two paths cannot pick different code.
 template <class T, class PIPE, int POL>
-inline void launch_i(const StepParams& p, int integrator, dim3 grid, hipStream_t s) {
+inline StepKernel select_i(const StepParams& p, int integrator, dim3 grid) {
 #ifdef SIXDOF_AB_BUILD
     if constexpr (!PIPE::kHasModel) {
-        if ((p.streaming & 512u) && integrator == kRk4 && !p.accel_in_check) {      // A/B: half-filled waves (ROWS = 32)
-            hipLaunchKernelGGL((sixdof_step_kernel<T, kRk4, PIPE, POL, false, 32>), dim3((p.n + 31) / 32), dim3(kWave), 0, s, p);
-            return;
-        }
+        if ((p.streaming & 512u) && integrator == kRk4 && !p.accel_in_check)      // A/B: half-filled waves (ROWS = 32)
+            return {reinterpret_cast<const void*>(&sixdof_step_kernel<T, kRk4, PIPE, POL, false, 32>), dim3((p.n + 31) / 32)};
     }
 #endif
     if (integrator == kRk4) {
         if constexpr (!PIPE::kHasModel) {
-            if (p.accel_in_check) {   // one launch per upload: a single cache policy is plenty
-                hipLaunchKernelGGL((sixdof_step_kernel<T, kRk4, PIPE, kPolPlain, true>), grid, dim3(kWave), 0, s, p);
-                return;
-            }
+            if (p.accel_in_check)   // one launch per upload: a single cache policy is plenty
+                return {reinterpret_cast<const void*>(&sixdof_step_kernel<T, kRk4, PIPE, kPolPlain, true>), grid};
         }
-        hipLaunchKernelGGL((sixdof_step_kernel<T, kRk4, PIPE, POL>), grid, dim3(kWave), 0, s, p);
-    } else if (integrator == kNone) {
-        if constexpr (PIPE::kHasModel) hipLaunchKernelGGL((sixdof_step_kernel<T, kNone, PIPE, POL>), grid, dim3(kWave), 0, s, p);
-    } else hipLaunchKernelGGL((sixdof_step_kernel<T, kSemiImplicit, PIPE, POL>), grid, dim3(kWave), 0, s, p);
+        return {reinterpret_cast<const void*>(&sixdof_step_kernel<T, kRk4, PIPE, POL>), grid};
+    }
+    if (integrator == kNone) {
+        if constexpr (PIPE::kHasModel) return {reinterpret_cast<const void*>(&sixdof_step_kernel<T, kNone, PIPE, POL>), grid};
+        return {};
+    }
+    return {reinterpret_cast<const void*>(&sixdof_step_kernel<T, kSemiImplicit, PIPE, POL>), grid};
 }
 
 // StepParams::streaming is the cache-policy code (load * 8 + store).  Every pipe has the three shipped policies
 // (plain, nt stores, nt both ways) and the product library has nothing else; an A/B build (-DSIXDOF_AB_BUILD) adds the
 // rest of the matrix (SWEEP, tools/step_ab.py) on the pipes that ask for it.
 template <class T, class PIPE, bool SWEEP>
-inline void launch_t(const StepParams& p, int integrator, dim3 grid, hipStream_t s) {
+inline StepKernel select_t(const StepParams& p, int integrator, dim3 grid) {
     const uint32_t pol = p.streaming & 255u;   // bit 8 = late flush (A/B knob), see the kernel
     switch (pol) {
-    case kPolNt: return launch_i<T, PIPE, kPolNt>(p, integrator, grid, s);
-    case kPolNtStores: return launch_i<T, PIPE, kPolNtStores>(p, integrator, grid, s);
+    case kPolNt: return select_i<T, PIPE, kPolNt>(p, integrator, grid);
+    case kPolNtStores: return select_i<T, PIPE, kPolNtStores>(p, integrator, grid);
     default: break;
     }
 #ifdef SIXDOF_AB_BUILD
     // A/B library only (make ab -> libsixdof_hip_ab.so, never shipped).  kPolSc1Stores is UNSAFE across launches
     // (the next launch reads stale rows, profiles/r02_sc1_store_policy_is_unsafe.txt): it exists to demonstrate that.
-    if (pol == kPolSc1Stores) return launch_i<T, PIPE, kPolSc1Stores>(p, integrator, grid, s);
+    if (pol == kPolSc1Stores) return select_i<T, PIPE, kPolSc1Stores>(p, integrator, grid);
     if constexpr (SWEEP) {
         switch (pol) {
-        case 3: return launch_i<T, PIPE, 3>(p, integrator, grid, s);
-        case 4: return launch_i<T, PIPE, 4>(p, integrator, grid, s);
-        case 8: return launch_i<T, PIPE, 8>(p, integrator, grid, s);
-        case 10: return launch_i<T, PIPE, 10>(p, integrator, grid, s);
-        case 11: return launch_i<T, PIPE, 11>(p, integrator, grid, s);
-        case 12: return launch_i<T, PIPE, 12>(p, integrator, grid, s);
+        case 3: return select_i<T, PIPE, 3>(p, integrator, grid);
+        case 4: return select_i<T, PIPE, 4>(p, integrator, grid);
+        case 8: return select_i<T, PIPE, 8>(p, integrator, grid);
+        case 10: return select_i<T, PIPE, 10>(p, integrator, grid);
+        case 11: return select_i<T, PIPE, 11>(p, integrator, grid);
+        case 12: return select_i<T, PIPE, 12>(p, integrator, grid);
         default: break;
         }
     }
 #endif
-    launch_i<T, PIPE, kPolPlain>(p, integrator, grid, s);
+    return select_i<T, PIPE, kPolPlain>(p, integrator, grid);
 }
 
 template <class PIPE, bool SWEEP = false>
-inline void launch_p(const StepParams& p, int integrator, int dtype, dim3 grid, hipStream_t s) {
-    if (dtype == SIXDOF_F64) launch_t<double, PIPE, SWEEP>(p, integrator, grid, s);
-    else launch_t<float, PIPE, false>(p, integrator, grid, s);
+inline StepKernel select_p(const StepParams& p, int integrator, int dtype, dim3 grid) {
+    if (dtype == SIXDOF_F64) return select_t<double, PIPE, SWEEP>(p, integrator, grid);
+    return select_t<float, PIPE, false>(p, integrator, grid);
 }
 
 }  // namespace sixdof

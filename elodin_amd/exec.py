@@ -311,6 +311,11 @@ class HipExec:
         if rc != L.OK:
             _raise(self._h, rc, "sixdof_prepare_step")
 
+    @property
+    def step_path(self) -> str:
+        """Which path the next invoke_batch takes: "aql", "hipgraph: <why not aql>", "eager: <why>", ... (sixdof_step_path)."""
+        return self._lib.sixdof_step_path(self._h).decode()
+
     def download(self, mask: int = L.COL_ALL):
         rc = self._lib.sixdof_download(self._h, mask)
         if rc != L.OK:

@@ -150,8 +150,10 @@ typedef struct sixdof_desc {
     uint32_t reserved;
 } sixdof_desc;
 
-#define SIXDOF_FLAG_USE_GRAPH 1u /* replay sixdof_step batches of >= 4 launches from captured hipGraphs (chains of 32 + one
-                                    chain of the remainder, cached per length) */
+#define SIXDOF_FLAG_USE_GRAPH 1u /* run sixdof_step batches of >= 4 launches as a pre-built chain: for a built-in pipe,
+                                    dispatch packets written into the library's own HSA queue (SIXDOF_AQL=0 at creation:
+                                    off; sixdof_step_path tells); otherwise captured hipGraphs (chains of 32 + one chain of
+                                    the remainder, cached per length) */
 #define SIXDOF_FLAG_TIME_EACH_LAUNCH 2u /* profiling: bracket every launch of sixdof_step with its own HIP
                                            event pair (<= 4096 launches per call; disables graph replay) */
 #define SIXDOF_FLAG_ASYNC_STEP 4u /* sixdof_step only enqueues and returns (no stream sync): pair it with
@@ -174,11 +176,14 @@ typedef struct sixdof_timings {
     double h2d_upload_ms;
     double kernel_invoke_ms;   /* host wall time of the step call incl. stream sync */
     double d2h_download_ms;
-    double kernel_device_ms;   /* HIP-event time of the launches of the last step, on the handle's stream */
+    double kernel_device_ms;   /* device time of the launches of the last step: HIP events on the handle's stream, or for
+                                  an AQL chain the first dispatch's start to the last one's end (starts later than the
+                                  event, which also holds the wait in front of the first launch) */
     uint64_t launches;         /* kernel launches issued by the last step */
     uint64_t ticks;
     double kernel_sum_ms;      /* SIXDOF_FLAG_TIME_EACH_LAUNCH: sum of the per-launch event times (no gaps) */
-    uint64_t graph_launches;   /* how many of `launches` were replayed from a captured hipGraph (SIXDOF_FLAG_USE_GRAPH) */
+    uint64_t graph_launches;   /* how many of `launches` ran from a pre-built chain (SIXDOF_FLAG_USE_GRAPH): an AQL chain
+                                  or a captured hipGraph */
 } sixdof_timings;
 
 typedef struct sixdof_slot {
@@ -223,6 +228,9 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* timings /* m
 /* SIXDOF_FLAG_USE_GRAPH: capture (and cache) the launch chains a later sixdof_step(h, n_ticks) replays, without stepping —
  * the one-off cost CraneliftExec::new pays at build time (cranelift_exec.rs:54-127), kept out of the first timed batch. */
 int sixdof_prepare_step(sixdof_handle* h, uint64_t n_ticks);
+/* Which path the next sixdof_step batch takes, and why not the AQL chain when it does not: "aql", "hipgraph: <why>",
+ * "eager: <why>", "pair" or "apollo".  Sets the AQL chain up when the columns are resident.  Valid until the next call. */
+const char* sixdof_step_path(sixdof_handle* h);
 int sixdof_download(sixdof_handle* h, uint32_t column_mask);
 /* Telemetry commit without the per-batch stall (the step either side of the path: commit_world_head after
  * every batch, impeller2_server.rs:390-438; JaxExec blocks on copy_to_host there, jax_exec.rs:150-178).
