@@ -1,6 +1,6 @@
 // aql_chain.hpp — a batch of step-kernel launches written straight into an HSA queue the library owns.
 //
-// Every launch of a replayed chain has the same kernel object, grid and argument block (sixdof_capi.cpp step_signature),
+// Every launch of a replayed chain has the same kernel object, grid and argument block (sixdof_capi.cpp Replay::key),
 // so a batch needs none of the graph-replay machinery: its launches are written as kernel-dispatch packets that share
 // pre-built argument blocks in device memory, the doorbell is rung once, and the host spins on the last packet's
 // completion signal.  The packet layout (header bits, fence scopes by position, ring wrap-around and flow control) is

@@ -1,12 +1,15 @@
 // aql_packet_test.cpp — host unit test of the AQL packet builder (aql_packets.cpp): header bits, fence scopes by
 // position, grid in work-items, segment sizes, argument-block address, ring wrap-around and flow control.  No GPU, no
-// HSA runtime: a fake ring stands in for the queue.  Prints "aql packet test ok" on success (tests/test_aql_packets.py).
+// HSA runtime: a fake ring stands in for the queue.  Also the batch plan (step_plan.hpp) every step-kernel path runs by,
+// against the launch counts the GPU tests pin.  Prints "aql packet test ok" on success (tests/test_aql_packets.py).
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "aql_chain.hpp"
+#include "step_plan.hpp"
 
+using namespace sixdof;
 using namespace sixdof::aql;
 
 #define CHECK(c)                                                              \
@@ -96,9 +99,58 @@ void check_chain(uint64_t size, uint64_t start, const std::vector<Run>& runs) {
     }
 }
 
+struct Batch {
+    uint64_t ticks, launches, graph_launches;
+};
+
+// A ladder of batches on one handle with K ticks per launch, as the GPU tests run it: `check[i]`, batch i opens with the
+// accel-check launch.  The hipGraph and AQL paths count what the plan replays as graph_launches, an eager handle nothing.
+void check_ladder(uint32_t K, const std::vector<Batch>& ladder, const std::vector<bool>& check) {
+    for (size_t i = 0; i < ladder.size(); i++) {
+        const Batch& x = ladder[i];
+        const BatchPlan b = plan_batch(x.ticks, K, check[i], true);
+        CHECK(b.launches() == x.launches && b.chains.launches() == x.graph_launches);
+        CHECK(b.check_ticks + b.full * K + b.rem == x.ticks && b.rem < K && b.chains.launches() <= b.full);
+        CHECK((b.check_ticks != 0) == check[i]);
+        const BatchPlan eager = plan_batch(x.ticks, K, check[i], false);
+        CHECK(eager.launches() == x.launches && eager.chains.launches() == 0);
+    }
+}
+
+void check_chains(uint64_t full, bool open, uint64_t n_long, uint64_t n_short, uint32_t tail) {
+    const ChainPlan c = plan_chains(full);
+    CHECK(c.open == open && c.n_long == n_long && c.n_short == n_short && c.tail == tail);
+}
+
+void check_plans() {
+    // tests/test_gpu_graph_replay.py K1_LADDER and K4_LADDER: only the first batch after the upload opens with the check launch
+    const std::vector<Batch> k1 = {{40, 40, 39},    {3, 3, 0},       {4, 4, 4},       {20, 20, 20},    {35, 35, 32},
+                                   {36, 36, 36},    {543, 543, 543}, {547, 547, 544}, {600, 600, 600}, {4099, 4099, 4096}};
+    std::vector<bool> first(k1.size(), false);
+    first[0] = true;
+    check_ladder(1, k1, first);
+    check_ladder(4, {{8, 2, 0}, {103, 26, 25}}, {true, false});
+    // tests/test_gpu_aql_chain.py K8_TICKS: -(-n // 8) launches; the test uploads before entries 0 and 9
+    const uint64_t k8[] = {20, 17, 18, 19, 21, 22, 23, 5, 3, 100, 7, 23, 61, 8, 30, 1, 4099};
+    for (size_t i = 0; i < sizeof(k8) / sizeof(k8[0]); i++) {
+        const BatchPlan b = plan_batch(k8[i], 8, i == 0 || i == 9, true);
+        CHECK(b.launches() == (k8[i] + 7) / 8 && b.check_ticks + b.full * 8 + b.rem == k8[i]);
+    }
+    CHECK(plan_batch(5, 8, true, true).check_ticks == 5 && plan_batch(0, 8, true, true).launches() == 0);
+    // the chains behind those counts: an opening 32-launch chain from 544 launches on, tails of at least kGraphMinLen
+    check_chains(39, false, 0, 1, 7);
+    check_chains(3, false, 0, 0, 0);
+    check_chains(4, false, 0, 0, 4);
+    check_chains(543, false, 0, 16, 31);
+    check_chains(544, true, 4, 0, 0);
+    check_chains(600, true, 4, 1, 24);
+    check_chains(4099, true, 31, 3, 0);
+}
+
 }  // namespace
 
 int main() {
+    check_plans();
     CHECK(sizeof(hsa_kernel_dispatch_packet_t) == 64);
     for (uint64_t n : {1u, 2u, 3u, 20u, 4096u})
         for (uint64_t i = 0; i < n; i++) check_header(header_setup(i, n), i, n);

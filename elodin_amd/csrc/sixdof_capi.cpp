@@ -29,6 +29,7 @@
 #include "kernels.hpp"
 #include "abi_guard.hpp"
 #include "aql_chain.hpp"
+#include "step_plan.hpp"
 
 using namespace sixdof;
 
@@ -64,7 +65,43 @@ double now_ms() {
 
 uint64_t cid(const char* s) { return sixdof_component_id(s); }
 
-constexpr uint32_t kAqlSlots = 8;   // argument blocks of AQL chains per handle (sixdof_handle::aql_args)
+constexpr uint32_t kAqlSlots = 8;   // argument blocks of AQL chains per handle (Replay::aql_args)
+
+// What the step kernel's batches replay: captured hipGraphs, and the queue and argument blocks of AQL chains (aql_chain.hpp).
+// Both are built from `key` and dropped together.
+struct Replay {
+    // Everything a replayed launch bakes in: the batch's StepParams (column pointers, n, both time steps, effector ops, cache
+    // policy) with n_ticks = K and tick0 = hist_slot0 = 0 (read only off the graph-eligible paths).  Integrator and dtype are
+    // fixed per handle.
+    StepParams key{};
+    std::map<uint32_t, hipGraphExec_t> graphs;   // replay graphs by chain length (launches per replay)
+    bool aql_off = false;                   // SIXDOF_AQL=0 when the handle was created: keep the hipGraph path
+    aql::Device* aql_dev = nullptr;
+    std::string aql_why;                    // why AQL setup failed (the hipGraph path then stays); not retried
+    std::string aql_fault;                  // a chain failed on the queue: every later step fails with this
+    void* aql_args = nullptr;               // device arena of argument blocks (kAqlSlots)
+    std::map<uint64_t, aql::Run> aql_runs;  // by (accel_in_check, n_ticks): kernel, argument block, grid
+    uint64_t aql_slot_key[kAqlSlots] = {};  // the run whose block each spare slot (2 ..) holds, 0: none
+    uint32_t aql_next_spare = 2;            // the spare slot the next new run takes
+
+    void drop() {
+        for (auto& kv : graphs) hipGraphExecDestroy(kv.second);
+        graphs.clear();
+        aql_runs.clear();
+        std::fill(std::begin(aql_slot_key), std::end(aql_slot_key), 0);
+        aql_next_spare = 2;
+    }
+    // `P`: a batch's parameters (n_ticks = K).  Whatever was built from other parameters is dropped.
+    void rekey(StepParams P) {
+        P.tick0 = P.hist_slot0 = 0;   // fill_step_params memsets the struct: the padding compares equal too
+        if (std::memcmp(&P, &key, sizeof(P)) != 0) drop(), key = P;
+    }
+    void release() {
+        drop();
+        if (aql_args && aql_fault.empty()) hipFree(aql_args);   // after a failed chain a dispatch may still read it
+        aql::release(aql_dev);
+    }
+};
 
 }  // namespace
 
@@ -127,20 +164,7 @@ struct sixdof_handle {
     uint64_t ap_max_ticks = 0;
     double* d_tick_refs = nullptr;
     size_t tick_refs_cap = 0;
-    // graph cache for long batches
-    std::map<uint32_t, hipGraphExec_t> graphs;   // replay graphs by chain length (launches per replay), one StepParams signature
-    uint32_t graph_k = 0;
-    uint64_t graph_sig = 0;
-    // AQL chains (aql_chain.hpp): graph-eligible batches of a built-in pipe as pre-built dispatch packets
-    bool aql_off = false;                   // SIXDOF_AQL=0 when the handle was created: keep the hipGraph path
-    aql::Device* aql_dev = nullptr;
-    std::string aql_why;                    // why AQL setup failed (the hipGraph path then stays); not retried
-    std::string aql_fault;                  // a chain failed on the queue: every later step fails with this
-    void* aql_args = nullptr;               // device arena of argument blocks (kAqlSlots)
-    std::map<uint64_t, aql::Run> aql_runs;  // by (accel_in_check, n_ticks): kernel, argument block, grid; of aql_params
-    uint64_t aql_slot_key[kAqlSlots] = {};  // the key whose block each spare slot (2 ..) holds, ~0: none
-    uint32_t aql_next_spare = 2;            // the spare slot the next new key takes
-    StepParams aql_params{};                // the batch parameters the argument blocks were built from (tick0 = 0)
+    Replay replay;
     std::string path;                       // sixdof_step_path's answer
     mutable std::string err;
 
@@ -170,10 +194,6 @@ struct sixdof_handle {
         c.rows.clear();
         c.live = nullptr;
         c.joined = false;
-    }
-    void drop_graph() {
-        for (auto& kv : graphs) hipGraphExecDestroy(kv.second);
-        graphs.clear();
     }
     bool has_pair_op() const {
         for (auto& o : ops)
@@ -275,7 +295,7 @@ int sixdof_create(const sixdof_desc* d, sixdof_handle** out) try {
     h->desc = *d;
     if (h->desc.ticks_per_launch == 0) h->desc.ticks_per_launch = 1;
     const char* aql_env = std::getenv("SIXDOF_AQL");   // "0": hipGraph replay instead of AQL chains (A/B runs)
-    h->aql_off = aql_env && aql_env[0] == '0';
+    h->replay.aql_off = aql_env && aql_env[0] == '0';
     h->device = d->device_ordinal;
     h->id_pos = cid("world_pos");
     h->id_vel = cid("world_vel");
@@ -299,7 +319,7 @@ void sixdof_destroy(sixdof_handle* h) try {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    h->drop_graph();
+    h->replay.release();
     if (h->copy_stream) hipStreamSynchronize(h->copy_stream);
     for (auto& kv : h->cols) {
         h->free_join(kv.second);
@@ -322,8 +342,6 @@ void sixdof_destroy(sixdof_handle* h) try {
     if (h->custom_dl) dlclose(h->custom_dl);
     if (h->pair_dl) dlclose(h->pair_dl);
     for (hipEvent_t e : h->launch_events) hipEventDestroy(e);
-    if (h->aql_args && h->aql_fault.empty()) hipFree(h->aql_args);   // after a failed chain a dispatch may still read it
-    aql::release(h->aql_dev);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->evp0) hipEventDestroy(h->evp0);
@@ -335,7 +353,7 @@ void sixdof_destroy(sixdof_handle* h) try {
 int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_cols) try {
     if (!h || (!cols && n_cols)) return SIXDOF_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    h->drop_graph();
+    h->replay.drop();
     for (size_t i = 0; i < n_cols; i++) {
         const sixdof_column& c = cols[i];
         if (c.ndim > 1) return h->fail(SIXDOF_ERR_UNSUPPORTED, "bind_columns: only scalar / 1-D components");
@@ -451,7 +469,7 @@ int sixdof_set_effectors(sixdof_handle* h, const sixdof_effector_op* ops, size_t
         return h->fail(SIXDOF_ERR_UNSUPPORTED, "set_effectors: at most 4 per-entity ops");
     if (n_pair > 1) return h->fail(SIXDOF_ERR_UNSUPPORTED, "set_effectors: at most one pair op");
     h->ops.assign(ops, ops + n_ops);
-    h->drop_graph();
+    h->replay.drop();
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -517,7 +535,7 @@ int sixdof_set_edges(sixdof_handle* h, const uint64_t* from_ids, const uint64_t*
     h->edge_dst.swap(dst);
     h->csr_start.swap(start);
     h->csr_dst.swap(cdst);
-    h->drop_graph();
+    h->replay.drop();
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -680,7 +698,7 @@ int sixdof_set_tick(sixdof_handle* h, uint64_t tick) try {
 int sixdof_set_ticks_per_launch(sixdof_handle* h, uint32_t k) try {
     if (!h || k == 0) return SIXDOF_ERR_INVALID_ARGUMENT;
     h->desc.ticks_per_launch = k;
-    h->drop_graph();
+    h->replay.drop();
     return h->resident ? prepare_graph(h) : SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -1099,7 +1117,7 @@ int sixdof_set_custom_pipe(sixdof_handle* h, const char* so_path, const uint64_t
     h->custom_model_width.assign(k_model, 0u);
     if (col_widths && k_model) col_widths(h->custom_model_width.data());
     h->ops.clear();
-    h->drop_graph();
+    h->replay.drop();
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -1124,7 +1142,7 @@ int sixdof_set_custom_pair(sixdof_handle* h, const char* so_path) try {
     sixdof_effector_op op{};
     op.kind = SIXDOF_EFF_EDGE_CUSTOM;
     h->ops.push_back(op);
-    h->drop_graph();
+    h->replay.drop();
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -1140,7 +1158,7 @@ int sixdof_set_history(sixdof_handle* h, uint32_t ring_ticks) try {
     for (void* p : h->d_model_hist) if (p) hipFree(p);
     h->d_model_hist.clear();
     h->hist_ring = 0;
-    h->drop_graph();
+    h->replay.drop();
     if (ring_ticks == 0) return SIXDOF_OK;
     const size_t n = h->desc.n_entities, es = h->elem_size();
     const size_t widths[4] = {7, 6, 6, 6};
@@ -1272,77 +1290,30 @@ int sixdof_upload_column(sixdof_handle* h, uint64_t component_id) try {
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
-// Launches per replayed chain.  A long chain amortises the gap between two replays (4,096 launches: 4.96 -> 4.83 us each with
-// 128-launch chains) but starts later (100 launches as one chain: 8 % slower than 32 + 32 + 32 + 4), so a batch OPENS with a
-// 32-launch chain and, when at least four fit, continues with 128-launch ones (profiles/r02_graph_len_ab.txt).
-constexpr uint32_t kGraphLen = 32;
-constexpr uint32_t kGraphLong = 128;
-
 bool graph_eligible(const sixdof_handle* h) {
     return (h->desc.flags & SIXDOF_FLAG_USE_GRAPH) && !(h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) && !h->hist_ring &&
            (h->custom_model.empty() || h->custom_tick_free) && h->model == 0 && !h->has_pair_op();
 }
 
-constexpr uint32_t kGraphMinLen = 4;   // shorter chains are launched eagerly (a replay costs ~10-16 us of host time)
+// Whether a batch of `n_ticks` opens with the accel-check launch: the first RK4 launch after an upload (step_rigid).
+static bool opens_with_check(const sixdof_handle* h, uint64_t n_ticks) {
+    return h->accel_is_host_data && h->desc.integrator == SIXDOF_INTEGRATOR_RK4 && n_ticks > 0;
+}
+
 constexpr size_t kGraphCacheMax = 8;
 
-// What a batch of `full` K-tick launches replays, in this order: an opening 32-launch chain (long batches only: 200
-// launches as 32 + 128 + 40 measured 5 % slower), `n_long` 128-launch chains, `n_short` further 32-launch chains, and one
-// chain of the `tail` launches left (0 when fewer than kGraphMinLen: those run eagerly).  A short batch as a whole, e.g.
-// 20 launches, is its tail — so a short timed region is steady-state device work too, not eager launches racing the host.
-struct ChainPlan {
-    bool open = false;
-    uint64_t n_long = 0, n_short = 0;
-    uint32_t tail = 0;
-    uint64_t launches() const { return (open ? kGraphLen : 0) + n_long * kGraphLong + n_short * kGraphLen + tail; }
-};
-
-static ChainPlan plan_chains(uint64_t full) {
-    ChainPlan c;
-    if (full >= kGraphLen + 4 * kGraphLong) {
-        c.open = true;
-        c.n_long = (full - kGraphLen) / kGraphLong;
-        full -= kGraphLen + c.n_long * kGraphLong;
-    }
-    c.n_short = full / kGraphLen;
-    if (full % kGraphLen >= kGraphMinLen) c.tail = static_cast<uint32_t>(full % kGraphLen);
-    return c;
-}
-
-// Everything a captured launch bakes in: the whole argument block (column pointers, n, both time steps, effector ops
-// and their column pointers, cache policy) plus integrator and dtype.  Any change re-captures — e.g. sixdof_tick
-// overwriting simulation_time_step from its input slot, or a rebind.  tick0 / hist_slot0 differ per launch but are
-// only read by paths that are not graph-eligible.
-uint64_t step_signature(const sixdof_handle* h, StepParams P, uint32_t K) {
-    P.tick0 = 0;
-    P.hist_slot0 = 0;
-    P.n_ticks = K;
-    uint64_t sig = 0xcbf29ce484222325ull;
-    auto mix = [&](const void* p, size_t n) {
-        const unsigned char* b = static_cast<const unsigned char*>(p);
-        for (size_t i = 0; i < n; i++) sig = (sig ^ b[i]) * 0x100000001b3ull;
-    };
-    mix(&P, sizeof(P));
-    const int32_t extra[2] = {h->desc.integrator, h->desc.dtype};
-    mix(extra, sizeof(extra));
-    return sig;
-}
-
-// An executable graph of `len` identical launches of the step kernel (cached per chain length; all cached graphs share
-// one signature and are dropped together when it changes).
-int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t K, uint32_t len, hipGraphExec_t* out) {
-    const uint64_t sig = step_signature(h, P, K);
-    if (h->graph_sig != sig || h->graph_k != K) h->drop_graph();
-    auto it = h->graphs.find(len);
-    if (it != h->graphs.end()) {
+// An executable graph of `len` identical launches of the step kernel, cached per chain length (Replay::key holds for all).
+int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t len, hipGraphExec_t* out) {
+    std::map<uint32_t, hipGraphExec_t>& graphs = h->replay.graphs;
+    if (auto it = graphs.find(len); it != graphs.end()) {
         *out = it->second;
         return SIXDOF_OK;
     }
-    if (h->graphs.size() >= kGraphCacheMax) {   // many distinct batch lengths: keep the 32- and 128-launch chains, drop the rest
-        for (auto g = h->graphs.begin(); g != h->graphs.end();) {
+    if (graphs.size() >= kGraphCacheMax) {   // many distinct batch lengths: keep the 32- and 128-launch chains, drop the rest
+        for (auto g = graphs.begin(); g != graphs.end();) {
             if (g->first == kGraphLen || g->first == kGraphLong) { ++g; continue; }
             hipGraphExecDestroy(g->second);
-            g = h->graphs.erase(g);
+            g = graphs.erase(g);
         }
     }
     hipGraph_t g = nullptr;
@@ -1357,41 +1328,27 @@ int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t K, uint32_t len
     hipGraphDestroy(g);
     if (ie != hipSuccess) return h->hip_fail(ie, "hipGraphInstantiate");
     (void)hipGraphUpload(exec, h->stream);   // move the one-off device-side setup out of the first replay
-    h->graphs[len] = exec;
-    h->graph_k = K;
-    h->graph_sig = sig;
+    graphs[len] = exec;
     *out = exec;
     return SIXDOF_OK;
 }
 
 // The graphs a plan replays, from the cache or captured now: g[0] the 32-launch chain, g[1] the 128-launch one, g[2] the
 // tail.  The tail comes last, so a cache eviction it triggers (which keeps the 32- and 128-launch chains) drops none of them.
-static int ensure_plan_graphs(sixdof_handle* h, const StepParams& P, uint32_t K, const ChainPlan& c, hipGraphExec_t g[3]) {
+static int ensure_plan_graphs(sixdof_handle* h, const StepParams& P, const ChainPlan& c, hipGraphExec_t g[3]) {
     int rc = SIXDOF_OK;
-    if (c.open || c.n_short) rc = ensure_graph(h, P, K, kGraphLen, &g[0]);
-    if (rc == SIXDOF_OK && c.n_long) rc = ensure_graph(h, P, K, kGraphLong, &g[1]);
-    if (rc == SIXDOF_OK && c.tail) rc = ensure_graph(h, P, K, c.tail, &g[2]);
+    if (c.open || c.n_short) rc = ensure_graph(h, P, kGraphLen, &g[0]);
+    if (rc == SIXDOF_OK && c.n_long) rc = ensure_graph(h, P, kGraphLong, &g[1]);
+    if (rc == SIXDOF_OK && c.tail) rc = ensure_graph(h, P, c.tail, &g[2]);
     return rc;
 }
 
 // ---- AQL chains ------------------------------------------------------------------------------------------------
 // A graph-eligible batch of a built-in pipe is written into the process's own HSA queue as dispatch packets of the same
-// kernel objects HIP launches (select_step), with argument blocks built ahead of the batch.  plan_chains stays the
-// accounting: what it would replay counts as graph_launches, the launches it leaves (and the accel-check launch) as eager.
+// kernel objects HIP launches (select_step), with argument blocks built ahead of the batch.  The launches are plan_batch's.
 
 constexpr size_t kAqlSlotBytes = (sizeof(StepParams) + 255) / 256 * 256;
 constexpr double kAqlStallS = 60.0;     // no packet of a chain started or finished for this long: the queue is stuck
-constexpr int kAqlFallback = 1;         // step_aql: nothing submitted, take the hipGraph path
-
-// Why a batch of this handle cannot take the AQL path, or null.
-static const char* aql_ineligible(const sixdof_handle* h) {
-    if (h->aql_off) return "SIXDOF_AQL=0";
-    if (!graph_eligible(h)) return "not graph-eligible";
-    if (h->custom_launch) return "generated pipe";
-    if (h->desc.flags & SIXDOF_FLAG_ASYNC_STEP) return "ASYNC_STEP";
-    if (h->desc.n_entities == 0) return "no rows";
-    return nullptr;
-}
 
 // The packet run of one launch of `P` with `check` / `ticks` (its kernel and argument block, count 0), built on first use.
 // The argument blocks of the K-tick launches keep slots 0 (plain) and 1 (accel check) for as long as the parameters hold.
@@ -1399,122 +1356,117 @@ static const char* aql_ineligible(const sixdof_handle* h) {
 // a batch holds at most one such block (aql_batch), so no block a batch is about to run can be overwritten by its own
 // later lookups, and nothing is in flight between two batches.
 static bool aql_run(sixdof_handle* h, const StepParams& P, uint32_t check, uint32_t ticks, aql::Run* out) {
+    Replay& rp = h->replay;
     const uint64_t key = uint64_t(check) << 32 | ticks;
-    if (auto it = h->aql_runs.find(key); it != h->aql_runs.end()) return *out = it->second, true;
+    if (auto it = rp.aql_runs.find(key); it != rp.aql_runs.end()) return *out = it->second, true;
     uint32_t slot_index = check;
     if (ticks != h->desc.ticks_per_launch) {
-        slot_index = h->aql_next_spare;
-        h->aql_next_spare = slot_index + 1 == kAqlSlots ? 2 : slot_index + 1;
-        h->aql_runs.erase(h->aql_slot_key[slot_index]);
-        h->aql_slot_key[slot_index] = ~0ull;
+        slot_index = rp.aql_next_spare;
+        rp.aql_next_spare = slot_index + 1 == kAqlSlots ? 2 : slot_index + 1;
+        rp.aql_runs.erase(rp.aql_slot_key[slot_index]);
+        rp.aql_slot_key[slot_index] = 0;
     }
     StepParams Q = P;
     Q.accel_in_check = check;
     Q.n_ticks = ticks;
     Q.tick0 = Q.hist_slot0 = 0;   // read only by generated and history-ring pipes, which never take this path
     const StepKernel k = select_step(Q, h->desc.integrator, h->desc.dtype);
-    if (!k.fn) return h->aql_why = "no built-in kernel for this launch", false;
+    if (!k.fn) return rp.aql_why = "no built-in kernel for this launch", false;
     aql::Run r;
-    if (!aql::kernel_code(h->aql_dev, k.fn, sizeof(StepParams), &r.code, &h->aql_why)) return false;
-    if (r.code.kernarg_align > 256) return h->aql_why = "kernarg alignment above 256 bytes", false;
-    char* slot = static_cast<char*>(h->aql_args) + slot_index * kAqlSlotBytes;
+    if (!aql::kernel_code(rp.aql_dev, k.fn, sizeof(StepParams), &r.code, &rp.aql_why)) return false;
+    if (r.code.kernarg_align > 256) return rp.aql_why = "kernarg alignment above 256 bytes", false;
+    char* slot = static_cast<char*>(rp.aql_args) + slot_index * kAqlSlotBytes;
     hipError_t e = hipMemcpy(slot, &Q, sizeof(Q), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return h->aql_why = std::string("hipMemcpy (argument block): ") + hipGetErrorString(e), false;
+    if (e != hipSuccess) return rp.aql_why = std::string("hipMemcpy (argument block): ") + hipGetErrorString(e), false;
     r.kernarg = slot;
     r.blocks = k.grid.x;
-    h->aql_runs[key] = r;
-    if (slot_index >= 2) h->aql_slot_key[slot_index] = key;
+    rp.aql_runs[key] = r;
+    if (slot_index >= 2) rp.aql_slot_key[slot_index] = key;
     return *out = r, true;
 }
 
-// Whether the next batch takes the AQL path; sets the queue and the batch's argument blocks up on first use.  `P`: the
-// batch's parameters (K ticks per launch).  A faulted handle answers yes: step_aql then reports the fault.
-static bool aql_ready(sixdof_handle* h, StepParams* P) {
-    if (aql_ineligible(h) || !h->aql_why.empty()) return false;
-    if (!h->aql_fault.empty()) return true;
-    if (fill_step_params(h, P) != SIXDOF_OK) return false;
+// The runs of a batch planned by `b`: the accel-check launch, the K-tick launches (what the plan replays and the eager
+// ones it leaves are the same packets: one run), the remainder.  Apart from the two K-tick blocks, the runs hold at most one
+// block: a remainder needs n_ticks >= K, and then the check launch runs K ticks.
+static bool aql_batch(sixdof_handle* h, const StepParams& P, const BatchPlan& b, aql::Run runs[3]) {
+    const uint32_t K = h->desc.ticks_per_launch;
+    if ((b.check_ticks && !aql_run(h, P, 1, b.check_ticks, &runs[0])) || (b.full && !aql_run(h, P, 0, K, &runs[1])) ||
+        (b.rem && !aql_run(h, P, 0, b.rem, &runs[2])))
+        return false;
+    runs[0].count = b.check_ticks ? 1 : 0;
+    runs[1].count = b.full;
+    runs[2].count = b.rem ? 1 : 0;
+    return true;
+}
+
+enum class Path { kApollo, kPair, kAql, kRigid };   // kRigid: the step kernel through HIP, hipGraph replays or eager
+
+struct Route {
+    Path path;
+    const char* why = nullptr;   // kRigid: why the batch is no AQL chain
+    int rc = SIXDOF_OK;          // the step kernel's parameters could not be made: the step fails with this
+    BatchPlan plan{};            // kAql, kRigid: the batch's launches
+};
+
+// The path of a batch of `n_ticks`: what sixdof_step runs, sixdof_step_path reports and the prepare calls build for.  For
+// the step kernel, *P gets the batch's parameters (n_ticks = K) and the replay caches are keyed to them.  kAql has built
+// the batch's packet runs into runs[]; when they cannot be built, aql_why says why, and this batch, like every later one,
+// takes kRigid.  A handle whose chain faulted stays on kAql, where the step reports the fault.
+static Route choose_path(sixdof_handle* h, uint64_t n_ticks, StepParams* P, aql::Run runs[3]) {
+    if (h->model == 1) return {Path::kApollo};
+    if (h->has_pair_op()) return {Path::kPair};
+    Replay& rp = h->replay;
+    const bool replay = graph_eligible(h);
+    const char* why = nullptr;   // why the batch is no AQL chain
+    if (rp.aql_off) why = "SIXDOF_AQL=0";
+    else if (!replay) why = "not graph-eligible";
+    else if (h->custom_launch) why = "generated pipe";
+    else if (h->desc.flags & SIXDOF_FLAG_ASYNC_STEP) why = "ASYNC_STEP";
+    else if (h->desc.n_entities == 0) why = "no rows";
+    else if (!rp.aql_why.empty()) why = rp.aql_why.c_str();   // setup failed earlier: not retried
+    else if (!rp.aql_fault.empty()) return {Path::kAql};
+    else if (!h->resident) why = "columns not uploaded yet";
+    if (!h->bound) return {Path::kRigid, why, SIXDOF_ERR_COMPONENT_NOT_FOUND};
+    if (int rc = fill_step_params(h, P); rc != SIXDOF_OK) return {Path::kRigid, why ? why : h->err.c_str(), rc};
     const uint32_t K = h->desc.ticks_per_launch;
     P->n_ticks = K;
-    if (!h->aql_dev) {
-        if (!(h->aql_dev = aql::acquire(h->device, &h->aql_why))) return false;
-        hipError_t e = hipMalloc(&h->aql_args, kAqlSlots * kAqlSlotBytes);
-        if (e != hipSuccess) return h->aql_args = nullptr, h->aql_why = std::string("hipMalloc: ") + hipGetErrorString(e), false;
+    if (replay) rp.rekey(*P);
+    const BatchPlan plan = plan_batch(n_ticks, K, opens_with_check(h, n_ticks), replay);
+    if (!why && !rp.aql_dev && (rp.aql_dev = aql::acquire(h->device, &rp.aql_why))) {   // the queue and the arena, once
+        if (hipError_t e = hipMalloc(&rp.aql_args, kAqlSlots * kAqlSlotBytes); e != hipSuccess)
+            rp.aql_args = nullptr, rp.aql_why = std::string("hipMalloc: ") + hipGetErrorString(e);
     }
-    // what step_signature hashes for the graph cache, compared whole (integrator and dtype are fixed per handle)
-    StepParams key = *P;
-    key.tick0 = key.hist_slot0 = 0;
-    if (std::memcmp(&key, &h->aql_params, sizeof(key)) != 0) {
-        h->aql_runs.clear();
-        std::fill(std::begin(h->aql_slot_key), std::end(h->aql_slot_key), ~0ull);
-        h->aql_next_spare = 2;
-        h->aql_params = key;
-    }
-    aql::Run r;
-    if (!aql_run(h, *P, 0, K, &r)) return false;
-    // the first RK4 batch after an upload opens with the accel-check launch (step_rigid)
-    if (h->accel_is_host_data && h->desc.integrator == SIXDOF_INTEGRATOR_RK4 && !aql_run(h, *P, 1, K, &r)) return false;
-    return true;
+    if (!why && (!rp.aql_why.empty() || !aql_batch(h, *P, plan, runs))) why = rp.aql_why.c_str();
+    return {why ? Path::kRigid : Path::kAql, why, SIXDOF_OK, plan};
 }
 
-// The launches of a batch of `n_ticks`, as step_rigid makes them: the accel-check launch when `check`, the K-tick launches
-// (what plan_chains replays and the eager ones it leaves are the same packets: one run), the remainder.  *full: the K-tick
-// launches.  Apart from the two K-tick blocks, the runs hold at most one block: a remainder needs n_ticks >= K, and then the
-// check launch runs K ticks.
-static bool aql_batch(sixdof_handle* h, const StepParams& P, uint64_t n_ticks, bool check, aql::Run runs[3], uint64_t* full) {
-    const uint32_t K = h->desc.ticks_per_launch;
-    *full = n_ticks / K;
-    uint32_t rem = static_cast<uint32_t>(n_ticks % K);
-    const uint32_t check_ticks = static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks));
-    if (check) {
-        if (n_ticks >= K) *full -= 1;
-        else rem = 0;
-    }
-    if ((check && !aql_run(h, P, 1, check_ticks, &runs[0])) || (*full && !aql_run(h, P, 0, K, &runs[1])) ||
-        (rem && !aql_run(h, P, 0, rem, &runs[2])))
-        return false;
-    runs[0].count = check ? 1 : 0;
-    runs[1].count = *full;
-    runs[2].count = rem ? 1 : 0;
-    return true;
-}
-
-static bool aql_check_launch(const sixdof_handle* h, uint64_t n_ticks) {
-    return h->accel_is_host_data && n_ticks > 0 && h->desc.integrator == SIXDOF_INTEGRATOR_RK4;
-}
-
-// step_rigid as one AQL chain: the same launches, counted the same way, then a spin on the last packet.
-static int step_aql(sixdof_handle* h, const StepParams& P, uint64_t n_ticks, uint64_t* launches) {
-    if (!h->aql_fault.empty()) return h->fail(SIXDOF_ERR_BACKEND, h->aql_fault);
+// Builds what a batch of `n_ticks` replays ahead of it, so that no step call pays for it: its AQL argument blocks, or the
+// hipGraphs of its chains (capture + instantiation).  Whether the batch opens with the accel-check launch the library
+// cannot know (a warm-up batch may come first), so both shapes are built.
+static int prepare_batch(sixdof_handle* h, const Route& r, const StepParams& P, uint64_t n_ticks) {
+    if (r.path == Path::kAql && !h->replay.aql_fault.empty()) return SIXDOF_OK;   // the step reports the fault
     aql::Run runs[3];
-    uint64_t full = 0;
-    if (!aql_batch(h, P, n_ticks, aql_check_launch(h, n_ticks), runs, &full)) return kAqlFallback;
-    // the chain bypasses the HIP stream: let what was enqueued there (and on the null stream it waits for) finish first
-    for (hipStream_t s : {h->stream, static_cast<hipStream_t>(nullptr)}) {
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipErrorNotReady) HIP_TRY(h, hipStreamSynchronize(s));
-        else if (q != hipSuccess) return h->hip_fail(q, "hipStreamQuery");
+    hipGraphExec_t unused[3] = {};
+    for (bool check : {false, opens_with_check(h, n_ticks)}) {
+        const BatchPlan b = plan_batch(n_ticks, h->desc.ticks_per_launch, check, true);
+        if (r.path == Path::kAql) (void)aql_batch(h, P, b, runs);   // on failure the step takes the hipGraph path
+        else if (int rc = ensure_plan_graphs(h, P, b.chains, unused); rc != SIXDOF_OK) return rc;
     }
-    double device_ms = 0.0;
-    if (!aql::run_chain(h->aql_dev, runs, 3, kAqlStallS, &device_ms, &h->aql_fault))
-        return h->fail(SIXDOF_ERR_BACKEND, h->aql_fault);
-    if (n_ticks > 0) h->accel_is_host_data = false;
-    *launches = runs[0].count + runs[1].count + runs[2].count;
-    h->last.graph_launches = plan_chains(full).launches();
-    h->last.kernel_device_ms = device_ms;
+    if (r.path != Path::kAql) HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SIXDOF_OK;
 }
 
-// Build the replay graph ahead of the first long batch (called when the columns become resident and when the batch
-// shape changes), so that no step call pays for capture + instantiation.
+// Builds what a first long batch replays (called when the columns become resident and when the batch shape changes): the
+// blocks of a K-tick launch, or the 32-launch chain.
 int prepare_graph(sixdof_handle* h) {
     if (!h->bound || !graph_eligible(h)) return SIXDOF_OK;
     StepParams P;
-    if (aql_ready(h, &P)) return SIXDOF_OK;
-    int rc = fill_step_params(h, &P);
-    if (rc != SIXDOF_OK) return SIXDOF_OK;     // not steppable yet (columns missing): the step call will report it
-    P.n_ticks = h->desc.ticks_per_launch;
+    aql::Run runs[3];
+    const Route r = choose_path(h, h->desc.ticks_per_launch, &P, runs);
+    if (r.rc != SIXDOF_OK) return SIXDOF_OK;     // not steppable yet (columns missing): the step call will report it
+    if (r.path == Path::kAql) return prepare_batch(h, r, P, h->desc.ticks_per_launch);
     hipGraphExec_t unused = nullptr;
-    rc = ensure_graph(h, P, h->desc.ticks_per_launch, kGraphLen, &unused);
+    int rc = ensure_graph(h, P, kGraphLen, &unused);
     if (rc == SIXDOF_OK) (void)hipStreamSynchronize(h->stream);
     return rc;
 }
@@ -1525,45 +1477,21 @@ int sixdof_prepare_step(sixdof_handle* h, uint64_t n_ticks) try {
     if (!graph_eligible(h)) return SIXDOF_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     StepParams P;
-    if (aql_ready(h, &P)) {
-        // nothing to capture: build the argument blocks the batch needs, with and without the accel-check launch (whether
-        // a warm-up batch takes it first the library cannot know)
-        aql::Run runs[3];
-        uint64_t full = 0;
-        for (bool check : {false, aql_check_launch(h, n_ticks)})
-            if (!aql_batch(h, P, n_ticks, check, runs, &full)) break;   // the step falls back and reports why
-        return SIXDOF_OK;
-    }
-    int rc = fill_step_params(h, &P);
-    if (rc != SIXDOF_OK) return rc;
-    const uint32_t K = h->desc.ticks_per_launch;
-    P.n_ticks = K;
-    hipGraphExec_t unused[3] = {};
-    const uint64_t full = n_ticks / K;
-    if ((rc = ensure_plan_graphs(h, P, K, plan_chains(full), unused)) != SIXDOF_OK) return rc;
-    // the first RK4 step after an upload takes one eager launch out of `full` (step_rigid: accel_in_check), so that
-    // batch replays `full - 1` launches; whether the batch being prepared is that one the library cannot know (a warm-up
-    // may come first), so both shapes are captured
-    if (h->accel_is_host_data && h->desc.integrator == SIXDOF_INTEGRATOR_RK4 && full > 0 &&
-        (rc = ensure_plan_graphs(h, P, K, plan_chains(full - 1), unused)) != SIXDOF_OK)
-        return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SIXDOF_OK;
+    aql::Run runs[3];
+    const Route r = choose_path(h, n_ticks, &P, runs);
+    return r.rc != SIXDOF_OK ? r.rc : prepare_batch(h, r, P, n_ticks);
 } SIXDOF_ABI_CATCH(err_of(h))
 
 const char* sixdof_step_path(sixdof_handle* h) try {
     if (!h) return "invalid handle";
     (void)hipSetDevice(h->device);
     StepParams P;
-    if (h->model == 1) h->path = "apollo";
-    else if (h->has_pair_op()) h->path = "pair";
-    else if (!h->aql_fault.empty()) h->path = "aql (failed: " + h->aql_fault + ")";
-    else if (h->bound && h->resident && aql_ready(h, &P)) h->path = "aql";
-    else {
-        const char* why = aql_ineligible(h);
-        h->path = std::string(graph_eligible(h) ? "hipgraph: " : "eager: ") +
-                  (why ? why : !h->aql_why.empty() ? h->aql_why.c_str() : "columns not uploaded yet");
-    }
+    aql::Run runs[3];
+    const Route r = choose_path(h, h->desc.ticks_per_launch, &P, runs);   // as for a batch of one launch
+    if (r.path == Path::kApollo) h->path = "apollo";
+    else if (r.path == Path::kPair) h->path = "pair";
+    else if (r.path == Path::kAql) h->path = h->replay.aql_fault.empty() ? "aql" : "aql (failed: " + h->replay.aql_fault + ")";
+    else h->path = std::string(graph_eligible(h) ? "hipgraph: " : "eager: ") + r.why;
     return h->path.c_str();
 } SIXDOF_ABI_CATCH_VALUE(err_of(h), nullptr)
 
@@ -1608,19 +1536,13 @@ static int step_pair(sixdof_handle* h, uint64_t n_ticks, uint64_t* launches) {
     return SIXDOF_OK;
 }
 
-// The step kernel: K ticks per launch, long batches replayed from hipGraphs (launch-bound regime: a 65,536-entity tick is
-// a few microseconds of device time), the rest launched eagerly.
-static int step_rigid(sixdof_handle* h, uint64_t n_ticks, uint64_t* launches) {
-    StepParams P;
-    int rc = fill_step_params(h, &P);
-    if (rc != SIXDOF_OK) return rc;
+// The step kernel through HIP: K ticks per launch, the plan's chains replayed from hipGraphs (launch-bound regime: a
+// 65,536-entity tick is a few microseconds of device time), the rest launched eagerly.
+static int step_rigid(sixdof_handle* h, const StepParams& P, const BatchPlan& b, uint64_t n_ticks, uint64_t* launches) {
     const uint32_t K = h->desc.ticks_per_launch;
-    uint64_t full = n_ticks / K;
-    uint32_t rem = static_cast<uint32_t>(n_ticks % K);
-    P.n_ticks = K;
     const bool time_each = (h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) != 0;
     if (time_each) {
-        const uint64_t need = 2 * (full + (rem ? 1 : 0));
+        const uint64_t need = 2 * b.launches();
         if (need > 8192) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "step: TIME_EACH_LAUNCH supports <= 4096 launches per call");
         while (h->launch_events.size() < need) {
             hipEvent_t e = nullptr;
@@ -1639,38 +1561,49 @@ static int step_rigid(sixdof_handle* h, uint64_t n_ticks, uint64_t* launches) {
         ++*launches;
         return SIXDOF_OK;
     };
-    if (h->accel_is_host_data && n_ticks > 0) {
+    if (n_ticks > 0) h->accel_is_host_data = false;
+    if (b.check_ticks) {
         // First launch after an upload: the world_accel column holds whatever the host put there.  The reference's RK4
         // forms v_s = v0 + 0 * a_in on stage 0 (rk4.rs:96-100), so a non-finite row poisons that tick; this one launch
         // reads the column to do the same (step_kernel.hpp).  Every later a_in is this kernel's own output and is
         // already folded into v0.  A launch of its own, eager, so the replay graphs never carry the flag.
-        h->accel_is_host_data = false;
-        if (h->desc.integrator == SIXDOF_INTEGRATOR_RK4) {
-            StepParams P1 = P;
-            P1.accel_in_check = 1;
-            if ((rc = eager(P1, static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks)))) != SIXDOF_OK) return rc;
-            if (n_ticks >= K) full -= 1;   // that launch was one of the K-tick launches ...
-            else rem = 0;                  // ... or the whole (short) batch
-        }
+        StepParams P1 = P;
+        P1.accel_in_check = 1;
+        if (int rc = eager(P1, b.check_ticks); rc != SIXDOF_OK) return rc;
     }
-    uint64_t graph_launches = 0;
-    const ChainPlan c = graph_eligible(h) ? plan_chains(full) : ChainPlan{};
-    if (c.launches()) {
+    if (const ChainPlan& c = b.chains; c.launches()) {
         hipGraphExec_t g[3] = {};
-        if ((rc = ensure_plan_graphs(h, P, K, c, g)) != SIXDOF_OK) return rc;
+        if (int rc = ensure_plan_graphs(h, P, c, g); rc != SIXDOF_OK) return rc;
         // a capture may just have happened after ev0 was recorded: re-record so the pair brackets real work only
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
         const std::pair<hipGraphExec_t, uint64_t> replays[4] = {{g[0], c.open ? 1 : 0}, {g[1], c.n_long}, {g[0], c.n_short}, {g[2], c.tail ? 1 : 0}};
         for (const auto& [graph, times] : replays)
             for (uint64_t i = 0; i < times; i++) HIP_TRY(h, hipGraphLaunch(graph, h->stream));
-        graph_launches = c.launches();
-        *launches += graph_launches;
-        full -= graph_launches;
+        *launches += c.launches();
     }
-    h->last.graph_launches = graph_launches;
-    for (uint64_t i = 0; i < full; i++)
-        if ((rc = eager(P, K)) != SIXDOF_OK) return rc;
-    if (rem && (rc = eager(P, rem)) != SIXDOF_OK) return rc;
+    h->last.graph_launches = b.chains.launches();
+    for (uint64_t i = b.chains.launches(); i < b.full; i++)
+        if (int rc = eager(P, K); rc != SIXDOF_OK) return rc;
+    return b.rem ? eager(P, b.rem) : SIXDOF_OK;
+}
+
+// The batch's packet runs as one AQL chain: step_rigid's launches, counted the same way, then a spin on the last packet.
+static int step_aql(sixdof_handle* h, const BatchPlan& b, const aql::Run runs[3], uint64_t n_ticks, uint64_t* launches) {
+    Replay& rp = h->replay;
+    if (!rp.aql_fault.empty()) return h->fail(SIXDOF_ERR_BACKEND, rp.aql_fault);
+    // the chain bypasses the HIP stream: let what was enqueued there (and on the null stream it waits for) finish first
+    for (hipStream_t s : {h->stream, static_cast<hipStream_t>(nullptr)}) {
+        const hipError_t q = hipStreamQuery(s);
+        if (q == hipErrorNotReady) HIP_TRY(h, hipStreamSynchronize(s));
+        else if (q != hipSuccess) return h->hip_fail(q, "hipStreamQuery");
+    }
+    double device_ms = 0.0;
+    if (!aql::run_chain(rp.aql_dev, runs, 3, kAqlStallS, &device_ms, &rp.aql_fault))
+        return h->fail(SIXDOF_ERR_BACKEND, rp.aql_fault);
+    if (n_ticks > 0) h->accel_is_host_data = false;
+    *launches = b.launches();
+    h->last.graph_launches = b.chains.launches();
+    h->last.kernel_device_ms = device_ms;
     return SIXDOF_OK;
 }
 
@@ -1706,15 +1639,16 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
         return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: SIXDOF_INTEGRATOR_NONE runs generated system programs only (sixdof_set_custom_pipe)");
     uint64_t launches = 0;
     StepParams P;
+    aql::Run runs[3];
+    const Route r = choose_path(h, n_ticks, &P, runs);
+    if (r.rc != SIXDOF_OK) return r.rc;
     // an AQL chain waits for itself and times itself from its packets: no event pair on the HIP stream
-    int rc = h->model == 0 && !h->has_pair_op() && aql_ready(h, &P) ? step_aql(h, P, n_ticks, &launches) : kAqlFallback;
-    const bool aql = rc != kAqlFallback;
-    if (!aql) {
-        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-        rc = h->model == 1 ? step_apollo(h, n_ticks, &launches)
-             : h->has_pair_op() ? step_pair(h, n_ticks, &launches)
-                                : step_rigid(h, n_ticks, &launches);
-    }
+    const bool aql = r.path == Path::kAql;
+    if (!aql) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    const int rc = aql                       ? step_aql(h, r.plan, runs, n_ticks, &launches)
+                   : r.path == Path::kApollo ? step_apollo(h, n_ticks, &launches)
+                   : r.path == Path::kPair   ? step_pair(h, n_ticks, &launches)
+                                             : step_rigid(h, P, r.plan, n_ticks, &launches);
     if (rc != SIXDOF_OK) return rc;
     if (!aql) HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     if (!async_step && !aql) {
@@ -1726,14 +1660,12 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
             (void)hipGetLastError();
             HIP_TRY(h, hipStreamSynchronize(h->stream));
         }
-    }
-    h->tick += n_ticks;  // increment_sim_tick (globals.rs:42-44), once per tick
-    h->step_pending = async_step;
-    if (!async_step && !aql) {
         float ms0 = 0.f;
         hipEventElapsedTime(&ms0, h->ev0, h->ev1);
         h->last.kernel_device_ms = ms0;
     }
+    h->tick += n_ticks;  // increment_sim_tick (globals.rs:42-44), once per tick
+    h->step_pending = async_step;
     h->last.kernel_invoke_ms = now_ms() - t0;
     h->last.launches = launches;
     h->last.ticks = n_ticks;

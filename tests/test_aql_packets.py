@@ -1,6 +1,7 @@
 """The AQL packet builder of the step chains (csrc/aql_packets.cpp), as pure host code: header bits and fence scopes by position
 in the chain, grid in work-items, segment sizes, argument-block address and alignment, ring wrap-around and flow control on the
-read index.  csrc/aql_packet_test.cpp drives it through a fake ring; no GPU, no HSA runtime."""
+read index.  csrc/aql_packet_test.cpp drives it through a fake ring; no GPU, no HSA runtime.  The same binary checks the batch
+plan (csrc/step_plan.hpp) against the launch counts the GPU tests pin."""
 import shutil
 import subprocess
 from pathlib import Path

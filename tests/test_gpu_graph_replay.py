@@ -1,4 +1,4 @@
-"""The replay-chain plan of sixdof_step (csrc/sixdof_capi.cpp plan_chains): how many launches of a batch replay from a
+"""The replay-chain plan of sixdof_step (csrc/step_plan.hpp plan_chains): how many launches of a batch replay from a
 captured graph at the benchmark's size, and that the replayed launches give the bits of eager ones."""
 import sys
 from pathlib import Path
