@@ -126,6 +126,10 @@ SYMBOLS = {
     "sixdof_bind_world": (C.c_int, [_H, C.c_void_p]),
     "sixdof_set_custom_pipe": (C.c_int, [_H, C.c_char_p, C.POINTER(C.c_uint64), C.c_size_t]),
     "sixdof_set_custom_pair": (C.c_int, [_H, C.c_char_p]),
+    "sixdof_set_fold_edges": (C.c_int, [_H, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_size_t]),
+    "sixdof_build_fold_table": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "sixdof_download_async": (C.c_int, [_H, C.c_uint32]),
     "sixdof_download_wait": (C.c_int, [_H]),
     "sixdof_sync": (C.c_int, [_H]),

@@ -391,8 +391,13 @@ class World:
         return out
 
     def build(self, system: System, simulation_rate: float = 120.0, telemetry_rate: Optional[float] = None,
-              device: int = 0, backend: str = "hip", _dry: bool = False) -> "Exec":
-        """World.build (world_builder.rs:1737-1780): validate rates, fix globals, bind the backend."""
+              device: int = 0, backend: str = "hip", _dry: bool = False, graph_tables: str = "auto") -> "Exec":
+        """World.build (world_builder.rs:1737-1780): validate rates, fix globals, bind the backend.
+        graph_tables: where stand-alone folds between the systems find their edges — "baked" into the generated code (at most
+        65,536 edges per fold), "device" memory (any number; HipExec.set_graph_edges replaces them), or "auto": baked up to
+        65,536 edges, device beyond."""
+        if graph_tables not in ("auto", "baked", "device"):
+            raise ValueError('graph_tables must be "auto", "baked" or "device"')
         import os
         backend = os.environ.get("ELODIN_BACKEND", backend)    # same override as world_builder.rs:248
         if backend != "hip":
@@ -549,7 +554,10 @@ class World:
                     body_rows, row_ids = at_real, ext_ids
                 where_row = {int(e): k for k, e in enumerate(row_ids)}
                 fold_rows = {name: ([where_row[a] for a in f_], [where_row[b] for b in t_]) for name, (f_, t_) in fold_pairs.items()}
-            probe = _dsl.Program(program_stages[0], eff_pipe, program_stages[1]).trace(widths, fold_edges=fold_rows)
+            fold_tables = graph_tables
+            if fold_tables == "auto":
+                fold_tables = "device" if any(len(f_) > 65536 for f_, _ in (fold_rows or {}).values()) else "baked"
+            probe = _dsl.Program(program_stages[0], eff_pipe, program_stages[1]).trace(widths, fold_edges=fold_rows, fold_tables=fold_tables)
             partial = [n for n, _ in probe.columns if "#fold" not in n and not n.endswith("#head") and n not in hidden
                        and not np.all(np.isin(row_ids, self.column(n)[1]))]
             if body_rows is not None:
@@ -586,7 +594,7 @@ class World:
                         side_entities.update(int(e) for e in stray)
             effs = _dsl.Program(program_stages[0], eff_pipe, program_stages[1], substeps=substeps)
             extra_columns = {}
-            for name, w_ in effs.trace(widths, partial, fold_edges=fold_rows).columns:
+            for name, w_ in effs.trace(widths, partial, fold_edges=fold_rows, fold_tables=fold_tables).columns:
                 if name == "has:world_pos":                      # which rows are real Bodies (the others are stand-ins)
                     mask = np.zeros((len(row_ids), 1))
                     mask[body_rows] = 1.0
@@ -636,6 +644,10 @@ class World:
                 effs.append(e)
         same = all(np.array_equal(v, ids) for v in column_ids.values())
         edges = None
+        fold_ids = None      # device fold tables: the executor installs the folds' edges itself, as entity ids of its rows
+        if program_stages is not None and fold_rows and fold_tables == "device":
+            rid = np.asarray(row_ids, dtype=np.uint64)
+            fold_ids = {name: (rid[np.asarray(f_, dtype=np.int64)], rid[np.asarray(t_, dtype=np.int64)]) for name, (f_, t_) in fold_rows.items()}
         if program_stages is None and not isinstance(system.effectors, _dsl.Pipe) and system.effectors.edge_component:
             edges = self.edge_pairs(system.effectors.edge_component)
             if system.effectors.edge_component == self.TOTAL_EDGE:   # only pairs of Body entities can join the fold's queries
@@ -654,7 +666,8 @@ class World:
                       integrator=L.INTEGRATOR_NONE if getattr(system, "no_six_dof", False) else system.integrator.value,
                       effectors=effs, edges=edges,
                       ticks_per_launch=ticks_per_telemetry * (substeps if program_stages is not None else 1), device=device,
-                      column_entity_ids=None if same else column_ids, columns=extra_columns,
+                      column_entity_ids=None if same else column_ids, columns=extra_columns, graph_edges=fold_ids,
+                      graph_tables="auto" if fold_ids is None else "device",
                       reuse_trace=True)      # traced above, in THIS build, with the presence masks and fold rows the executor cannot know
         ex = Exec(hip, self, ticks_per_telemetry, dt)
         ex._substeps = substeps if program_stages is not None else 1

@@ -15,7 +15,7 @@ import os
 import subprocess
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Optional, Dict, List, Sequence
+from typing import Optional, Dict, List, Sequence, Tuple
 
 from . import dsl
 
@@ -1286,6 +1286,126 @@ __global__ __launch_bounds__(64) void fold{j}_commit(const StepParams P) {{
 '''
 
 
+# What a device-table fold kernel gets next to StepParams (csrc/sixdof_capi.cpp holds the same struct and checks its size through
+# sixdof_custom_fold_info).  The sources are PARTITIONED: [0, n_lane) are folded by one lane each, [n_lane, n_src) by one wave
+# each (out-degree >= 64 of a fold that may be regrouped) — the two lists of a fold are two ranges of one CSR.
+_FOLD_TABLE = """
+// ---- fold tables in device memory (sixdof_set_fold_edges) ----
+struct FoldTable {
+    const uint32_t* src_rows;     // [n_src] row of source i (replica 0)
+    const uint32_t* row_start;    // [n_src + 1] first edge of source i
+    const uint32_t* dst;          // [row_start[n_src]] target rows (replica 0), spawn order inside a source
+    uint32_t n_src;
+    uint32_t n_lane;              // sources [0, n_lane): one lane each; [n_lane, n_src): one wave each
+};
+"""
+
+
+def _fold_wave_ok(fs: "dsl.TracedFoldStage") -> bool:
+    """The fold asked for waves (dsl.GraphFold.wave_fold) and is a plain sum, so partial folds may be regrouped."""
+    return bool(getattr(fs.traced.fold, "wave_fold", False)) and _graph_fold_kinds(fs.traced.outputs, fs.out[2]) is not None
+
+
+def _emit_fold_stage_device(u: _Unit, fs: "dsl.TracedFoldStage") -> str:
+    """_emit_fold_stage with the CSR read from device memory (FoldTable): the same arithmetic in the same order — one lane per
+    source walks row_start[i] .. row_start[i + 1] in spawn order, gather_batch and direct_out as in the baked flavour.  Nothing
+    about the graph is in the text.  A fold that may be regrouped (_fold_wave_ok) gets a second kernel, one WAVE per source, for
+    the sources the host put behind n_lane (out-degree >= 64): the baked wave kernel's partition and shuffle tree.  Every index
+    is a plain load; the host has checked every target row (sixdof_set_fold_edges), the kernels guard i and the source row."""
+    j = fs.index
+    f = fs.traced.fold
+    w = fs.out[2]
+    body_ptr = {"world_pos": "P.pos", "world_vel": "P.vel", "inertia": "P.inertia"}
+    ptr = lambda name, slot: f"static_cast<const T*>({body_ptr[name]})" if slot is None else f"static_cast<const T*>(P.model_cols[{slot}])"
+    leaves = {f"acc_{k}": f"acc[{k}]" for k in range(w)}
+    dst_of = lambda e_: f"F.dst[{e_}]"
+    loads_a, loads_b = [], []
+    for i, (n, slot, wn) in enumerate(fs.left):
+        for k in range(wn):
+            leaves[f"a{i}_{k}"] = f"a{i}[{k}]"
+        loads_a.append(f"    const T* a{i} = {ptr(n, slot)} + (size_t)row * {wn};")
+    for i, (n, slot, wn) in enumerate(fs.right):
+        for k in range(wn):
+            leaves[f"b{i}_{k}"] = f"b{i}[{k}]"
+        loads_b.append(f"        const T* b{i} = {ptr(n, slot)} + (size_t)(base + {dst_of('e')}) * {wn};")
+    body = "\n".join(emit_block(u, [(f"acc[{k}]", e) for k, e in enumerate(fs.traced.outputs)], leaves, indent="        "))
+    init = ", ".join(f"T({v!r})" for v in f.init)
+    nl = "\n"
+    batched = ""
+    B = int(getattr(f, "gather_batch", 1) or 1)
+    if B > 1 and sum(wn for _, _, wn in fs.right) <= 16:
+        decl = "".join(f"        T rb{i}[{B}][{wn}];\n" for i, (_, _, wn) in enumerate(fs.right))
+        fetch = "".join(f"            {{ const T* g = {ptr(n, slot)} + (size_t)(base + {dst_of('e + u')}) * {wn};\n"
+                        f"#pragma unroll\n              for (int k = 0; k < {wn}; k++) rb{i}[u][k] = g[k]; }}\n" for i, (n, slot, wn) in enumerate(fs.right))
+        use = "".join(f"            const T* b{i} = rb{i}[u];\n" for i in range(len(fs.right)))
+        inner = "\n".join("    " + ln for ln in body.split("\n"))
+        batched = (f"    for (; e_hi - e >= {B}u; e += {B}) {{\n{decl}#pragma unroll\n        for (int u = 0; u < {B}; u++) {{\n{fetch}        }}\n"
+                   f"#pragma unroll\n        for (int u = 0; u < {B}; u++) {{\n{use}{inner}\n        }}\n    }}\n")
+    count, stride = fs.replicas if fs.replicas else (1, 0)
+    direct = bool(getattr(f, "direct_out", False)) and fs.out[0] not in [n for n, _, _ in fs.left + fs.right]
+    out_slot = fs.out[1] if direct else fs.scratch_slot
+    wave = ""
+    if _fold_wave_ok(fs):
+        kinds = _graph_fold_kinds(fs.traced.outputs, w)
+        zero = ", ".join("T(0)" for _ in range(w))
+        fin = "\n".join({"sum": f"        if (lane == 0) sc[{k}] = T({f.init[k]!r}) + v{k};", "keep": f"        if (lane == 0) sc[{k}] = T({f.init[k]!r});",
+                         "zero": f"        if (lane == 0) sc[{k}] = (e_hi > e_lo) ? T(0) : T({f.init[k]!r});"}[kd] for k, kd in enumerate(kinds))
+        red = "\n".join(f"        T v{k} = acc[{k}];\n#pragma unroll\n        for (int off = 32; off >= 1; off >>= 1) v{k} += __shfl_down(v{k}, off, 64);"
+                        for k, kd in enumerate(kinds) if kd == "sum")
+        wave = f'''// one WAVE per source of the wave range: lane l folds edges l, l + 64, ... from zero, a fixed shuffle tree adds the partials, init joins last
+template <class T>
+__global__ __launch_bounds__(64) void fold{j}_wave(const StepParams P, const FoldTable F) {{
+    const uint32_t gi = blockIdx.x, lane = threadIdx.x;
+    const uint32_t n_wave = F.n_src - F.n_lane;
+    if (n_wave == 0u || gi / n_wave >= {count}u) return;
+    const uint32_t i = F.n_lane + gi % n_wave, base = (gi / n_wave) * {stride}u;   // source within the template, replica's first row
+    const uint32_t row = base + F.src_rows[i];
+    if (row >= P.n) return;
+    const uint32_t e_lo = F.row_start[i], e_hi = F.row_start[i + 1];
+{nl.join(loads_a)}
+    T acc[{w}] = {{{zero}}};
+    for (uint32_t e = e_lo + lane; e < e_hi; e += 64u) {{
+{nl.join(loads_b)}
+{body}
+    }}
+    T* sc = static_cast<T*>(P.model_cols[{out_slot}]) + (size_t)row * {w};
+    {{
+{red}
+{fin}
+    }}
+}}
+'''
+    return f'''// ---- fold stage {j}: {fs.name}, edges in device memory{f" (x {count} replicas of {stride} rows)" if fs.replicas else ""} ----
+template <class T>
+__global__ __launch_bounds__(64) void fold{j}_kernel(const StepParams P, const FoldTable F) {{
+    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (F.n_lane == 0u || gi / F.n_lane >= {count}u) return;
+    const uint32_t i = gi % F.n_lane, base = (gi / F.n_lane) * {stride}u;   // source within the template, replica's first row
+    const uint32_t row = base + F.src_rows[i];
+    if (row >= P.n) return;
+    const uint32_t e_lo = F.row_start[i], e_hi = F.row_start[i + 1];
+{nl.join(loads_a)}
+    T acc[{w}] = {{{init}}};
+{("    uint32_t e = e_lo;" + nl + batched + "    for (; e < e_hi; e++) {") if batched else "    for (uint32_t e = e_lo; e < e_hi; e++) {"}
+{nl.join(loads_b)}
+{body}
+    }}
+    T* sc = static_cast<T*>(P.model_cols[{out_slot}]) + (size_t)row * {w};
+    for (int k = 0; k < {w}; k++) sc[k] = acc[k];
+}}
+{wave}template <class T>
+__global__ __launch_bounds__(64) void fold{j}_commit(const StepParams P, const FoldTable F) {{
+    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (F.n_src == 0u || gi / F.n_src >= {count}u) return;
+    const uint32_t row = (gi / F.n_src) * {stride}u + F.src_rows[gi % F.n_src];
+    if (row >= P.n) return;
+    const T* sc = static_cast<const T*>(P.model_cols[{fs.scratch_slot}]) + (size_t)row * {w};
+    T* o = static_cast<T*>(P.model_cols[{fs.out[1]}]) + (size_t)row * {w};
+    for (int k = 0; k < {w}; k++) o[k] = sc[k];
+}}
+'''
+
+
 # Integer components (el.PrimitiveType.I64: flags, counters, examples/stablehlo/sim.py:243-251) live in the executor's float
 # columns, exact up to 2^53 (2^24 in a float32 program); bitwise operators act on the integer the value holds.
 _BITWISE = '''
@@ -1330,6 +1450,38 @@ __device__ __forceinline__ double m_erfinv_fast(double u) {
     return static_cast<double>(p * static_cast<float>(u));
 }
 '''
+
+
+def _fold_table_exports(tp) -> Tuple[str, str]:
+    """The host side of a device-table object: where the library's tables land (sixdof_custom_set_fold_table), what it must know
+    per fold to build and check one (sixdof_custom_fold_info), and the launch entry's refusal to run a fold without its table."""
+    nf = len(tp.fold_stages)
+    dev = lambda fs_: bool(getattr(fs_, "device_tables", False))
+    info = ", ".join(f"{{{(1 if dev(fs_) else 0) | (2 if dev(fs_) and _fold_wave_ok(fs_) else 0)}u, "
+                     f"{fs_.replicas[0] if fs_.replicas else 1}u, {fs_.replicas[1] if fs_.replicas else 0}u}}" for fs_ in tp.fold_stages)
+    text = f"""// ---- the fold stages' tables: handed over by the library (sixdof_set_fold_edges) before a launch, passed to the kernels by value ----
+static thread_local sixdof::FoldTable g_fold_table[{nf}];
+static thread_local bool g_fold_set[{nf}];
+extern "C" unsigned sixdof_custom_fold_count() {{ return {nf}u; }}
+// out[0]: bit 0 the fold reads a table (a complete graph has none), bit 1 its long sources may be folded by waves; out[1], out[2]: the
+// replica count and stride the object was generated for (1, 0: none); out[3]: sizeof(FoldTable)
+extern "C" int sixdof_custom_fold_info(unsigned fold, unsigned* out) {{
+    static const unsigned info[{nf}][3] = {{{info}}};
+    if (fold >= {nf}u || !out) return 1;
+    out[0] = info[fold][0]; out[1] = info[fold][1]; out[2] = info[fold][2]; out[3] = static_cast<unsigned>(sizeof(sixdof::FoldTable));
+    return 0;
+}}
+extern "C" int sixdof_custom_set_fold_table(unsigned fold, const sixdof::FoldTable* t) {{
+    if (fold >= {nf}u) return 1;
+    g_fold_set[fold] = t != nullptr;
+    if (t) g_fold_table[fold] = *t;
+    return 0;
+}}
+
+"""
+    need = " || ".join(f"!g_fold_set[{fs_.index}]" for fs_ in tp.fold_stages if dev(fs_))
+    guard = f"    if ({need}) return static_cast<int>(hipErrorInvalidValue);      // a fold without its table: never a launch\n" if need else ""
+    return text, guard
 
 
 def generate_source(tp, dtype: str, integrator: int, fast_math: bool = False, window_soa: bool = False,
@@ -1384,6 +1536,7 @@ def _source(tp, dtype: str, integrator: int, fast_math: bool, u: _Unit) -> str:
         launch_k = lambda pipe, ig, params: (
             f"    hipLaunchKernelGGL((sixdof_step_kernel<{T}, {ig}, {pipe}, {pname}>), grid, dim3(kWave), 0, s, {params});   // built for this executor's cache policy only\n")
     staged = is_prog and bool(tp.fold_stages)
+    fold_exports = fold_guard = ""
     body_dead = False
     if is_prog and not staged and integrator == 2 and getattr(tp, "body_free", False):
         # the program says no system touches a Body column (a whole-world StableHLO tick, stablehlo.world_system): hold it to that —
@@ -1453,6 +1606,20 @@ def _source(tp, dtype: str, integrator: int, fast_math: bool, u: _Unit) -> str:
         for i, c in enumerate(chain):
             if c[0] == "fold":
                 fs = c[1]
+                if getattr(fs, "device_tables", False):
+                    # grid sizes are data: the launch entry reads them from the table the library handed over
+                    parts.append(_emit_fold_stage_device(u, fs))
+                    cnt = fs.replicas[0] if fs.replicas else 1
+                    direct = bool(getattr(fs.traced.fold, "direct_out", False)) and fs.out[0] not in [n_ for n_, _, _ in fs.left + fs.right]
+                    jf = fs.index
+                    call = (f"        {{ const FoldTable& F = g_fold_table[{jf}];\n"
+                            f"          if (F.n_lane) hipLaunchKernelGGL(fold{jf}_kernel<{T}>, dim3((F.n_lane * {cnt}u + 63u) / 64u), dim3(64), 0, s, q, F);\n")
+                    if _fold_wave_ok(fs):
+                        call += f"          if (F.n_src > F.n_lane) hipLaunchKernelGGL(fold{jf}_wave<{T}>, dim3((F.n_src - F.n_lane) * {cnt}u), dim3(64), 0, s, q, F);\n"
+                    if not direct:
+                        call += f"          if (F.n_src) hipLaunchKernelGGL(fold{jf}_commit<{T}>, dim3((F.n_src * {cnt}u + 63u) / 64u), dim3(64), 0, s, q, F);\n"
+                    calls.append(call + "        }")
+                    continue
                 parts.append(_emit_fold_stage(u, fs))
                 nb = (len(fs.src_rows) * (fs.replicas[0] if fs.replicas else 1) + 63) // 64
                 waves = (getattr(fs.traced.fold, "wave_fold", False) and _graph_fold_kinds(fs.traced.outputs, fs.out[2]) is not None)
@@ -1473,6 +1640,9 @@ def _source(tp, dtype: str, integrator: int, fast_math: bool, u: _Unit) -> str:
             tweak += "" if six else " qs.accel_in_check = 0;"
             calls.append(f"        {{ StepParams qs = q;{tweak}\n" + launch_k(f"PipeSeg{i}", ig, "qs").replace("    if", "          if", 1).replace("\n    else", "\n          else") + "        }")
         structs = "\n".join(parts)
+        if getattr(tp, "fold_tables", "baked") == "device":
+            structs = _FOLD_TABLE + structs
+            fold_exports, fold_guard = _fold_table_exports(tp)
         stage_comment = "// tick = " + " | ".join(("fold:" + c[1].name) if c[0] == "fold" else ("[" + " | ".join([s_.name for s_ in c[1]] + (["six_dof"] if c[3] and integrator != 2 else []) + [s_.name for s_ in c[2]]) + "]") for c in chain) + "\n"
         launch = ("    for (uint32_t t = 0; t < p->n_ticks; t++) {   // a fold needs every row of the link in front of it: one chain per tick\n"
                   "        StepParams q = *p;\n        q.n_ticks = 1;\n        q.tick0 = p->tick0 + t;\n        q.hist_slot0 = p->hist_slot0 + t;\n"
@@ -1512,10 +1682,10 @@ extern "C" void sixdof_custom_column_widths(unsigned* out) {{
     for (unsigned k = 0; k < {n_model}u; k++) out[k] = w[k];
 }}
 
-{rows_export}extern "C" int sixdof_custom_launch(const sixdof::StepParams* p, int integrator, int dtype, void* stream) {{
+{rows_export}{fold_exports}extern "C" int sixdof_custom_launch(const sixdof::StepParams* p, int integrator, int dtype, void* stream) {{
     using namespace sixdof;
     if (integrator != {integrator} || dtype != {0 if dtype == "float64" else 1}) return static_cast<int>(hipErrorInvalidValue);
-    if (p->n == 0) return static_cast<int>(hipSuccess);
+{fold_guard}    if (p->n == 0) return static_cast<int>(hipSuccess);
     const dim3 grid((p->n + kWave - 1) / kWave);
     hipStream_t s = static_cast<hipStream_t>(stream);
 {launch}    return static_cast<int>(hipGetLastError());

@@ -202,6 +202,29 @@ int main() {
         std::memcpy(lastrow, dv + (nn - 1) * 56, 56);
         CHECK(lastrow[6] == 3.0);
         sixdof_sink_destroy(z);
+
+        // the fold-table builder (what sixdof_set_fold_edges uploads): spawn order per source, the lane / wave partition, row checks —
+        // and every allocation of it failing once
+        {
+            const uint32_t fs[5] = {2, 0, 2, 0, 2}, fd[5] = {1, 2, 0, 1, 2};
+            uint32_t o_src[5], o_start[6], o_dst[5], n_src = 0, n_lane = 0;
+            long built = -1;
+            for (long k = 0; k < 16 && built < 0; k++) {
+                g_fail_in = k;
+                const int rc = sixdof_build_fold_table(fs, fd, 5, 3, 0, o_src, o_start, o_dst, &n_src, &n_lane);
+                g_fail_in = -1;
+                if (rc == SIXDOF_OK) { built = k; break; }
+                CHECK(rc == SIXDOF_ERR_OUT_OF_MEMORY);
+            }
+            CHECK(built > 0 && n_src == 2 && n_lane == 2 && o_src[0] == 0 && o_src[1] == 2);
+            CHECK(o_start[0] == 0 && o_start[1] == 2 && o_start[2] == 5);
+            const uint32_t want[5] = {2, 1, 1, 0, 2};
+            CHECK(std::memcmp(o_dst, want, sizeof(want)) == 0);
+            CHECK(sixdof_build_fold_table(fs, fd, 5, 2, 0, o_src, o_start, o_dst, &n_src, &n_lane) == SIXDOF_ERR_INVALID_ARGUMENT);      // row 2 with two rows
+            CHECK(sixdof_build_fold_table(fs, fd, 5, 3, 3, o_src, o_start, o_dst, &n_src, &n_lane) == SIXDOF_OK);                        // degree 3 -> a wave
+            CHECK(n_src == 2 && n_lane == 1 && o_src[0] == 0 && o_src[1] == 2 && o_start[1] == 2 && o_start[2] == 5);
+            CHECK(sixdof_build_fold_table(nullptr, nullptr, 0, 3, 64, nullptr, o_start, nullptr, &n_src, &n_lane) == SIXDOF_OK && n_src == 0 && o_start[0] == 0);
+        }
         CHECK(g_thrown > 20);
         std::printf("asan_host_test: exception barrier: %ld injected allocation failures came back as statuses\n", g_thrown);
     }

@@ -58,6 +58,29 @@ struct Column {
 
 thread_local std::string g_create_error;
 
+// What the fold kernels of a generated program with device fold tables take next to StepParams (elodin_amd/codegen.py emits the
+// same struct into the object, which reports its size: sixdof_custom_fold_info).  Sources [0, n_lane) are folded by one lane each,
+// [n_lane, n_src) by one wave each.
+struct FoldTable {
+    const uint32_t* src_rows;
+    const uint32_t* row_start;
+    const uint32_t* dst;
+    uint32_t n_src;
+    uint32_t n_lane;
+};
+constexpr uint32_t kFoldWaveDegree = 64;   // out-degree from which a regroupable fold gives a source a whole wave
+
+// One fold stage of the installed generated program, as the object describes it, and the table it currently reads.
+struct FoldSlot {
+    bool needs_table = false;   // false: the complete graph over a world's rows (arithmetic, no table)
+    bool wave_ok = false;       // a plain sum that asked for waves: long sources go behind n_lane
+    uint32_t count = 1, stride = 0;   // replicas the object was generated for (1, 0: none)
+    bool set = false;
+    uint32_t* d_blob = nullptr;       // [src_rows | row_start | dst]
+    FoldTable table{};
+};
+using SetFoldTableFn = int (*)(unsigned, const FoldTable*);
+
 double now_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
@@ -149,6 +172,9 @@ struct sixdof_handle {
     bool custom_tick_free = false;          // the generated program never looks at the absolute tick (layout bit 17): replayable
     int pair_only_small = -1;               // what the installed pair object was generated for (-1: both launch shapes)
     unsigned custom_rows_multiple = 1;      // rows a world of the generated program occupies (lane mode): the joined row count must be a multiple
+    // fold stages of a generated program that reads its edges from device memory (empty: none, or a baked object)
+    SetFoldTableFn custom_set_fold_table = nullptr;
+    std::vector<FoldSlot> custom_folds;
     // telemetry ring
     uint32_t hist_ring = 0;
     uint64_t hist_first_tick = 0;   // first tick (1-based count) recorded since the ring was enabled
@@ -194,6 +220,13 @@ struct sixdof_handle {
         c.rows.clear();
         c.live = nullptr;
         c.joined = false;
+    }
+    // the tables of the installed program's fold stages; the caller has drained the stream
+    void free_fold_tables() {
+        for (FoldSlot& f : custom_folds)
+            if (f.d_blob) hipFree(f.d_blob);
+        custom_folds.clear();
+        custom_set_fold_table = nullptr;
     }
     bool has_pair_op() const {
         for (auto& o : ops)
@@ -337,6 +370,7 @@ void sixdof_destroy(sixdof_handle* h) try {
     if (h->d_chunk_partial) hipFree(h->d_chunk_partial);
     if (h->d_scratch) hipFree(h->d_scratch);
     if (h->d_tick_refs) hipFree(h->d_tick_refs);
+    h->free_fold_tables();
     for (void* p : h->d_hist) if (p) hipFree(p);
     for (void* p : h->d_model_hist) if (p) hipFree(p);
     if (h->custom_dl) dlclose(h->custom_dl);
@@ -725,6 +759,10 @@ int build_dev_ops(sixdof_handle* h, DevOp* out, uint32_t* n_out, uint32_t* vel_i
     uint32_t n = 0;
     *vel_independent = 1;
     if (h->custom_launch) {   // generated pipe: slots are just the columns its code reads
+        for (size_t k = 0; k < h->custom_folds.size(); k++)
+            if (h->custom_folds[k].needs_table && !h->custom_folds[k].set)
+                return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: fold stage " + std::to_string(k) + " of the installed program reads its edges from "
+                               "device memory and has no table yet (sixdof_set_fold_edges)");
         for (uint64_t id : h->custom_aux) {
             Column* c = h->col(id);
             if (!c) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "step: column read by the generated pipe is not bound");
@@ -856,7 +894,12 @@ size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // built-in pipes or the handle's generated pipe
 hipError_t launch_any(sixdof_handle* h, const StepParams& P) {
     if (h->desc.integrator == SIXDOF_INTEGRATOR_NONE && !h->custom_launch) return hipErrorInvalidValue;
-    if (h->custom_launch) return static_cast<hipError_t>(h->custom_launch(&P, h->desc.integrator, h->desc.dtype, h->stream));
+    if (h->custom_launch) {
+        // the object keeps the tables it launches with per thread (one object may serve several handles): hand this handle's over
+        for (size_t k = 0; k < h->custom_folds.size(); k++)
+            if (h->custom_folds[k].needs_table) h->custom_set_fold_table(static_cast<unsigned>(k), h->custom_folds[k].set ? &h->custom_folds[k].table : nullptr);
+        return static_cast<hipError_t>(h->custom_launch(&P, h->desc.integrator, h->desc.dtype, h->stream));
+    }
     return launch_step(P, h->desc.integrator, h->desc.dtype, h->stream);
 }
 
@@ -1106,6 +1149,31 @@ int sixdof_set_custom_pipe(sixdof_handle* h, const char* so_path, const uint64_t
         dlclose(dl);
         return h->fail(SIXDOF_ERR_VALUE_SIZE_MISMATCH, "set_custom_pipe: column list does not match the generated code's layout");
     }
+    // fold stages that read their edges from device memory (optional exports; an object without them bakes its edges)
+    auto fold_count = reinterpret_cast<unsigned (*)()>(dlsym(dl, "sixdof_custom_fold_count"));
+    auto fold_info = reinterpret_cast<int (*)(unsigned, unsigned*)>(dlsym(dl, "sixdof_custom_fold_info"));
+    auto set_fold_table = reinterpret_cast<SetFoldTableFn>(dlsym(dl, "sixdof_custom_set_fold_table"));
+    std::vector<FoldSlot> folds;
+    if (fold_count && fold_info && set_fold_table) {
+        folds.resize(fold_count());
+        for (size_t k = 0; k < folds.size(); k++) {
+            unsigned info[4] = {0, 0, 0, 0};
+            if (fold_info(static_cast<unsigned>(k), info) != 0 || info[3] != sizeof(FoldTable)) {
+                dlclose(dl);
+                return h->fail(SIXDOF_ERR_BACKEND, "set_custom_pipe: the object's fold tables are not this library build's (FoldTable layout differs)");
+            }
+            folds[k].needs_table = (info[0] & 1u) != 0;
+            folds[k].wave_ok = (info[0] & 2u) != 0;
+            folds[k].count = info[1];
+            folds[k].stride = info[2];
+        }
+    }
+    if (h->stream) (void)hipStreamSynchronize(h->stream);      // nothing in flight reads the tables of the program being replaced
+    h->free_fold_tables();
+    if (!folds.empty()) {
+        h->custom_folds.swap(folds);
+        h->custom_set_fold_table = set_fold_table;
+    }
     if (h->custom_dl) dlclose(h->custom_dl);
     h->custom_dl = dl;
     h->custom_launch = launch;
@@ -1118,6 +1186,70 @@ int sixdof_set_custom_pipe(sixdof_handle* h, const char* so_path, const uint64_t
     if (col_widths && k_model) col_widths(h->custom_model_width.data());
     h->ops.clear();
     h->replay.drop();
+    return SIXDOF_OK;
+} SIXDOF_ABI_CATCH(err_of(h))
+
+int sixdof_set_fold_edges(sixdof_handle* h, uint32_t fold_index, const uint64_t* from_ids, const uint64_t* to_ids, size_t n_edges) try {
+    if (!h || ((!from_ids || !to_ids) && n_edges)) return SIXDOF_ERR_INVALID_ARGUMENT;
+    if (!h->custom_launch) return h->fail(SIXDOF_ERR_UNSUPPORTED, "set_fold_edges: no generated program is installed (sixdof_set_custom_pipe)");
+    if (!h->custom_set_fold_table)
+        return h->fail(SIXDOF_ERR_UNSUPPORTED, "set_fold_edges: the installed program bakes its folds' edges into its code; build it with device fold tables");
+    if (fold_index >= h->custom_folds.size())
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "set_fold_edges: fold_index " + std::to_string(fold_index) + " out of range (the program has " +
+                       std::to_string(h->custom_folds.size()) + " fold stages)");
+    FoldSlot& f = h->custom_folds[fold_index];
+    if (!f.needs_table) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "set_fold_edges: this fold stage folds the complete graph of a world: it has no edge table");
+    if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_fold_edges: bind Body columns first");
+    if (n_edges > 0xFFFFFFFFull) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "set_fold_edges: more than 2^32 - 1 edges");
+    const uint64_t n = h->desc.n_entities;
+    const bool replicated = f.count > 1 || f.stride > 0;
+    if (replicated && static_cast<uint64_t>(f.count) * f.stride != n)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "set_fold_edges: the program was generated for " + std::to_string(f.count) + " replicas of " +
+                       std::to_string(f.stride) + " rows; the handle has " + std::to_string(n) + " rows");
+    const uint32_t row_limit = replicated ? f.stride : static_cast<uint32_t>(std::min<uint64_t>(n, 0xFFFFFFFFull));
+    std::unordered_map<uint64_t, uint32_t> row_of;   // entity id -> row of the joined Body set
+    row_of.reserve(h->joined_ids.size() * 2);
+    for (size_t r = 0; r < h->joined_ids.size(); r++) row_of.emplace(h->joined_ids[r], static_cast<uint32_t>(r));
+    std::vector<uint32_t> src(n_edges), dst(n_edges);
+    for (size_t e = 0; e < n_edges; e++) {
+        auto a = row_of.find(from_ids[e]), b = row_of.find(to_ids[e]);
+        if (a == row_of.end() || b == row_of.end())
+            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_fold_edges: edge endpoint is not an entity of this handle");
+        src[e] = a->second;
+        dst[e] = b->second;
+    }
+    // one block [src_rows (n_src) | row_start (n_src + 1) | dst (n_edges)], built for the most sources there can be
+    std::vector<uint32_t> o_src(n_edges), o_start(n_edges + 1), o_dst(n_edges);
+    uint32_t n_src = 0, n_lane = 0;
+    const int brc = sixdof_build_fold_table(src.data(), dst.data(), n_edges, row_limit, f.wave_ok ? kFoldWaveDegree : 0u, o_src.data(),
+                                            o_start.data(), o_dst.data(), &n_src, &n_lane);
+    if (brc == SIXDOF_ERR_INVALID_ARGUMENT)
+        return h->fail(brc, replicated ? "set_fold_edges: with replicas the edges name entities of replica 0 only" : "set_fold_edges: an edge row lies outside the handle's rows");
+    if (brc != SIXDOF_OK) return h->fail(brc, "set_fold_edges: the table could not be built (out of memory)");
+    std::vector<uint32_t> blob;
+    blob.reserve(static_cast<size_t>(n_src) * 2 + 1 + n_edges);
+    blob.insert(blob.end(), o_src.begin(), o_src.begin() + n_src);
+    blob.insert(blob.end(), o_start.begin(), o_start.begin() + n_src + 1);
+    blob.insert(blob.end(), o_dst.begin(), o_dst.end());
+    HIP_TRY(h, hipSetDevice(h->device));
+    uint32_t* d_new = nullptr;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&d_new), blob.size() * sizeof(uint32_t)));
+    hipError_t e = hipMemcpyAsync(d_new, blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream);
+    // drains the batches that still read the old table, and the copy itself (its source is a local)
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        hipFree(d_new);
+        return h->hip_fail(e, "set_fold_edges: upload");
+    }
+    if (f.d_blob) hipFree(f.d_blob);
+    f.d_blob = d_new;
+    f.table.src_rows = d_new;
+    f.table.row_start = d_new + n_src;
+    f.table.dst = d_new + static_cast<size_t>(n_src) * 2 + 1;
+    f.table.n_src = n_src;
+    f.table.n_lane = n_lane;
+    f.set = true;
+    h->replay.drop();      // captured launches hold the old pointers and grid sizes
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 

@@ -3,6 +3,7 @@
 // entity id of every row, rows in spawn order, ids handed out sequentially, entity 0 = "Globals" carrying
 // `tick` (u64) and `simulation_time_step` (f64).  Pure host code (no HIP): usable and tested without a GPU.
 // A world is bound to a backend handle with sixdof_bind_world (sixdof_capi.cpp).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -182,5 +183,46 @@ void sixdof_world_advance_tick(sixdof_world* w, uint64_t n) try {
     auto it = w->host.find(sixdof_component_id("tick"));
     if (it != w->host.end() && it->second.buffer.size() >= 8) std::memcpy(it->second.buffer.data(), &w->tick, 8);
 } SIXDOF_ABI_CATCH_VALUE(err_of(w), )
+
+// The table of one fold stage of a generated program whose kernels read their edges from device memory
+// (sixdof_set_fold_edges uploads what this builds).  CSR by source: sources ascending, each source's targets in the order
+// given (spawn order, graph.rs:113-175 — the fold order).  With wave_min_degree > 0 the sources are PARTITIONED: those of
+// out-degree below it first (one lane each), the others behind them (one wave each), ascending inside each range.
+// Every row must be below row_limit: a table never names a row the kernels may not gather.
+int sixdof_build_fold_table(const uint32_t* src_rows, const uint32_t* dst_rows, size_t n_edges, uint32_t row_limit,
+                            uint32_t wave_min_degree, uint32_t* out_src, uint32_t* out_start, uint32_t* out_dst,
+                            uint32_t* n_src, uint32_t* n_lane) try {
+    if (((!src_rows || !dst_rows || !out_src || !out_dst) && n_edges) || !out_start || !n_src || !n_lane) return SIXDOF_ERR_INVALID_ARGUMENT;
+    if (n_edges > 0xFFFFFFFFull) return SIXDOF_ERR_INVALID_ARGUMENT;
+    for (size_t e = 0; e < n_edges; e++)
+        if (src_rows[e] >= row_limit || dst_rows[e] >= row_limit) return SIXDOF_ERR_INVALID_ARGUMENT;
+    // (source, position) keys: sorting them is a stable sort by source
+    std::vector<uint64_t> key(n_edges);
+    for (size_t e = 0; e < n_edges; e++) key[e] = static_cast<uint64_t>(src_rows[e]) << 32 | static_cast<uint64_t>(e);
+    std::sort(key.begin(), key.end());
+    struct Run { uint32_t row, first, degree; };
+    std::vector<Run> runs;
+    for (size_t e = 0; e < n_edges;) {
+        size_t f = e;
+        while (f < n_edges && key[f] >> 32 == key[e] >> 32) f++;
+        runs.push_back({static_cast<uint32_t>(key[e] >> 32), static_cast<uint32_t>(e), static_cast<uint32_t>(f - e)});
+        e = f;
+    }
+    uint32_t i = 0, at = 0;
+    out_start[0] = 0;
+    for (int pass = 0; pass < 2; pass++) {      // lane sources, then wave sources
+        for (const Run& r : runs) {
+            const bool wave = wave_min_degree > 0 && r.degree >= wave_min_degree;
+            if (wave != (pass == 1)) continue;
+            out_src[i] = r.row;
+            for (uint32_t k = 0; k < r.degree; k++) out_dst[at + k] = dst_rows[key[r.first + k] & 0xFFFFFFFFull];
+            at += r.degree;
+            out_start[++i] = at;
+        }
+        if (pass == 0) *n_lane = i;
+    }
+    *n_src = i;
+    return SIXDOF_OK;
+} SIXDOF_ABI_CATCH(nullptr)
 
 }  // extern "C"

@@ -1921,7 +1921,14 @@ class GraphFold:
     components (libs/nox-py/python/elodin/__init__.py:454-557, e.g. test_all.py:117-142): for every entity with out-edges,
     acc = init; for each out-edge in spawn order: acc = fn(acc, *left components of the source, *right components of the
     target); the result replaces the `out` component on source rows.  All folds read the component values from BEFORE the
-    system ran (the reference's arrays are immutable)."""
+    system ran (the reference's arrays are immutable).
+
+    Inside a program a fold may ask for `wave_fold = True` (stablehlo.world_program does, for scans of 64 edges or more): when
+    it is a plain sum its sources may be folded by a wave each — another association of the same sum, inside 1e-9 of the
+    sequential fold.  WHICH sources depends on where the program keeps its edges (Program.trace(fold_tables=...)): a baked
+    program folds EVERY source of such a fold by a wave; a program with device tables bins the sources by out-degree when the
+    table is installed — 64 edges or more: a wave (the baked kernel's partition and tree, the same bits), fewer: one lane,
+    sequentially (the reference's association bit for bit, so the last bits differ from the baked object's there)."""
 
     def __init__(self, fn: Callable, edge_component: str, left: Sequence[str], right: Sequence[str], out: str, init):
         self.fn, self.edge_component = fn, edge_component
@@ -2139,7 +2146,8 @@ class Program:
     translation unit and driven by one launch call, the columns staying in HBM between the links (codegen.py).  The edges of
     each fold's edge component are given as ROW pairs of the executor's row set when tracing (`fold_edges`, spawn order;
     HipExec resolves them from entity ids) and are baked into the generated code, like the reference bakes its gather
-    indices into the compiled tick."""
+    indices into the compiled tick — or, with trace(fold_tables="device"), kept out of it: the fold kernels then read the CSR
+    from device memory, where the library puts it (sixdof_set_fold_edges), and one generated object serves every graph."""
 
     def __init__(self, pre: Sequence, effectors: Pipe, post: Sequence, substeps: int = 1):
         """substeps = k > 1: the reference pipe was `pre | (six_dof | post) x k` (examples/drone/sim.py:173-208: three
@@ -2155,13 +2163,19 @@ class Program:
         return [s for s in self.pre + self.post if isinstance(s, GraphFold)]
 
     def trace(self, widths: Optional[Dict[str, int]] = None, partial: Sequence[str] = (), fold_edges=None,
-              fold_replicas: Optional[Tuple[int, int]] = None) -> "TracedProgram":
+              fold_replicas: Optional[Tuple[int, int]] = None, fold_tables: str = "baked") -> "TracedProgram":
         """fold_replicas=(count, stride): the executor holds `count` copies of one small world, `stride` rows each (a
         Monte-Carlo batch of graph worlds); `fold_edges` then describe replica 0 only (rows < stride) and every replica folds
-        over the same template, shifted by its base row — one baked CSR for the whole batch."""
+        over the same template, shifted by its base row — one baked CSR for the whole batch.
+        fold_tables: "baked" — every fold's CSR is written into the generated code (at most 65,536 edges per fold; the graph is
+        part of the object); "device" — the fold kernels read the CSR from device memory (sixdof_set_fold_edges): any number
+        of edges, and the generated text does not depend on the graph.  The trace keeps the CSR either way (the executor
+        installs it, the numpy walker of the tests reads it)."""
+        if fold_tables not in ("baked", "device"):
+            raise ValueError('fold_tables must be "baked" or "device"')
         if self._traced is None:
             Expr.fresh()
-            self._traced = TracedProgram(self, widths, partial, fold_edges, fold_replicas)
+            self._traced = TracedProgram(self, widths, partial, fold_edges, fold_replicas, fold_tables)
         return self._traced
 
 
@@ -2197,8 +2211,9 @@ class TracedFoldStage:
     BODY_WIDTH = {"world_pos": 7, "world_vel": 6, "inertia": 7}
 
     def __init__(self, fold: GraphFold, table: ColumnTable, index: int, edges, partial: Sequence[str] = (),
-                 replicas: Optional[Tuple[int, int]] = None):
+                 replicas: Optional[Tuple[int, int]] = None, device_tables: bool = False):
         self.name, self.index = fold.__name__, index
+        self.device_tables = False      # True: the kernels read this fold's CSR from device memory (a complete graph never has one)
         self.replicas = (int(replicas[0]), int(replicas[1])) if replicas else None
         names = list(dict.fromkeys(fold.left + fold.right + (fold.out,)))
         if fold.out in self.BODY_WIDTH:
@@ -2240,9 +2255,26 @@ class TracedFoldStage:
             raise ValueError("fold edges: from / to lengths differ")
         if self.replicas and any(not 0 <= r < self.replicas[1] for r in src + dst):
             raise ValueError(f"fold {self.name}: with fold_replicas the edges describe replica 0 (rows 0..{self.replicas[1] - 1})")
+        if device_tables:
+            # the CSR is data: sources ascending, each source's targets in the order given (a stable sort by source), kept as
+            # uint32 arrays for the executor and the walker — none of it enters the generated text
+            import numpy as _np
+            a_, b_ = _np.asarray(src, dtype=_np.int64), _np.asarray(dst, dtype=_np.int64)
+            if len(a_) > 0xFFFFFFFF or (len(a_) and (min(a_.min(), b_.min()) < 0 or max(a_.max(), b_.max()) > 0xFFFFFFFF)):
+                raise ValueError(f"fold {self.name}: edge rows and counts must fit 32 bits")
+            order = _np.argsort(a_, kind="stable")
+            rows_, counts_ = _np.unique(a_, return_counts=True)
+            self.device_tables = True
+            self.src_rows = rows_.astype(_np.uint32)
+            self.row_start = _np.concatenate([[0], _np.cumsum(counts_)]).astype(_np.uint32)
+            self.dst = b_[order].astype(_np.uint32)
+            self.written = [f"c{self.out[1]}_{k}" for k in range(self.out[2])] + [f"c{self.scratch_slot}_{k}" for k in range(self.out[2])]
+            self.every, self.phase, self.also_at, self.reads_accel, self.writes_inertia = 1, 0, None, False, False
+            return
         if len(src) > 65536:
             raise ValueError(f"fold {self.name}: {len(src)} edges — folds inside a program bake their edges into the generated "
-                             "code (<= 65,536); run a larger graph as a stand-alone fold (World.build(fold))")
+                             "code (<= 65,536); trace with fold_tables=\"device\" (HipExec / World.build: graph_tables) to keep the edges "
+                             "in device memory instead, or run the graph as a stand-alone fold (World.build(fold))")
         by_src: Dict[int, List[int]] = {}                            # spawn order kept inside a source (graph.rs:113-175)
         for a, b in zip(src, dst):
             by_src.setdefault(a, []).append(b)
@@ -2272,7 +2304,8 @@ MAX_PROGRAM_COLUMNS = 128      # = csrc/kernels.hpp kMaxModelCols (two kernarg p
 
 class TracedProgram:
     def __init__(self, prog: Program, widths: Optional[Dict[str, int]] = None, partial: Sequence[str] = (), fold_edges=None,
-                 fold_replicas: Optional[Tuple[int, int]] = None):
+                 fold_replicas: Optional[Tuple[int, int]] = None, fold_tables: str = "baked"):
+        self.fold_tables = fold_tables      # "baked" | "device": where the fold stages' kernels find their CSR
         self.table = ColumnTable("c", MAX_PROGRAM_COLUMNS, _MAT_MAX_ELEMS, widths)
         self.partial = tuple(partial)
         fold_edges = fold_edges or {}
@@ -2281,12 +2314,16 @@ class TracedProgram:
         def trace_item(s, after):
             if isinstance(s, GraphFold):
                 n_folds[0] += 1
-                return TracedFoldStage(s, self.table, n_folds[0] - 1, fold_edges.get(s.edge_component), self.partial, fold_replicas)
+                return TracedFoldStage(s, self.table, n_folds[0] - 1, fold_edges.get(s.edge_component), self.partial, fold_replicas,
+                                       device_tables=fold_tables == "device")
             return TracedSystem(s, self.table, self.partial, after_six_dof=after)
         self.pre = [trace_item(s, False) for s in prog.pre]
         self.pipe = TracedPipe(prog.effectors.effectors, table=self.table, partial=self.partial)
         self.post = [trace_item(s, True) for s in prog.post]
         self.fold_stages = [s for s in self.pre + self.post if isinstance(s, TracedFoldStage)]
+        # per fold stage: the edge component whose table the executor installs (fold_tables="device"), None for a stage that reads
+        # no table (a baked program; a complete graph)
+        self.device_fold_components = [s.traced.fold.edge_component if s.device_tables else None for s in self.fold_stages]
         # every system declares itself free of Body state and nothing else is in the pipe: a systems-only executor of this program
         # may leave the Body slabs alone (NoModel::kBodyDead, csrc/effectors.hpp)
         self.body_free = (bool(self.pre + self.post) and not self.fold_stages and not prog.effectors.effectors

@@ -57,7 +57,14 @@ class HipExec:
                  integrator: int = L.RK4, dtype=np.float64, effectors: Sequence[Effector] = (),
                  edges=None, ticks_per_launch: int = 1, use_graph: bool = False, device: int = 0,
                  tick: int = 0, column_entity_ids=None, columns=None, fast_math: bool = False, graph_edges=None,
-                 graph_replicas=None, guard_selects: Optional[bool] = None, reuse_trace: bool = False):
+                 graph_replicas=None, guard_selects: Optional[bool] = None, reuse_trace: bool = False,
+                 graph_tables: str = "auto"):
+        """graph_tables: where the stand-alone folds of a program find their edges (`graph_edges`).  "baked": written into the
+        generated code (at most 65,536 edges per fold; the graph is part of the object); "device": read from device memory
+        (sixdof_set_fold_edges: any number of edges, one object for every graph, replaceable with set_graph_edges); "auto":
+        baked while every listed fold has at most 65,536 edges, device beyond."""
+        if graph_tables not in ("auto", "baked", "device"):
+            raise ValueError('graph_tables must be "auto", "baked" or "device"')
         lib = L.lib()
         self._lib = lib
         self.dtype = np.dtype(dtype)
@@ -92,6 +99,7 @@ class HipExec:
         self._window_soa = False
         self._column_soa = False
         self._soa = {}            # program column name -> the element-major staging array bound to the C ABI
+        self._device_folds = []   # per fold stage of a program with device fold tables: its edge component (None: no table)
         d = L.Desc()
         d.struct_size = C.sizeof(L.Desc)
         d.device_ordinal = device
@@ -140,7 +148,9 @@ class HipExec:
                             raise KeyError(f"graph_edges[{name!r}]: edge endpoint {e} is not an entity of this executor") from None
                     if graph_replicas is not None and int(graph_replicas[0]) * int(graph_replicas[1]) != len(self.entity_ids):
                         raise ValueError("graph_replicas=(count, rows per replica) must cover the executor's rows exactly")
-                    custom = effectors.trace(widths, fold_edges=fold_rows, fold_replicas=graph_replicas)
+                    if graph_tables == "auto":
+                        graph_tables = "device" if any(not isinstance(frm, str) and len(frm) > 65536 for frm, _ in fold_rows.values()) else "baked"
+                    custom = effectors.trace(widths, fold_edges=fold_rows, fold_replicas=graph_replicas, fold_tables=graph_tables)
                     columns = dict(columns or {})
                     for fs in custom.fold_stages:       # scratch rows: a fold reads the values from before it ran
                         columns.setdefault(fs.scratch_name, np.zeros((self.world_pos.shape[0], fs.out[2])))
@@ -249,6 +259,16 @@ class HipExec:
                 rc = lib.sixdof_set_custom_pipe(self._h, str(so).encode(), ids, len(custom.columns))
                 if rc != L.OK:
                     _raise(self._h, rc, "sixdof_set_custom_pipe")
+                # a program with device fold tables: the fold stages that read one, by edge component; install what was given
+                self._device_folds = list(getattr(custom, "device_fold_components", None) or [])
+                if any(c is not None for c in self._device_folds):
+                    if graph_edges is None and getattr(custom, "graph_edge_rows", None):      # a loaded object's sidecar: rows of one world
+                        graph_edges = {c: (self.entity_ids[np.asarray(a_, dtype=np.int64)], self.entity_ids[np.asarray(b_, dtype=np.int64)])
+                                       for c, (a_, b_) in custom.graph_edge_rows.items()}
+                    missing = sorted({c for c in self._device_folds if c is not None} - set(graph_edges or {}))
+                    if missing:
+                        raise ValueError(f"graph_edges lacks the edges of {missing}: every fold of a program with device fold tables needs a table")
+                    self.set_graph_edges({c: (graph_edges or {})[c] for c in self._device_folds if c is not None})
             if pair_so is not None:
                 rc = lib.sixdof_set_custom_pair(self._h, str(pair_so).encode())
                 if rc != L.OK:
@@ -304,6 +324,28 @@ class HipExec:
             _raise(self._h, rc, "sixdof_step")
         return TickTimings(t.h2d_upload_ms, t.kernel_invoke_ms, t.d2h_download_ms, t.kernel_device_ms,
                            int(t.launches), int(t.ticks), t.kernel_sum_ms, int(t.graph_launches))
+
+    def set_graph_edges(self, graph_edges) -> None:
+        """Replace the edges of stand-alone folds between batches: {edge_component: (from_ids, to_ids)}, entity ids of this
+        executor (of replica 0 under graph_replicas), any size and source set.  Only for a program built with device fold
+        tables (graph_tables="device", or "auto" beyond 65,536 edges): a baked program's graph is part of its code."""
+        if not any(c is not None for c in self._device_folds):
+            raise ValueError("set_graph_edges: this executor's program bakes its folds' edges into the generated code; "
+                             "build it with graph_tables=\"device\" to replace them")
+        unknown = sorted(set(graph_edges) - {c for c in self._device_folds if c is not None})
+        if unknown:
+            raise KeyError(f"set_graph_edges: no fold of this program with device tables reads {unknown}")
+        u64p = C.POINTER(C.c_uint64)
+        for k, comp in enumerate(self._device_folds):
+            if comp is None or comp not in graph_edges:
+                continue
+            frm = np.ascontiguousarray(graph_edges[comp][0], dtype=np.uint64)
+            to = np.ascontiguousarray(graph_edges[comp][1], dtype=np.uint64)
+            if frm.shape != to.shape or frm.ndim != 1:
+                raise ValueError(f"graph_edges[{comp!r}]: from / to must be two id vectors of one length")
+            rc = self._lib.sixdof_set_fold_edges(self._h, k, frm.ctypes.data_as(u64p), to.ctypes.data_as(u64p), len(frm))
+            if rc != L.OK:
+                _raise(self._h, rc, "sixdof_set_fold_edges")
 
     def prepare(self, n_ticks: int):
         """Capture the replay graphs a later invoke_batch(n_ticks) uses (use_graph=True), outside any timed region."""

@@ -3031,9 +3031,14 @@ def float32_hazards(funcs: Dict[str, Func]) -> List[str]:
 
 
 def compile_world(text: str, slots_doc: dict, out: Optional[str] = None, mode: str = "auto", dtype: str = "float64", fast_math: bool = False,
-                  wave_folds: bool = True, arith: str = "reference", one_world: bool = False):
+                  wave_folds: bool = True, arith: str = "reference", one_world: bool = False, fold_tables: str = "auto"):
     """The build-time step a host (`WorldExec::Hip`, INTEGRATION.md §3) runs once per world: module text + slot metadata -> the
-    shared object `sixdof_set_custom_pipe` installs, and the manifest of its columns.  -> (path of the .so, manifest)"""
+    shared object `sixdof_set_custom_pipe` installs, and the manifest of its columns.  -> (path of the .so, manifest)
+    fold_tables (fold stages only): "baked" — the scans' edges are written into the object; "device" — the object reads them from
+    device memory, the edges go to the sidecar `<out>.edges` (manifest "edge_sidecar") and the host installs them with
+    sixdof_set_fold_edges: one object for every graph of the same tick; "auto" — baked up to 65,536 edges per scan, device beyond."""
+    if fold_tables not in ("auto", "baked", "device"):
+        raise ValueError('fold_tables must be "auto", "baked" or "device"')
     import json
     import shutil
     import time
@@ -3066,7 +3071,9 @@ def compile_world(text: str, slots_doc: dict, out: Optional[str] = None, mode: s
         if rows % n_world:
             raise ValueError(f"{rows} rows are not a whole number of {n_world}-entity worlds")
         widths = {c["column"]: c["width"] for c in manifest["columns"]}
-        tp = prog.trace(widths, fold_edges=edges, fold_replicas=(rows // n_world, n_world) if rows > n_world else None)
+        if fold_tables == "auto":
+            fold_tables = "device" if any(not isinstance(e_[0], str) and len(e_[0]) > 65536 for e_ in edges.values()) else "baked"
+        tp = prog.trace(widths, fold_edges=edges, fold_replicas=(rows // n_world, n_world) if rows > n_world else None, fold_tables=fold_tables)
         t1 = time.perf_counter()
         so = codegen.build(tp, dtype, 2, fast_math=False)
         t2 = time.perf_counter()
@@ -3077,8 +3084,25 @@ def compile_world(text: str, slots_doc: dict, out: Optional[str] = None, mode: s
         manifest["columns"] = sorted(manifest["columns"], key=lambda c: order.index(c["column"]))
         manifest.update({"integrator": "none", "dtype": dtype, "column_layout": "rows", "row_count": rows,      # the fold kernels are generated for this many rows
                          "build": {"trace_ms": round((t1 - t0) * 1e3, 1), "compile_ms": round((t2 - t1) * 1e3, 1), "resources": dict(codegen.last_resources)}})
+        manifest["fold_tables"] = fold_tables
+        sidecar = b""
+        if fold_tables == "device":
+            # the edges travel next to the object: per fold stage that reads a table, its (source row, target row) pairs of one world
+            # in spawn order, little-endian uint32 — what a host resolves to entity ids and hands to sixdof_set_fold_edges
+            entries = []
+            for k, comp in enumerate(tp.device_fold_components):
+                if comp is None:
+                    continue
+                pairs = np.stack([np.asarray(edges[comp][0], dtype="<u4"), np.asarray(edges[comp][1], dtype="<u4")], axis=1)
+                entries.append({"fold": k, "edge_component": comp, "n_edges": int(pairs.shape[0]), "offset_bytes": len(sidecar)})
+                sidecar += pairs.tobytes()
+            manifest["edge_sidecar"] = {"file": Path(str(out)).name + ".edges" if out else None,
+                                        "layout": "per fold: n_edges x (source row, target row) of one world, little-endian uint32, spawn order, at offset_bytes",
+                                        "folds": entries}
         if out:
             shutil.copyfile(so, out)
+            if fold_tables == "device":
+                Path(str(out) + ".edges").write_bytes(sidecar)
             Path(str(out) + ".json").write_text(json.dumps(manifest, indent=1))
             so = Path(out)
         return so, manifest
@@ -3113,6 +3137,20 @@ def load_world(so_path: str):
                               column_soa=manifest.get("column_layout") == "element-major", prebuilt_so=str(so_path))
     prog._traced.rows_multiple = int(manifest.get("rows_per_world", 1))      # exec.HipExec refuses a row count that splits a world
     prog._traced.exact_rows = int(manifest.get("row_count", 0))              # ... and, for an object with fold stages, any count but the one it was generated for
+    # an object that reads its folds' edges from device memory: the sidecar's row pairs, per edge component (`prog.graph_edges`, rows
+    # of one world) — the executor installs them (sixdof_set_fold_edges) unless it is given others (HipExec(graph_edges=...))
+    prog.graph_edges = {}
+    if manifest.get("fold_tables") == "device":
+        side = manifest["edge_sidecar"]
+        raw = (Path(so_path).parent / side["file"]).read_bytes() if side.get("file") else b""
+        n_folds = int(manifest.get("fold_stages", 0)) or (max([f["fold"] for f in side["folds"]], default=-1) + 1)
+        comps = [None] * n_folds
+        for f in side["folds"]:
+            pairs = np.frombuffer(raw, dtype="<u4", count=2 * f["n_edges"], offset=f["offset_bytes"]).reshape(-1, 2)
+            prog.graph_edges[f["edge_component"]] = (pairs[:, 0].copy(), pairs[:, 1].copy())
+            comps[f["fold"]] = f["edge_component"]
+        prog._traced.device_fold_components = comps
+        prog._traced.graph_edge_rows = prog.graph_edges
     return prog, manifest
 
 
@@ -3215,6 +3253,9 @@ def _main(argv=None) -> int:
                     help="relaxed: finite values assumed (0 * x = 0), one division per denominator, a * b + c contracted — inside 1e-9 of the "
                          "reference instead of its last bits, about half the instructions (world_system)")
     ap.add_argument("--one-world", action="store_true", help="lane mode: the executor's rows are ONE world, its Globals are read once per wavefront")
+    ap.add_argument("--fold-tables", default="auto", choices=("auto", "baked", "device"),
+                    help="fold stages: edges baked into the object, or read from device memory (sidecar <out>.edges, installed with "
+                         "sixdof_set_fold_edges; one object for every graph); auto: baked up to 65,536 edges per scan")
     a = ap.parse_args(argv)
     if a.checkpoint:
         rep = checkpoint(a.checkpoint, a.mode)
@@ -3223,9 +3264,9 @@ def _main(argv=None) -> int:
     if not (a.module and a.slots and a.out):
         ap.error("module, --slots and -o are required (or --checkpoint DIR)")
     so, manifest = compile_world(Path(a.module).read_text(), json.loads(Path(a.slots).read_text()), a.out, a.mode, a.dtype, a.fast_math,
-                                 wave_folds=not a.sequential_folds, arith=a.arith, one_world=a.one_world)
+                                 wave_folds=not a.sequential_folds, arith=a.arith, one_world=a.one_world, fold_tables=a.fold_tables)
     print(json.dumps({"object": str(so), "mode": manifest["mode"], "rows": manifest["rows"], "columns": [c["column"] for c in manifest["columns"]],
-                      "build": manifest["build"], **({k: manifest[k] for k in ("arith", "one_world") if k in manifest}), **({"lane_refused": manifest["lane_refused"]} if "lane_refused" in manifest else {})}))
+                      "build": manifest["build"], **({k: manifest[k] for k in ("arith", "one_world", "fold_tables") if k in manifest}), **({"lane_refused": manifest["lane_refused"]} if "lane_refused" in manifest else {})}))
     return 0
 
 

@@ -350,6 +350,26 @@ int sixdof_set_custom_pipe(sixdof_handle* h, const char* so_path, const uint64_t
  * (csrc/pair_kernel.hpp) with that function.  Appends the fold as the LAST op of the pipe set by
  * sixdof_set_effectors (per-entity built-in ops before it are kept); edges come from sixdof_set_edges. */
 int sixdof_set_custom_pair(sixdof_handle* h, const char* so_path);
+/* The edges of fold stage `fold_index` (order of the stages in the program) of a generated program whose fold kernels read
+ * their edges from device memory (codegen: fold_tables="device"; such an object exports sixdof_custom_fold_count /
+ * sixdof_custom_fold_info / sixdof_custom_set_fold_table, an object without them has its edges baked in).  Ids are resolved
+ * to rows like sixdof_set_edges does; for a program generated for replicas (count x stride rows) they name entities of
+ * replica 0.  The library builds the CSR by source in spawn order (sixdof_build_fold_table), splits the sources of a fold that
+ * may be regrouped at out-degree 64 (one wave per long source, one lane per other source), checks every row, uploads on the
+ * handle's stream and hands the table to the object.  May be called again between batches with any other edge list: the old
+ * table is released once the stream has drained, and captured replays are dropped.  Rows that stop being sources keep their
+ * last `out` value.  Until every such fold stage has a table sixdof_step returns SIXDOF_ERR_UNSUPPORTED.  Errors (nothing is
+ * installed then): no generated program / a baked object -> SIXDOF_ERR_UNSUPPORTED; fold_index out of range, a fold over a
+ * complete graph, more than 2^32 - 1 edges, a row outside the handle (replica 0) -> SIXDOF_ERR_INVALID_ARGUMENT; an unknown
+ * entity id -> SIXDOF_ERR_COMPONENT_NOT_FOUND. */
+int sixdof_set_fold_edges(sixdof_handle* h, uint32_t fold_index, const uint64_t* from_ids, const uint64_t* to_ids, size_t n_edges);
+/* Pure host (no device): the table sixdof_set_fold_edges uploads, from ROW pairs.  Sources ascending, each source's targets
+ * in the order given; with wave_min_degree > 0 the sources of out-degree below it come first (*n_lane of them), the others
+ * behind, ascending inside each range.  out_src and out_dst hold n_edges values, out_start n_edges + 1; the table uses
+ * *n_src, *n_src + 1 and n_edges of them.  A row >= row_limit or more than 2^32 - 1 edges: SIXDOF_ERR_INVALID_ARGUMENT. */
+int sixdof_build_fold_table(const uint32_t* src_rows, const uint32_t* dst_rows, size_t n_edges, uint32_t row_limit,
+                            uint32_t wave_min_degree, uint32_t* out_src, uint32_t* out_start, uint32_t* out_dst,
+                            uint32_t* n_src, uint32_t* n_lane);
 
 /* ---- telemetry: device-side history ring (the commit step either side of the path) ------------------------
  * The reference commits every output column to its DB after each batch (exec.rs:110-172,
