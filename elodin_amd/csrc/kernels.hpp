@@ -50,7 +50,10 @@ struct StepParams {
     void* hist_force;         // [ring][n,6]
     uint64_t tick0;           // tick count before this launch (generated systems may read the tick)
     uint32_t accel_in_check;  // 1: the world_accel column holds HOST data (first launch after an upload): RK4 stage 0 reads it
-    uint32_t reserved0;       //    the way the reference does, v_s = v0 + 0 * a_in (rk4.rs:96-100), so a non-finite row poisons the tick
+                              //    the way the reference does, v_s = v0 + 0 * a_in (rk4.rs:96-100), so a non-finite row poisons the tick
+    uint32_t state_only;      // 1: store world_pos / world_vel only.  For a launch of a batch that another launch follows inside the same
+                              //    sixdof_step call: nothing reads world_accel / force before that launch overwrites them.  Built-in pipes
+                              //    only, never with the history ring or accel_in_check (sixdof_capi.cpp state_only_eligible)
     DevOp ops[kMaxOps];
     // generated programs only — behind everything the hand-written kernels read, so their kernarg loads stay within the
     // first 400 bytes whatever kMaxModelCols is

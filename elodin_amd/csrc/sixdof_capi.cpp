@@ -89,30 +89,32 @@ double now_ms() {
 uint64_t cid(const char* s) { return sixdof_component_id(s); }
 
 constexpr uint32_t kAqlSlots = 8;   // argument blocks of AQL chains per handle (Replay::aql_args)
+constexpr uint32_t kAqlSpare0 = 3;  // slots 0 .. 2: the K-tick launches (plain, accel check, state-only); the rest are spares
 
 // What the step kernel's batches replay: captured hipGraphs, and the queue and argument blocks of AQL chains (aql_chain.hpp).
 // Both are built from `key` and dropped together.
 struct Replay {
     // Everything a replayed launch bakes in: the batch's StepParams (column pointers, n, both time steps, effector ops, cache
-    // policy) with n_ticks = K and tick0 = hist_slot0 = 0 (read only off the graph-eligible paths).  Integrator and dtype are
-    // fixed per handle.
+    // policy) with n_ticks = K and tick0 = hist_slot0 = 0 (read only off the graph-eligible paths); state_only stays 0 like
+    // accel_in_check: both are set per launch.  Integrator and dtype are fixed per handle.
     StepParams key{};
-    std::map<uint32_t, hipGraphExec_t> graphs;   // replay graphs by chain length (launches per replay)
+    std::map<uint32_t, hipGraphExec_t> graphs;   // replay graphs by graph_key(chain length, variant)
+    bool state_only_off = false;            // SIXDOF_STATE_ONLY=0 when the handle was created: every launch stores all four columns
     bool aql_off = false;                   // SIXDOF_AQL=0 when the handle was created: keep the hipGraph path
     aql::Device* aql_dev = nullptr;
     std::string aql_why;                    // why AQL setup failed (the hipGraph path then stays); not retried
     std::string aql_fault;                  // a chain failed on the queue: every later step fails with this
     void* aql_args = nullptr;               // device arena of argument blocks (kAqlSlots)
-    std::map<uint64_t, aql::Run> aql_runs;  // by (accel_in_check, n_ticks): kernel, argument block, grid
-    uint64_t aql_slot_key[kAqlSlots] = {};  // the run whose block each spare slot (2 ..) holds, 0: none
-    uint32_t aql_next_spare = 2;            // the spare slot the next new run takes
+    std::map<uint64_t, aql::Run> aql_runs;  // by (state_only, accel_in_check, n_ticks): kernel, argument block, grid
+    uint64_t aql_slot_key[kAqlSlots] = {};  // the run whose block each spare slot (kAqlSpare0 ..) holds, 0: none
+    uint32_t aql_next_spare = kAqlSpare0;   // the spare slot the next new run takes
 
     void drop() {
         for (auto& kv : graphs) hipGraphExecDestroy(kv.second);
         graphs.clear();
         aql_runs.clear();
         std::fill(std::begin(aql_slot_key), std::end(aql_slot_key), 0);
-        aql_next_spare = 2;
+        aql_next_spare = kAqlSpare0;
     }
     // `P`: a batch's parameters (n_ticks = K).  Whatever was built from other parameters is dropped.
     void rekey(StepParams P) {
@@ -329,6 +331,8 @@ int sixdof_create(const sixdof_desc* d, sixdof_handle** out) try {
     if (h->desc.ticks_per_launch == 0) h->desc.ticks_per_launch = 1;
     const char* aql_env = std::getenv("SIXDOF_AQL");   // "0": hipGraph replay instead of AQL chains (A/B runs)
     h->replay.aql_off = aql_env && aql_env[0] == '0';
+    const char* so_env = std::getenv("SIXDOF_STATE_ONLY");   // "0": every launch stores world_accel and force (A/B runs, tests)
+    h->replay.state_only_off = so_env && so_env[0] == '0';
     h->device = d->device_ordinal;
     h->id_pos = cid("world_pos");
     h->id_vel = cid("world_vel");
@@ -1432,26 +1436,46 @@ static bool opens_with_check(const sixdof_handle* h, uint64_t n_ticks) {
     return h->accel_is_host_data && h->desc.integrator == SIXDOF_INTEGRATOR_RK4 && n_ticks > 0;
 }
 
+// Whether the handle's launches may leave world_accel and force unwritten (StepParams::state_only): a built-in pipe without
+// a history ring.  Inside one sixdof_step call nothing reads the two columns between launches — the host cannot look
+// before the call returns, RK4 reads world_accel in the accel-check launch only — so every launch of a batch but the last
+// overwrites them unread.  Launch i of a batch of L carries the flag iff i < L - 1 and it is not the accel-check launch:
+// the LAST launch of every call stores all four columns, and after any call they hold what they always held.
+static bool state_only_eligible(const sixdof_handle* h) {
+    return !h->replay.state_only_off && !h->custom_launch && !h->hist_ring && h->model == 0 && !h->has_pair_op();
+}
+
 constexpr size_t kGraphCacheMax = 8;
 
-// An executable graph of `len` identical launches of the step kernel, cached per chain length (Replay::key holds for all).
-int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t len, hipGraphExec_t* out) {
+// A chain's launches: kAll = every launch stores all four columns (handles that never use the flag), kStateOnly = every
+// launch carries StepParams::state_only (more of the batch follows), kClosing = state-only launches and a last one that
+// stores everything (the chain ends the batch).
+enum class Chain : uint32_t { kAll = 0, kStateOnly = 1, kClosing = 2 };
+static uint32_t graph_key(uint32_t len, Chain v) { return len << 2 | static_cast<uint32_t>(v); }
+
+// An executable graph of `len` launches of the step kernel, cached per chain length and variant (Replay::key holds for all).
+int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t len, Chain variant, hipGraphExec_t* out) {
     std::map<uint32_t, hipGraphExec_t>& graphs = h->replay.graphs;
-    if (auto it = graphs.find(len); it != graphs.end()) {
+    if (auto it = graphs.find(graph_key(len, variant)); it != graphs.end()) {
         *out = it->second;
         return SIXDOF_OK;
     }
-    if (graphs.size() >= kGraphCacheMax) {   // many distinct batch lengths: keep the 32- and 128-launch chains, drop the rest
+    if (graphs.size() >= kGraphCacheMax) {   // many distinct batch lengths: keep the 32- and 128-launch chains (every variant), drop the rest
         for (auto g = graphs.begin(); g != graphs.end();) {
-            if (g->first == kGraphLen || g->first == kGraphLong) { ++g; continue; }
+            if (g->first >> 2 == kGraphLen || g->first >> 2 == kGraphLong) { ++g; continue; }
             hipGraphExecDestroy(g->second);
             g = graphs.erase(g);
         }
     }
+    StepParams Q = P;
+    Q.state_only = variant == Chain::kAll ? 0u : 1u;
     hipGraph_t g = nullptr;
     HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     hipError_t le = hipSuccess;
-    for (uint32_t i = 0; i < len && le == hipSuccess; i++) le = launch_any(h, P);
+    for (uint32_t i = 0; i < len && le == hipSuccess; i++) {
+        if (i + 1 == len && variant == Chain::kClosing) Q.state_only = 0;
+        le = launch_any(h, Q);
+    }
     hipError_t ce = hipStreamEndCapture(h->stream, &g);
     if (le != hipSuccess) return h->hip_fail(le, "launch_step (capture)");
     if (ce != hipSuccess) return h->hip_fail(ce, "hipStreamEndCapture");
@@ -1460,19 +1484,43 @@ int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t len, hipGraphEx
     hipGraphDestroy(g);
     if (ie != hipSuccess) return h->hip_fail(ie, "hipGraphInstantiate");
     (void)hipGraphUpload(exec, h->stream);   // move the one-off device-side setup out of the first replay
-    graphs[len] = exec;
+    graphs[graph_key(len, variant)] = exec;
     *out = exec;
     return SIXDOF_OK;
 }
 
-// The graphs a plan replays, from the cache or captured now: g[0] the 32-launch chain, g[1] the 128-launch one, g[2] the
-// tail.  The tail comes last, so a cache eviction it triggers (which keeps the 32- and 128-launch chains) drops none of them.
-static int ensure_plan_graphs(sixdof_handle* h, const StepParams& P, const ChainPlan& c, hipGraphExec_t g[3]) {
-    int rc = SIXDOF_OK;
-    if (c.open || c.n_short) rc = ensure_graph(h, P, kGraphLen, &g[0]);
-    if (rc == SIXDOF_OK && c.n_long) rc = ensure_graph(h, P, kGraphLong, &g[1]);
-    if (rc == SIXDOF_OK && c.tail) rc = ensure_graph(h, P, c.tail, &g[2]);
-    return rc;
+// One step of a plan's replay sequence: `times` replays of the `len`-launch chain `variant`.
+struct ChainReplay {
+    uint32_t len = 0;
+    Chain variant = Chain::kAll;
+    uint64_t times = 0;
+    hipGraphExec_t graph = nullptr;
+};
+
+// The replays of batch plan `b`, in order, their graphs from the cache or captured now.  A chain that closes the batch
+// (no eager launch, no remainder and no further replay after it) is the kClosing variant; on a handle that uses the flag
+// every other chain is state-only throughout.  The one chain that is neither 32 nor 128 launches long (the tail) is
+// looked up last, so a cache eviction it triggers (which keeps the 32- and 128-launch chains) drops none of the others.
+static int ensure_plan_graphs(sixdof_handle* h, const StepParams& P, const BatchPlan& b, ChainReplay r[5]) {
+    const ChainPlan& c = b.chains;
+    const Chain v = state_only_eligible(h) ? Chain::kStateOnly : Chain::kAll;
+    r[0] = {kGraphLen, v, c.open ? 1u : 0u};
+    r[1] = {kGraphLong, v, c.n_long};
+    r[2] = {kGraphLen, v, c.n_short};
+    r[3] = {c.tail, v, c.tail ? 1u : 0u};
+    r[4] = {};
+    if (v == Chain::kStateOnly && c.launches() && c.launches() == b.full && !b.rem) {
+        int last = 3;
+        while (!r[last].times) last--;
+        r[last].times--;
+        r[4] = {r[last].len, Chain::kClosing, 1};
+    }
+    for (bool tail : {false, true})
+        for (int i = 0; i < 5; i++) {
+            if (!r[i].times || (r[i].len != kGraphLen && r[i].len != kGraphLong) != tail) continue;
+            if (int rc = ensure_graph(h, P, r[i].len, r[i].variant, &r[i].graph); rc != SIXDOF_OK) return rc;
+        }
+    return SIXDOF_OK;
 }
 
 // ---- AQL chains ------------------------------------------------------------------------------------------------
@@ -1482,24 +1530,26 @@ static int ensure_plan_graphs(sixdof_handle* h, const StepParams& P, const Chain
 constexpr size_t kAqlSlotBytes = (sizeof(StepParams) + 255) / 256 * 256;
 constexpr double kAqlStallS = 60.0;     // no packet of a chain started or finished for this long: the queue is stuck
 
-// The packet run of one launch of `P` with `check` / `ticks` (its kernel and argument block, count 0), built on first use.
-// The argument blocks of the K-tick launches keep slots 0 (plain) and 1 (accel check) for as long as the parameters hold.
-// Any other block (a remainder, or a batch shorter than K) takes the next spare slot, evicting whichever block was there:
-// a batch holds at most one such block (aql_batch), so no block a batch is about to run can be overwritten by its own
-// later lookups, and nothing is in flight between two batches.
-static bool aql_run(sixdof_handle* h, const StepParams& P, uint32_t check, uint32_t ticks, aql::Run* out) {
+// The packet run of one launch of `P` with `check` / `state_only` / `ticks` (its kernel and argument block, count 0), built
+// on first use.  The argument blocks of the K-tick launches keep slots 0 (plain), 1 (accel check) and 2 (state-only) for
+// as long as the parameters hold.  Any other block (a remainder, or a batch shorter than K: both close their batch, so
+// neither is ever state-only) takes the next spare slot, evicting whichever block was there: a batch holds at most one
+// such block (aql_batch), so no block a batch is about to run can be overwritten by its own later lookups, and nothing is
+// in flight between two batches.
+static bool aql_run(sixdof_handle* h, const StepParams& P, uint32_t check, uint32_t state_only, uint32_t ticks, aql::Run* out) {
     Replay& rp = h->replay;
-    const uint64_t key = uint64_t(check) << 32 | ticks;
+    const uint64_t key = uint64_t(state_only) << 33 | uint64_t(check) << 32 | ticks;
     if (auto it = rp.aql_runs.find(key); it != rp.aql_runs.end()) return *out = it->second, true;
-    uint32_t slot_index = check;
+    uint32_t slot_index = state_only ? 2 : check;
     if (ticks != h->desc.ticks_per_launch) {
         slot_index = rp.aql_next_spare;
-        rp.aql_next_spare = slot_index + 1 == kAqlSlots ? 2 : slot_index + 1;
+        rp.aql_next_spare = slot_index + 1 == kAqlSlots ? kAqlSpare0 : slot_index + 1;
         rp.aql_runs.erase(rp.aql_slot_key[slot_index]);
         rp.aql_slot_key[slot_index] = 0;
     }
     StepParams Q = P;
     Q.accel_in_check = check;
+    Q.state_only = state_only;
     Q.n_ticks = ticks;
     Q.tick0 = Q.hist_slot0 = 0;   // read only by generated and history-ring pipes, which never take this path
     const StepKernel k = select_step(Q, h->desc.integrator, h->desc.dtype);
@@ -1513,21 +1563,27 @@ static bool aql_run(sixdof_handle* h, const StepParams& P, uint32_t check, uint3
     r.kernarg = slot;
     r.blocks = k.grid.x;
     rp.aql_runs[key] = r;
-    if (slot_index >= 2) rp.aql_slot_key[slot_index] = key;
+    if (slot_index >= kAqlSpare0) rp.aql_slot_key[slot_index] = key;
     return *out = r, true;
 }
 
-// The runs of a batch planned by `b`: the accel-check launch, the K-tick launches (what the plan replays and the eager
-// ones it leaves are the same packets: one run), the remainder.  Apart from the two K-tick blocks, the runs hold at most one
-// block: a remainder needs n_ticks >= K, and then the check launch runs K ticks.
-static bool aql_batch(sixdof_handle* h, const StepParams& P, const BatchPlan& b, aql::Run runs[3]) {
+constexpr size_t kAqlRuns = 4;
+
+// The runs of a batch planned by `b`: the accel-check launch, the state-only K-tick launches, the K-tick launches that
+// store everything (one, and only when no remainder follows it, on a handle that uses the flag; else all of them), the
+// remainder.  What the plan replays and the eager launches it leaves are the same packets.  Apart from the three K-tick
+// blocks, the runs hold at most one block: a remainder needs n_ticks >= K, and then the check launch runs K ticks.
+static bool aql_batch(sixdof_handle* h, const StepParams& P, const BatchPlan& b, aql::Run runs[kAqlRuns]) {
     const uint32_t K = h->desc.ticks_per_launch;
-    if ((b.check_ticks && !aql_run(h, P, 1, b.check_ticks, &runs[0])) || (b.full && !aql_run(h, P, 0, K, &runs[1])) ||
-        (b.rem && !aql_run(h, P, 0, b.rem, &runs[2])))
+    const uint64_t closing = state_only_eligible(h) ? (b.full && !b.rem ? 1 : 0) : b.full;
+    const uint64_t state_only = b.full - closing;
+    if ((b.check_ticks && !aql_run(h, P, 1, 0, b.check_ticks, &runs[0])) || (state_only && !aql_run(h, P, 0, 1, K, &runs[1])) ||
+        (closing && !aql_run(h, P, 0, 0, K, &runs[2])) || (b.rem && !aql_run(h, P, 0, 0, b.rem, &runs[3])))
         return false;
     runs[0].count = b.check_ticks ? 1 : 0;
-    runs[1].count = b.full;
-    runs[2].count = b.rem ? 1 : 0;
+    runs[1].count = state_only;
+    runs[2].count = closing;
+    runs[3].count = b.rem ? 1 : 0;
     return true;
 }
 
@@ -1544,7 +1600,7 @@ struct Route {
 // the step kernel, *P gets the batch's parameters (n_ticks = K) and the replay caches are keyed to them.  kAql has built
 // the batch's packet runs into runs[]; when they cannot be built, aql_why says why, and this batch, like every later one,
 // takes kRigid.  A handle whose chain faulted stays on kAql, where the step reports the fault.
-static Route choose_path(sixdof_handle* h, uint64_t n_ticks, StepParams* P, aql::Run runs[3]) {
+static Route choose_path(sixdof_handle* h, uint64_t n_ticks, StepParams* P, aql::Run runs[kAqlRuns]) {
     if (h->model == 1) return {Path::kApollo};
     if (h->has_pair_op()) return {Path::kPair};
     Replay& rp = h->replay;
@@ -1577,28 +1633,28 @@ static Route choose_path(sixdof_handle* h, uint64_t n_ticks, StepParams* P, aql:
 // cannot know (a warm-up batch may come first), so both shapes are built.
 static int prepare_batch(sixdof_handle* h, const Route& r, const StepParams& P, uint64_t n_ticks) {
     if (r.path == Path::kAql && !h->replay.aql_fault.empty()) return SIXDOF_OK;   // the step reports the fault
-    aql::Run runs[3];
-    hipGraphExec_t unused[3] = {};
+    aql::Run runs[kAqlRuns];
+    ChainReplay unused[5];
     for (bool check : {false, opens_with_check(h, n_ticks)}) {
         const BatchPlan b = plan_batch(n_ticks, h->desc.ticks_per_launch, check, true);
         if (r.path == Path::kAql) (void)aql_batch(h, P, b, runs);   // on failure the step takes the hipGraph path
-        else if (int rc = ensure_plan_graphs(h, P, b.chains, unused); rc != SIXDOF_OK) return rc;
+        else if (int rc = ensure_plan_graphs(h, P, b, unused); rc != SIXDOF_OK) return rc;
     }
     if (r.path != Path::kAql) HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SIXDOF_OK;
 }
 
 // Builds what a first long batch replays (called when the columns become resident and when the batch shape changes): the
-// blocks of a K-tick launch, or the 32-launch chain.
+// blocks of the K-tick launches (a two-launch batch has all three), or the 32-launch chain that more of the batch follows.
 int prepare_graph(sixdof_handle* h) {
     if (!h->bound || !graph_eligible(h)) return SIXDOF_OK;
     StepParams P;
-    aql::Run runs[3];
+    aql::Run runs[kAqlRuns];
     const Route r = choose_path(h, h->desc.ticks_per_launch, &P, runs);
     if (r.rc != SIXDOF_OK) return SIXDOF_OK;     // not steppable yet (columns missing): the step call will report it
-    if (r.path == Path::kAql) return prepare_batch(h, r, P, h->desc.ticks_per_launch);
+    if (r.path == Path::kAql) return prepare_batch(h, r, P, 2 * uint64_t(h->desc.ticks_per_launch));
     hipGraphExec_t unused = nullptr;
-    int rc = ensure_graph(h, P, kGraphLen, &unused);
+    int rc = ensure_graph(h, P, kGraphLen, state_only_eligible(h) ? Chain::kStateOnly : Chain::kAll, &unused);
     if (rc == SIXDOF_OK) (void)hipStreamSynchronize(h->stream);
     return rc;
 }
@@ -1609,7 +1665,7 @@ int sixdof_prepare_step(sixdof_handle* h, uint64_t n_ticks) try {
     if (!graph_eligible(h)) return SIXDOF_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     StepParams P;
-    aql::Run runs[3];
+    aql::Run runs[kAqlRuns];
     const Route r = choose_path(h, n_ticks, &P, runs);
     return r.rc != SIXDOF_OK ? r.rc : prepare_batch(h, r, P, n_ticks);
 } SIXDOF_ABI_CATCH(err_of(h))
@@ -1618,7 +1674,7 @@ const char* sixdof_step_path(sixdof_handle* h) try {
     if (!h) return "invalid handle";
     (void)hipSetDevice(h->device);
     StepParams P;
-    aql::Run runs[3];
+    aql::Run runs[kAqlRuns];
     const Route r = choose_path(h, h->desc.ticks_per_launch, &P, runs);   // as for a batch of one launch
     if (r.path == Path::kApollo) h->path = "apollo";
     else if (r.path == Path::kPair) h->path = "pair";
@@ -1682,9 +1738,12 @@ static int step_rigid(sixdof_handle* h, const StepParams& P, const BatchPlan& b,
             h->launch_events.push_back(e);
         }
     }
-    // one eager launch of `ticks` ticks; every launch before it ran K ticks
+    // one eager launch of `ticks` ticks; every launch before it ran K ticks.  State-only unless it is the accel-check launch
+    // or closes the batch (state_only_eligible).
+    const bool may_skip = state_only_eligible(h);
     auto eager = [&](StepParams Q, uint32_t ticks) -> int {
         Q.n_ticks = ticks;
+        Q.state_only = may_skip && !Q.accel_in_check && *launches + 1 < b.launches();
         Q.tick0 = Q.hist_slot0 = h->tick + *launches * K;
         if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * *launches], h->stream));
         hipError_t e = launch_any(h, Q);
@@ -1704,13 +1763,12 @@ static int step_rigid(sixdof_handle* h, const StepParams& P, const BatchPlan& b,
         if (int rc = eager(P1, b.check_ticks); rc != SIXDOF_OK) return rc;
     }
     if (const ChainPlan& c = b.chains; c.launches()) {
-        hipGraphExec_t g[3] = {};
-        if (int rc = ensure_plan_graphs(h, P, c, g); rc != SIXDOF_OK) return rc;
+        ChainReplay replays[5];
+        if (int rc = ensure_plan_graphs(h, P, b, replays); rc != SIXDOF_OK) return rc;
         // a capture may just have happened after ev0 was recorded: re-record so the pair brackets real work only
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-        const std::pair<hipGraphExec_t, uint64_t> replays[4] = {{g[0], c.open ? 1 : 0}, {g[1], c.n_long}, {g[0], c.n_short}, {g[2], c.tail ? 1 : 0}};
-        for (const auto& [graph, times] : replays)
-            for (uint64_t i = 0; i < times; i++) HIP_TRY(h, hipGraphLaunch(graph, h->stream));
+        for (const ChainReplay& r : replays)
+            for (uint64_t i = 0; i < r.times; i++) HIP_TRY(h, hipGraphLaunch(r.graph, h->stream));
         *launches += c.launches();
     }
     h->last.graph_launches = b.chains.launches();
@@ -1720,7 +1778,7 @@ static int step_rigid(sixdof_handle* h, const StepParams& P, const BatchPlan& b,
 }
 
 // The batch's packet runs as one AQL chain: step_rigid's launches, counted the same way, then a spin on the last packet.
-static int step_aql(sixdof_handle* h, const BatchPlan& b, const aql::Run runs[3], uint64_t n_ticks, uint64_t* launches) {
+static int step_aql(sixdof_handle* h, const BatchPlan& b, const aql::Run runs[kAqlRuns], uint64_t n_ticks, uint64_t* launches) {
     Replay& rp = h->replay;
     if (!rp.aql_fault.empty()) return h->fail(SIXDOF_ERR_BACKEND, rp.aql_fault);
     // the chain bypasses the HIP stream: let what was enqueued there (and on the null stream it waits for) finish first
@@ -1730,7 +1788,7 @@ static int step_aql(sixdof_handle* h, const BatchPlan& b, const aql::Run runs[3]
         else if (q != hipSuccess) return h->hip_fail(q, "hipStreamQuery");
     }
     double device_ms = 0.0;
-    if (!aql::run_chain(rp.aql_dev, runs, 3, kAqlStallS, &device_ms, &rp.aql_fault))
+    if (!aql::run_chain(rp.aql_dev, runs, kAqlRuns, kAqlStallS, &device_ms, &rp.aql_fault))
         return h->fail(SIXDOF_ERR_BACKEND, rp.aql_fault);
     if (n_ticks > 0) h->accel_is_host_data = false;
     *launches = b.launches();
@@ -1771,7 +1829,7 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
         return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: SIXDOF_INTEGRATOR_NONE runs generated system programs only (sixdof_set_custom_pipe)");
     uint64_t launches = 0;
     StepParams P;
-    aql::Run runs[3];
+    aql::Run runs[kAqlRuns];
     const Route r = choose_path(h, n_ticks, &P, runs);
     if (r.rc != SIXDOF_OK) return r.rc;
     // an AQL chain waits for itself and times itself from its packets: no event pair on the HIP stream

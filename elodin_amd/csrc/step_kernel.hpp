@@ -23,6 +23,9 @@
 // Roofline: HBM-bound at n_ticks == 1 (f64: read pos 56 + vel 48 + inertia 56 [+24 per [n,3]
 // effector column], write pos 56 + vel 48 + accel 48 + force 48 = 360 B per entity-step);
 // with n_ticks > 1 the state stays in registers and the kernel is f64-VALU bound.
+// A launch that another launch of the same sixdof_step call follows (StepParams::state_only, built-in pipes) writes
+// pos 56 + vel 48 only: the next launch overwrites accel and force before anything reads them.  264 B per entity-step
+// instead of 360 (config 2, with its [n,3] torque column: 288 instead of 384); the closing launch of a call writes all four.
 //
 // RK4 quirks of the reference kept on purpose: stage positions advance with the
 // INITIAL velocity v0; stage offsets use the global dt, the final combination uses the
@@ -257,6 +260,10 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
     // Not with a generated program's post hook (it may still rewrite the pose) nor while recording.
     // (StepParams::streaming bit 8 turns it off: the A/B knob of tools/step_ab.py.)
     const bool early_ok = !PIPE::kHasModel && !record && !(P.streaming & 256u);
+    // StepParams::state_only (wave-uniform, built-in pipes): another launch of the same batch follows and overwrites
+    // world_accel and force before anything reads them, so this launch neither stages nor stores the two columns, and never
+    // forms the world-frame wrench.  world_pos / world_vel: same arithmetic in the same order, same bits.
+    const bool state_only = !PIPE::kHasModel && P.state_only != 0;
     const T dt_g = T(P.dt_g), dt = T(P.dt);
     Body<T> b;
     b.mass = mass;
@@ -350,15 +357,19 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
             F = zero_wrench<T>();
             PIPE::apply(P, aux, regs, b, F);
             if constexpr (early) {
-                stage6(l_force, world_wrench<PIPE>(b.q, F));
-                __syncthreads();
-                flush6(l_force, g_force, kLive);
+                if (!state_only) {
+                    stage6(l_force, world_wrench<PIPE>(b.q, F));
+                    __syncthreads();
+                    flush6(l_force, g_force, kLive);
+                }
             }
             A = calc_accel<PIPE>(b.q, F, inv_I, inv_m + taint, taint);
             if constexpr (early) {
-                stage6(l_c, A);
-                __syncthreads();
-                flush6(l_c, g_accel, kLive);
+                if (!state_only) {
+                    stage6(l_c, A);
+                    __syncthreads();
+                    flush6(l_c, g_accel, kLive);
+                }
             }
             sa = sa + A;
             // v' = v0 + (dt/6)(k1 + 2k2 + 2k3 + k4)
@@ -384,15 +395,19 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
             F = zero_wrench<T>();
             PIPE::apply(P, aux, regs, b, F);
             if constexpr (early) {
-                stage6(l_force, world_wrench<PIPE>(b.q, F));
-                __syncthreads();
-                flush6(l_force, g_force, kLive);
+                if (!state_only) {
+                    stage6(l_force, world_wrench<PIPE>(b.q, F));
+                    __syncthreads();
+                    flush6(l_force, g_force, kLive);
+                }
             }
             const Spatial<T> A = calc_accel<PIPE>(b.q, F, inv_I, inv_m + taint, taint);
             if constexpr (early) {
-                stage6(l_c, A);
-                __syncthreads();
-                flush6(l_c, g_accel, kLive);
+                if (!state_only) {
+                    stage6(l_c, A);
+                    __syncthreads();
+                    flush6(l_c, g_accel, kLive);
+                }
             }
             v0 = axpy(dt, A, v0);
             if constexpr (early) {
@@ -459,14 +474,17 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
         }
     }
     if (flushed || kDead) return;
-    if constexpr (INTEGRATOR != kNone) F_out = world_wrench<PIPE>(b.q, F);  // wrench of the last stage evaluated, world frame
     stage_pos(q0, p0);
     stage6(l_vel, v0);
-    stage6(l_c, A_out);
-    stage6(l_force, F_out);
+    if (!state_only) {
+        if constexpr (INTEGRATOR != kNone) F_out = world_wrench<PIPE>(b.q, F);  // wrench of the last stage evaluated, world frame
+        stage6(l_c, A_out);
+        stage6(l_force, F_out);
+    }
     __syncthreads();
     flush7(l_pos, g_pos, kLive);
     flush6(l_vel, g_vel, kLive);
+    if (state_only) return;
     flush6(l_c, g_accel, kLive);
     flush6(l_force, g_force, kLive);
 }

@@ -153,7 +153,12 @@ typedef struct sixdof_desc {
 #define SIXDOF_FLAG_USE_GRAPH 1u /* run sixdof_step batches of >= 4 launches as a pre-built chain: for a built-in pipe,
                                     dispatch packets written into the library's own HSA queue (SIXDOF_AQL=0 at creation:
                                     off; sixdof_step_path tells); otherwise captured hipGraphs (chains of 32 + one chain of
-                                    the remainder, cached per length) */
+                                    the remainder, cached per length).
+                                    On every path (eager launches too), a launch of a built-in pipe without a history ring
+                                    that another launch of the same sixdof_step call follows stores world_pos and world_vel
+                                    only: the last launch of every call stores world_accel and force as well, so after any
+                                    call the four columns hold what they always held (SIXDOF_STATE_ONLY=0 at creation:
+                                    every launch stores all four, for A/B runs) */
 #define SIXDOF_FLAG_TIME_EACH_LAUNCH 2u /* profiling: bracket every launch of sixdof_step with its own HIP
                                            event pair (<= 4096 launches per call; disables graph replay) */
 #define SIXDOF_FLAG_ASYNC_STEP 4u /* sixdof_step only enqueues and returns (no stream sync): pair it with
