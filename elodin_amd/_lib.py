@@ -24,6 +24,7 @@ PRIM_F64, PRIM_U64, PRIM_F32 = 0, 1, 2
 FLAG_USE_GRAPH = 1
 FLAG_TIME_EACH_LAUNCH = 2
 FLAG_ASYNC_STEP = 4
+WATCH_ASYNC = 1      # sixdof_watch_read flags
 
 EFF_CONST_WRENCH = 1
 EFF_UNIFORM_GRAVITY = 2
@@ -136,6 +137,8 @@ SYMBOLS = {
     "sixdof_set_history": (C.c_int, [_H, C.c_uint32]),
     "sixdof_history_read": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.c_void_p]),
     "sixdof_history_stream": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "sixdof_set_watch": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t]),
+    "sixdof_watch_read": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_set_model_apollo": (C.c_int, [_H, C.c_void_p]),
     "sixdof_download_column": (C.c_int, [_H, C.c_uint64]),
     "sixdof_upload_column": (C.c_int, [_H, C.c_uint64]),

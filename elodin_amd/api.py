@@ -777,6 +777,50 @@ class Exec:
             raise RuntimeError("history is not being recorded: build with elodin_amd.frontend.World (history=True)")
         return self._history.frame(components)
 
+    def enable_history(self, ring_ticks: int) -> None:
+        """Keep the last `ring_ticks` world ticks of every recorded column in the device ring history_series reads."""
+        self._hip.enable_history(int(ring_ticks) * getattr(self, "_substeps", 1))
+
+    def history_series(self, keys, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, np.ndarray]:
+        """The dict shape of history() — "time" plus one series per "entity.component" key — for world ticks first_tick,
+        first_tick + every, ... <= last_tick, read out of the device ring (enable_history) through a watch list: only the
+        named entities' rows cross the link.  Tick 0, the spawned state, is never in the ring.  Replaces the executor's
+        watch (HipExec.set_watch) when the keys differ from the previous call's."""
+        keys = [keys] if isinstance(keys, str) else list(keys)
+        by_name = {v: k for k, v in self._world._names.items()}
+        side = getattr(self, "_side", None)
+        hip_ids = {int(e) for e in self._hip.entity_ids}
+        pairs = []
+        for key in keys:
+            ent, _, comp = key.partition(".")
+            if side is not None and comp in side._world._components:
+                raise NotImplementedError(f"history_series: {key}: {comp} also lives on entities stepped by a side executor")
+            if comp in getattr(self, "_partial", {}):
+                raise NotImplementedError(f"history_series: {key}: {comp} lives on fewer entities than the executor's rows")
+            if comp in getattr(self._hip, "_windows", {}):
+                raise NotImplementedError(f"history_series: {key}: {comp} is a window component, the ring does not copy it per tick")
+            if ent not in by_name or int(by_name[ent]) not in hip_ids:
+                raise KeyError(key)
+            pairs.append((int(by_name[ent]), comp))
+        comps = list(dict.fromkeys(c for _, c in pairs))
+        ents = list(dict.fromkeys(e for e, _ in pairs))
+        cached = getattr(self, "_series_watch", None)      # (components, entities, the HipExec watch they became)
+        if cached is None or cached[:2] != (comps, ents) or cached[2] is not getattr(self._hip, "_watch", None):
+            self._hip.set_watch(comps, np.asarray(ents, dtype=np.uint64))
+            self._series_watch = (comps, ents, self._hip._watch)
+        s = getattr(self, "_substeps", 1)
+        first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
+        if every < 1:
+            raise ValueError("history_series: every must be at least 1")
+        last_sample = first_tick + (last_tick - first_tick) // every * every if last_tick >= first_tick else first_tick - 1
+        blocks = self._hip.history_series(first_tick * s, last_sample * s, every * s)
+        ticks = np.arange(first_tick, last_sample + 1, every, dtype=np.float64)
+        out = {"time": ticks * self._dt}
+        for key, (e, comp) in zip(keys, pairs):
+            series = np.array(blocks[comp][ents.index(e)], dtype=np.float64)
+            out[key] = series[:, 0] if series.shape[1] == 1 else series
+        return out
+
     def column_ids(self, name: str) -> np.ndarray:
         """Entity id of each row of column_array(name)."""
         n = len(self._main_column_array(name))

@@ -143,6 +143,21 @@ hipError_t launch_gather_rows(void* dst, const void* src, const uint32_t* rows, 
 hipError_t launch_scatter_rows(void* dst, const void* src, const uint32_t* rows, uint32_t m, uint32_t w, size_t elem,
                                hipStream_t s);
 
+// ---- watch lists: dense time series of chosen rows gathered out of the telemetry ring (join_kernels.hip) -----
+constexpr uint32_t kHistoryGatherMax = 32;   // components one launch covers (blockIdx.y)
+struct HistoryGatherDesc {
+    const void* ring;      // [ring][n, w] blocks of this component
+    uint64_t out_offset;   // where its [m][n_samples][w] block starts in `out`, in elements
+    uint32_t w;
+    uint32_t reserved;
+};
+struct HistoryGatherArgs { HistoryGatherDesc c[kHistoryGatherMax]; };   // by value: 768 bytes of kernel arguments
+// Sample j of row rows[e] = tick first_tick + j * every, for e < m, j < n_samples; the caller has validated the range
+// (history_plan.hpp: sampled_range_ok) and rows[e] < n.
+hipError_t launch_history_gather(const HistoryGatherArgs& a, uint32_t n_components, void* out, const uint32_t* rows,
+                                 uint64_t m, uint64_t n, uint64_t first_tick, uint64_t n_samples, uint64_t every,
+                                 uint64_t ring, size_t elem, hipStream_t s);
+
 hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags,
                             unsigned long long* count, hipStream_t s);
 

@@ -29,6 +29,7 @@
 #include "kernels.hpp"
 #include "abi_guard.hpp"
 #include "aql_chain.hpp"
+#include "history_plan.hpp"
 #include "step_plan.hpp"
 
 using namespace sixdof;
@@ -183,6 +184,14 @@ struct sixdof_handle {
     void* d_hist[4] = {nullptr, nullptr, nullptr, nullptr};  // pos, vel, accel, force
     std::vector<void*> d_model_hist;      // one ring per component column of a generated program (same order as custom_model)
     std::vector<unsigned> custom_model_width;   // what the generated code expects per column (0 = unknown), bit 31 = window
+    // watch list (sixdof_set_watch): the components and joined rows whose series sixdof_watch_read gathers out of the ring.
+    // Only ids and rows are kept: ring base pointers and widths are looked up per read, so the ring may come, go or be
+    // re-sized in between.
+    std::vector<uint64_t> watch_ids;
+    uint32_t* d_watch_rows = nullptr;
+    size_t watch_m = 0;
+    void* d_watch_stage = nullptr;        // device staging of one read, grown lazily
+    size_t watch_stage_bytes = 0;
     // rollout model (0 = none, 1 = Apollo lander)
     int model = 0;
     std::vector<double> ap_time, ap_alt, ap_rate, ap_pitch, ap_hspeed, ap_downrange;
@@ -229,6 +238,12 @@ struct sixdof_handle {
             if (f.d_blob) hipFree(f.d_blob);
         custom_folds.clear();
         custom_set_fold_table = nullptr;
+    }
+    // the caller has drained the compute stream (a gather may still read the table)
+    void drop_watch() {
+        if (d_watch_rows) hipFree(d_watch_rows), d_watch_rows = nullptr;
+        watch_ids.clear();
+        watch_m = 0;
     }
     bool has_pair_op() const {
         for (auto& o : ops)
@@ -377,6 +392,8 @@ void sixdof_destroy(sixdof_handle* h) try {
     h->free_fold_tables();
     for (void* p : h->d_hist) if (p) hipFree(p);
     for (void* p : h->d_model_hist) if (p) hipFree(p);
+    h->drop_watch();
+    if (h->d_watch_stage) hipFree(h->d_watch_stage);
     if (h->custom_dl) dlclose(h->custom_dl);
     if (h->pair_dl) dlclose(h->pair_dl);
     for (hipEvent_t e : h->launch_events) hipEventDestroy(e);
@@ -392,6 +409,10 @@ int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_co
     if (!h || (!cols && n_cols)) return SIXDOF_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
     h->replay.drop();
+    if (h->d_watch_rows) {      // a watch holds rows of the join this call replaces
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        h->drop_watch();
+    }
     for (size_t i = 0; i < n_cols; i++) {
         const sixdof_column& c = cols[i];
         if (c.ndim > 1) return h->fail(SIXDOF_ERR_UNSUPPORTED, "bind_columns: only scalar / 1-D components");
@@ -1392,6 +1413,161 @@ int sixdof_history_stream(sixdof_handle* h, uint64_t first_tick, uint64_t n_tick
     h->copy_pending = true;
     h->stream_lo = first_tick;
     h->stream_hi = last;
+    return SIXDOF_OK;
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// Ring and row width of a watchable component: the four recorded Body columns and the non-window component columns of the
+// installed program — what sixdof_history_read accepts.  *ring_base is null while no ring is enabled.
+static bool watch_lookup(const sixdof_handle* h, uint64_t id, const void** ring_base, size_t* w) {
+    const uint64_t body[4] = {h->id_pos, h->id_vel, h->id_accel, h->id_force};
+    for (int k = 0; k < 4; k++)
+        if (id == body[k]) {
+            *ring_base = h->hist_ring ? h->d_hist[k] : nullptr;
+            *w = k == 0 ? 7 : 6;
+            return true;
+        }
+    for (size_t m = 0; m < h->custom_model.size(); m++) {
+        if (h->custom_model[m] != id) continue;
+        const bool window = m < h->custom_model_width.size() && (h->custom_model_width[m] >> 31);
+        const Column* c = h->col(id);
+        if (window || !c) return false;
+        *ring_base = h->hist_ring && m < h->d_model_hist.size() ? h->d_model_hist[m] : nullptr;
+        *w = static_cast<size_t>(c->width);
+        return true;
+    }
+    return false;
+}
+
+int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, const uint64_t* entity_ids,
+                     size_t n_entities) try {
+    if (!h || (!component_ids && n_components) || (!entity_ids && n_entities)) return SIXDOF_ERR_INVALID_ARGUMENT;
+    if ((n_components == 0) != (n_entities == 0))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "set_watch: components without entities (or the reverse); 0 / 0 clears the watch");
+    if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_watch: bind Body columns first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // everything that can fail comes first: the previous watch stays as it is until the new one is complete
+    for (size_t k = 0; k < n_components; k++) {
+        const void* ring_base = nullptr;
+        size_t w = 0;
+        if (!watch_lookup(h, component_ids[k], &ring_base, &w))
+            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_watch: only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
+    }
+    std::vector<uint32_t> rows(n_entities);
+    if (n_entities) {
+        std::unordered_map<uint64_t, uint32_t> row_of;   // entity id -> row of the joined Body set
+        row_of.reserve(h->joined_ids.size() * 2);
+        for (size_t r = 0; r < h->joined_ids.size(); r++) row_of.emplace(h->joined_ids[r], static_cast<uint32_t>(r));
+        for (size_t e = 0; e < n_entities; e++) {
+            auto it = row_of.find(entity_ids[e]);
+            if (it == row_of.end())
+                return h->fail(SIXDOF_ERR_ENTITY_MISMATCH, "set_watch: entity " + std::to_string(entity_ids[e]) + " is not in the joined Body entity set");
+            rows[e] = it->second;
+        }
+    }
+    std::vector<uint64_t> ids(component_ids, component_ids + n_components);
+    uint32_t* d_rows = nullptr;
+    if (n_entities) {
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&d_rows), n_entities * sizeof(uint32_t)));
+        if (hipError_t e = hipMemcpy(d_rows, rows.data(), n_entities * sizeof(uint32_t), hipMemcpyHostToDevice); e != hipSuccess) {
+            hipFree(d_rows);
+            return h->hip_fail(e, "set_watch: upload of the row table");
+        }
+    }
+    if (hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) {   // a gather in flight reads the old table
+        if (d_rows) hipFree(d_rows);
+        return h->hip_fail(e, "set_watch: hipStreamSynchronize");
+    }
+    h->drop_watch();
+    h->watch_ids.swap(ids);
+    h->d_watch_rows = d_rows;
+    h->watch_m = n_entities;
+    return SIXDOF_OK;
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// Ordering of the gather after the batch that recorded the ticks it reads.  With a ring enabled a handle neither replays
+// hipGraphs nor submits AQL chains (graph_eligible needs !hist_ring): every recording launch — the step kernel, the pair
+// and model kernels and their snapshot_tick_to_ring copies — is an eager launch on h->stream, so the gather, launched on
+// h->stream, follows the batch's last launch by stream order, asynchronous steps included.  Were a ring ever recorded
+// through the other two paths: hipGraphLaunch replays on h->stream too (stream order again), and an AQL chain is waited
+// for on the host before sixdof_step returns (aql::run_chain spins on its last packet), i.e. before this call can start.
+// The ring is read on the compute stream only; the copy stream reads the staging buffer.  So the next batch, also on
+// the compute stream, may overwrite the slots with no further wait, and stream_lo / stream_hi — the overwrite protection
+// of a sixdof_history_stream copy that reads the RING from the copy stream — stay as that call left them.
+int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples, uint64_t every, void* const host_dst[],
+                      uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    if (flags & ~SIXDOF_WATCH_ASYNC) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: unknown flags");
+    if (h->watch_ids.empty()) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: no watch (sixdof_set_watch)");
+    if (!h->hist_ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: no history ring (sixdof_set_history)");
+    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: every must be at least 1");
+    if (n_samples == 0) return SIXDOF_OK;
+    if (!host_dst) return SIXDOF_ERR_INVALID_ARGUMENT;
+    if (!sampled_range_ok(first_tick, n_samples, every, h->hist_first_tick, h->tick, h->hist_ring))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: ticks are not (all) in the ring");
+    const size_t n_comp = h->watch_ids.size(), es = h->elem_size(), m = h->watch_m;
+    // per component: ring base and width as they are NOW, and its block in the staging buffer (256-byte aligned)
+    struct Part { const void* ring; size_t w, bytes, offset; };
+    std::vector<Part> parts(n_comp);
+    size_t stage = 0;
+    for (size_t k = 0; k < n_comp; k++) {
+        Part& p = parts[k];
+        if (!watch_lookup(h, h->watch_ids[k], &p.ring, &p.w) || !p.ring)
+            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "watch_read: a watched component is no longer recorded (the program was replaced)");
+        if (!host_dst[k]) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: null host buffer");
+        p.bytes = m * static_cast<size_t>(n_samples) * p.w * es;
+        p.offset = stage;
+        stage += (p.bytes + 255) / 256 * 256;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const bool async = (flags & SIXDOF_WATCH_ASYNC) != 0;
+    if (async && !h->copy_stream) {
+        HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_snap, hipEventDisableTiming));
+        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied, hipEventDisableTiming));
+    }
+    if (stage > h->watch_stage_bytes) {
+        // the copy stream may still read the old buffer (a previous asynchronous read), the compute stream may still write it
+        if (h->copy_pending) HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_watch_stage) hipFree(h->d_watch_stage), h->d_watch_stage = nullptr;
+        h->watch_stage_bytes = 0;
+        HIP_TRY(h, hipMalloc(&h->d_watch_stage, stage));
+        h->watch_stage_bytes = stage;
+    }
+    // one staging buffer: the previous asynchronous read's copies must have drained it before it is overwritten (device-side wait)
+    if (h->copy_pending) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied, 0));
+    for (size_t k0 = 0; k0 < n_comp; k0 += kHistoryGatherMax) {
+        const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kHistoryGatherMax, n_comp - k0));
+        HistoryGatherArgs a{};
+        for (uint32_t k = 0; k < cnt; k++) {
+            a.c[k].ring = parts[k0 + k].ring;
+            a.c[k].out_offset = parts[k0 + k].offset / es;
+            a.c[k].w = static_cast<uint32_t>(parts[k0 + k].w);
+        }
+        hipError_t e = launch_history_gather(a, cnt, h->d_watch_stage, h->d_watch_rows, m, h->desc.n_entities, first_tick, n_samples,
+                                             every, h->hist_ring, es, h->stream);
+        if (e != hipSuccess) return h->hip_fail(e, "history_gather");
+    }
+    const char* staged = static_cast<const char*>(h->d_watch_stage);
+    if (!async) {
+        for (const Part& p : parts)
+            if (p.bytes) HIP_TRY(h, hipMemcpyAsync(host_dst[&p - parts.data()], staged + p.offset, p.bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return SIXDOF_OK;
+    }
+    HIP_TRY(h, hipEventRecord(h->ev_snap, h->stream));            // the series are in the staging buffer after this
+    HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->ev_snap, 0));
+    for (size_t k = 0; k < n_comp; k++) {
+        if (!parts[k].bytes) continue;
+        if (std::find(h->pinned_user.begin(), h->pinned_user.end(), host_dst[k]) == h->pinned_user.end()) {
+            if (hipHostRegister(host_dst[k], parts[k].bytes, hipHostRegisterDefault) == hipSuccess) h->pinned_user.push_back(host_dst[k]);
+            else (void)hipGetLastError();
+        }
+        HIP_TRY(h, hipMemcpyAsync(host_dst[k], staged + parts[k].offset, parts[k].bytes, hipMemcpyDeviceToHost, h->copy_stream));
+    }
+    // re-recorded behind whatever the copy stream already carried: one sixdof_download_wait covers a history_stream copy too
+    HIP_TRY(h, hipEventRecord(h->ev_copied, h->copy_stream));
+    h->copy_pending = true;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 

@@ -460,6 +460,7 @@ class HipExec:
         rc = self._lib.sixdof_set_history(self._h, int(ring_ticks))
         if rc != L.OK:
             _raise(self._h, rc, "sixdof_set_history")
+        self._ring_ticks = int(ring_ticks)      # what stream_series compares its batch with (stream_history sizes its own ring)
 
     def history(self, name: str, first_tick: int, last_tick: int) -> np.ndarray:
         """exec.history() analogue: [last-first+1, n, w] block of component `name`, row k = state after tick first+k."""
@@ -472,6 +473,85 @@ class HipExec:
             if rc != L.OK:
                 _raise(self._h, rc, "sixdof_history_read")
         return out
+
+    # ---- watch lists: time series of chosen (entity, component) pairs out of the ring ---------------------------
+    def set_watch(self, names: Sequence[str], entity_ids) -> None:
+        """Choose what history_series / stream_series read: components `names` (world_pos / world_vel / world_accel / force and
+        the plain component columns of a generated program) of the entities `entity_ids`, in that order; duplicates are
+        allowed.  Independent of enable_history (either order).  Empty names and ids clear the watch."""
+        names = [names] if isinstance(names, str) else list(names)
+        for name in names:
+            if name in self._windows:
+                raise ValueError(f"{name} is a window component: it is its own history (HipExec.component), the ring does not copy it per tick")
+        ids = np.ascontiguousarray(entity_ids, dtype=np.uint64).reshape(-1)
+        comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        rc = self._lib.sixdof_set_watch(self._h, comp.ctypes.data_as(u64p), len(comp), ids.ctypes.data_as(u64p), len(ids))
+        if rc != L.OK:
+            _raise(self._h, rc, "sixdof_set_watch")
+        self._watch = (names, len(ids))
+
+    def _series_buffers(self, n_samples: int):
+        names, m = getattr(self, "_watch", ((), 0))
+        width = lambda name: 7 if name == "world_pos" else (self._aux[name].shape[1] if name in self._aux else 6)
+        out = {}
+        for name in names:      # a name watched twice shares one entry: its buffer is filled once per occurrence, identically
+            out[name] = np.empty((m, n_samples, width(name)), dtype=self.dtype)
+        ptrs = (C.c_void_p * max(1, len(names)))(*[out[name].ctypes.data for name in names])
+        return out, ptrs
+
+    def history_series(self, first_tick: int, last_tick: int, every: int = 1) -> dict:
+        """{name: [m, samples, w]} of the watched pairs: sample j of entity e is the state after tick first_tick + j * every,
+        up to last_tick.  The rows are gathered on the device; m rows per sample cross the link, not n."""
+        first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
+        n_samples = (last_tick - first_tick) // every + 1 if every > 0 and last_tick >= first_tick else 0
+        out, ptrs = self._series_buffers(n_samples)
+        rc = self._lib.sixdof_watch_read(self._h, first_tick, n_samples, every, ptrs, 0)
+        if rc != L.OK:
+            _raise(self._h, rc, "sixdof_watch_read")
+        return out
+
+    def stream_series(self, n_batches: int, ticks_per_batch: int, every: int = 1, consume=None, flags: int = 0) -> float:
+        """stream_history for a watch: every `every`-th tick of the watched pairs to the host, overlapped with the stepper.
+        After batch i is enqueued its samples are gathered on the compute stream and copied on the copy stream into one of two
+        host buffer sets while batch i+1 computes; because the ring is read on the compute stream, a ring of one batch is
+        enough (enabled here unless enable_history already made one at least that large).  `consume(batch_index, first_tick,
+        {name: array [m, ticks_per_batch // every, w]})` sees a batch once it has landed — first_tick is the batch's first
+        SAMPLED tick, the last one is the batch's last tick; the arrays are reused two batches later.  Returns the wall time in
+        seconds.  (The ring size is the one enable_history was last called with: after a stream_history, which sizes its own
+        ring, call enable_history again.)"""
+        import time
+        n_batches, ticks_per_batch, every = int(n_batches), int(ticks_per_batch), int(every)
+        if every < 1 or ticks_per_batch < 1 or ticks_per_batch % every != 0:
+            raise ValueError(f"stream_series: ticks_per_batch ({ticks_per_batch}) must be a positive multiple of every ({every})")
+        if not getattr(self, "_watch", ((), 0))[0]:
+            raise ValueError("stream_series: no watch (set_watch)")
+        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
+            self.enable_history(ticks_per_batch)
+        n_samples = ticks_per_batch // every
+        bufs, ptrs = zip(*[self._series_buffers(n_samples) for _ in range(2)])
+        self.sync()              # nothing of an earlier streaming run is in flight
+        self.set_flags(flags | L.FLAG_ASYNC_STEP)
+        t0 = time.perf_counter()
+        try:
+            first = []
+            for i in range(n_batches):
+                first.append(self.tick + every)                          # samples end on the batch's last tick
+                self.invoke_batch(ticks_per_batch)                       # enqueue batch i
+                if i > 0:
+                    self.download_wait()                                 # batch i-1 has landed in bufs[(i-1) % 2]
+                    if consume is not None:
+                        consume(i - 1, first[i - 1], bufs[(i - 1) % 2])
+                rc = self._lib.sixdof_watch_read(self._h, first[i], n_samples, every, ptrs[i % 2], L.WATCH_ASYNC)
+                if rc != L.OK:
+                    _raise(self._h, rc, "sixdof_watch_read")
+            self.download_wait()
+            if consume is not None and n_batches:
+                consume(n_batches - 1, first[-1], bufs[(n_batches - 1) % 2])
+        finally:
+            self.set_flags(flags)
+            self.sync()          # also drops the page locks on `bufs` before they go out of scope
+        return time.perf_counter() - t0
 
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))

@@ -399,6 +399,30 @@ int sixdof_history_read(sixdof_handle* h, uint64_t component_id, uint64_t tick, 
  * allocated until sixdof_sync, which also releases their page locks. */
 int sixdof_history_stream(sixdof_handle* h, uint64_t first_tick, uint64_t n_ticks, void* const host_dst[4]);
 
+/* ---- watch lists: time series of chosen (entity, component) pairs out of the ring ----------------------------
+ * What exec.history("e1.x"), a plot or the commit sink wants is a handful of pairs over time, often at a lower rate than
+ * the simulation's — not every row of every tick.  A watch names the components and the entities once; a read gathers
+ * their rows out of the ring on the device and moves m rows per sample to the host, not n.
+ *
+ * sixdof_set_watch: watchable components are the ones sixdof_history_read accepts (world_pos / world_vel / world_accel /
+ * force and the non-window component columns of a generated program; anything else: SIXDOF_ERR_COMPONENT_NOT_FOUND).
+ * Entity ids are resolved to rows of the joined Body set, in the order given; duplicates are allowed; an id outside the
+ * join is SIXDOF_ERR_ENTITY_MISMATCH.  A failed call leaves the previous watch as it was.  0 components and 0 entities
+ * clear the watch.  Independent of sixdof_set_history (either order, any later ring size); sixdof_bind_columns drops it. */
+int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, const uint64_t* entity_ids,
+                     size_t n_entities);
+#define SIXDOF_WATCH_ASYNC 1u
+/* Read n_samples samples of every watched pair: sample j is the state after tick first_tick + j * every.  host_dst[k]
+ * receives component k (the order of sixdof_set_watch) as [n_entities][n_samples][w_k]: one contiguous series per pair.
+ * flags = 0: returns when the data is in host_dst.  SIXDOF_WATCH_ASYNC: returns once the gather and the copies are
+ * enqueued (the copies on the copy stream, host_dst page-locked on first use); sixdof_download_wait blocks until they
+ * have landed, and the buffers must stay allocated until sixdof_sync, as for sixdof_history_stream.  Either way the ring
+ * is read on the compute stream, so a later sixdof_step may overwrite the slots without waiting for the copy.
+ * n_samples = 0 is a no-op.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied: no watch, no ring, every = 0, or a
+ * sampled tick that is not (or no longer) in the ring. */
+int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples, uint64_t every, void* const host_dst[],
+                      uint32_t flags);
+
 /* ---- rollout models: systems piped AROUND six_dof, fused with it (the pipes of examples/<name>/sim.py) ------------- */
 struct sixdof_apollo_tables; /* include/sixdof_apollo.h */
 /* Select the Apollo-lander rollout model (examples/apollo-lander/sim.py:517-526 + the guidance sidecar
