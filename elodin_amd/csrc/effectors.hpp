@@ -181,6 +181,8 @@ __device__ __forceinline__ Spatial<T> calc_accel(const Quat<T>& q, const Wrench<
 //   so the four are finite together; the LAST stage's taint is enough: it poisons A_3 (the world_accel output and, through
 //   sum(A_s), the new velocity), and the caller adds it to the (dt/6) factor of the position update, which the reference
 //   poisons through v_s = v0 + c*dt*A_(s-1).  One multiply and two adds per tick instead of work in every stage.
+//   A pipe that READS the stage velocity also gets it in the last stage's v_s (step_kernel.hpp), because there the
+//   reference's NaN A_2 reaches the last wrench, i.e. the `force` column, through the effector itself.
 //   Semi-implicit: the one calc_accel sees q0.
 template <class T>
 __device__ __forceinline__ T accel_taint(T norm2) {

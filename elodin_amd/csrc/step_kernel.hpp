@@ -343,7 +343,10 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
             b.q = integrate_world(q0, h3 * v0.ang, &n3);
             const T taint = accel_taint(n3);   // NaN when q0 or v0.ang is not finite (effectors.hpp), +-0 otherwise
             b.p = axpy(h3, v0.lin, p0);
-            b.v = axpy(h3, A, v0);
+            // an effector that reads the stage velocity sees v_s = v0 + dt * A_2, and the reference's A_2 is NaN when the attitude
+            // is not finite (calc_accel rotates both halves): the taint goes into the step (exact for +-0), so that the last
+            // stage's wrench — the `force` column — is poisoned like the reference's.  Velocity-independent pipes: nothing added.
+            b.v = axpy(PIPE::vel_independent(P) ? h3 : h3 + taint, A, v0);
             sv = sv + b.v;
             // x' = x0 (+) (dt/6) sum(v_s): complete here, before the last force evaluation
             const T g = dt * T(1.0 / 6.0);

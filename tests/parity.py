@@ -82,14 +82,19 @@ class Worst:
     def check(self, what=""):
         line = (f"{what}: {len(self.checkpoints)} checkpoints {self.checkpoints}; vector-scaled {self.vector}; element-wise (floor {ELEMENT_FLOOR:g} x "
                 f"vector) {self.element}; element-wise (floor {REPORT_FLOOR:g}, reported) {self.element_raw}")
+        self.report(line)
+        assert max(self.vector.values()) < F64_RTOL, (what, self.vector)
+        assert max(self.element.values()) < F64_RTOL, (what, "element-wise", self.element)
+
+    @staticmethod
+    def report(line, name="parity_figures.txt"):
+        """Print measured figures and, where the GPU run's scratch directory exists, append them to `name` there."""
         print(line)
         from pathlib import Path
         out = Path(__file__).resolve().parent.parent / "gpurun_out"
         if out.is_dir():                          # the GPU box's scratch: the measured figures come back with the run
-            with open(out / "parity_figures.txt", "a") as f:
+            with open(out / name, "a") as f:
                 f.write(line + "\n")
-        assert max(self.vector.values()) < F64_RTOL, (what, self.vector)
-        assert max(self.element.values()) < F64_RTOL, (what, "element-wise", self.element)
 
 
 def to_oracle_ops(effectors):
