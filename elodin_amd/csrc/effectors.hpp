@@ -73,6 +73,9 @@ __device__ __forceinline__ void apply_one(const DevOp& op, const Vec3<T>& aux, c
 // into the same kernel.  Pipes without such systems inherit these no-ops.
 struct NoModel {
     static constexpr bool kHasModel = false;
+    // one of the pipes below (PipeStatic, PipeGeneric), whose ops the host layer builds: every aux column is [n,3].  A generated
+    // effector pipe has no model either, but its columns are [n,1..3] and its op slots are just the columns its code reads
+    static constexpr bool kBuiltIn = false;
     static constexpr bool kWritesInertia = false;
     static constexpr bool kPreReadsAccel = false;   // a system in front of six_dof reads world_accel (the previous tick's)
     // a generated program WITHOUT six_dof whose systems touch no Body column (a whole-world StableHLO tick: every component of the
@@ -97,6 +100,9 @@ struct NoModel {
 
 template <int KIND>
 struct KindTraits {
+    // how many leading constants of DevOp::p the kind reads (apply_one above)
+    static constexpr int n_params =
+        KIND == SIXDOF_EFF_CONST_WRENCH ? 6 : (KIND == SIXDOF_EFF_UNIFORM_GRAVITY || KIND == SIXDOF_EFF_BALL_DRAG) ? 3 : 0;
     static constexpr bool reads_velocity = (KIND == SIXDOF_EFF_BALL_DRAG);
     static constexpr bool world_torque = (KIND == SIXDOF_EFF_CONST_WRENCH || KIND == SIXDOF_EFF_WORLD_TORQUE);
     static constexpr bool body_torque = (KIND == SIXDOF_EFF_BODY_TORQUE);
@@ -109,6 +115,7 @@ struct KindTraits {
 template <int... KINDS>
 struct PipeStatic : NoModel {
     static constexpr int kOps = sizeof...(KINDS);
+    static constexpr bool kBuiltIn = true;
     static constexpr bool kStatic = true;
     static constexpr bool kWorldTorque = (false || ... || KindTraits<KINDS>::world_torque);
     static constexpr bool kBodyTorque = (false || ... || KindTraits<KINDS>::body_torque);
@@ -117,6 +124,11 @@ struct PipeStatic : NoModel {
     static constexpr bool uses_aux() {
         constexpr bool t[sizeof...(KINDS) + 1] = {KindTraits<KINDS>::uses_aux..., false};
         return K < kOps && t[K];
+    }
+    template <int K>
+    static constexpr int n_params() {   // constants of op K the pipe reads
+        constexpr int t[sizeof...(KINDS) + 1] = {KindTraits<KINDS>::n_params..., 0};
+        return K < kOps ? t[K] : 0;
     }
     __device__ static __forceinline__ bool vel_independent(const StepParams&) { return !kReadsVelocity; }
     template <class T, size_t... I>
@@ -134,11 +146,14 @@ struct PipeStatic : NoModel {
 // Run-time interpreter: wave-uniform branches on kernel arguments.
 struct PipeGeneric : NoModel {
     static constexpr int kOps = kMaxOps;
+    static constexpr bool kBuiltIn = true;
     static constexpr bool kStatic = false;
     static constexpr bool kWorldTorque = true;
     static constexpr bool kBodyTorque = true;
     template <int K>
     static constexpr bool uses_aux() { return true; }
+    template <int K>
+    static constexpr int n_params() { return 6; }
     __device__ static __forceinline__ bool vel_independent(const StepParams& P) { return P.vel_independent != 0; }
     template <class T, class R>
     __device__ static __forceinline__ void apply(const StepParams& P, const Vec3<T> (&aux)[kMaxOps], const R&,

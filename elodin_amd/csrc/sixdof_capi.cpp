@@ -819,6 +819,8 @@ int build_dev_ops(sixdof_handle* h, DevOp* out, uint32_t* n_out, uint32_t* vel_i
             o.kind == SIXDOF_EFF_WORLD_TORQUE || o.kind == SIXDOF_EFF_WORLD_FORCE) {
             Column* c = h->col(o.aux_component_id);
             if (!c) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "step: effector aux column not bound");
+            // the built-in kernels count on this refusal: they load [n,3] rows with the width fixed at compile time and most of
+            // them never read DevOp::aux_width, which stays 0 here (step_kernel.hpp, kAuxRows3)
             if (c->width != 3 || c->prim != h->state_prim())
                 return h->fail(SIXDOF_ERR_VALUE_SIZE_MISMATCH, "step: effector aux column must be [n,3] of the state dtype");
             if (!c->joined) {   // first use after binding: join it onto the Body set and bring its rows over

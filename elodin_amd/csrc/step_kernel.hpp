@@ -120,6 +120,77 @@ __device__ __forceinline__ void col_st(T* p, T v) {
     else *p = v;
 }
 
+// ---- kernel arguments of the built-in pipes -----------------------------------------------------------------------
+
+// At one tick per launch the launch is a latency chain, and the packet's agent-scope acquire empties the scalar cache
+// before every launch.  An argument that is fetched where it is first used is then a fresh miss, waited for on its own in
+// the middle of the chain (one per 64-byte line of the argument block: the op count, the aux pointers, state_only, the
+// gravity vector...).  The built-in kernels that can afford it (kEntryArgs in the kernel) therefore read every StepParams
+// field they use at kernel entry, in one burst under the wait that precedes the slab DMA anyway, and hold the values in scalar
+// registers there: an empty asm statement takes them as "s" operands.  The kernel body goes on naming P.field; those reads are
+// the same (invariant) loads and fold into the entry ones.
+// What the hold guarantees and what it does not: the loads cannot sink below the statement, so they happen in the entry
+// block.  It does not keep the register allocator from dropping a value later, where scalar registers are short, and fetching
+// it again where it is used.  In this build that happens in: the gravity | drag pipe under RK4 (the drag's three constants,
+// once, in front of the tick body), the accel-check kernels (the tick count, after the check tick: once per upload), and a
+// recording launch's history-ring arguments.  tests/test_step_kernel_entry_loads.py lists these and pins every other
+// instantiation to no scalar load behind the slab DMA.
+// Generated pipes and programs (anything but PipeStatic / PipeGeneric: PIPE::kBuiltIn) are a different trade (up to hundreds
+// of arguments, most of them used once) and keep fetching on demand; their code is what it was.
+
+// The fields of op K that PIPE reads, by value (the others stay zero and are not held).
+template <class PIPE, int K, bool WIDTH>
+struct OpArgs {
+    int32_t kind, aux_width;
+    const void* aux;
+    double p[6];
+};
+template <class PIPE, int K, bool WIDTH>
+__device__ __forceinline__ OpArgs<PIPE, K, WIDTH> op_args(const StepParams& P) {
+    OpArgs<PIPE, K, WIDTH> o{};
+    if constexpr (!PIPE::kStatic) o.kind = P.ops[K].kind;
+    if constexpr (WIDTH) o.aux_width = P.ops[K].aux_width;
+    if constexpr (PIPE::template uses_aux<K>()) o.aux = P.ops[K].aux;
+#pragma unroll
+    for (int j = 0; j < PIPE::template n_params<K>(); j++) o.p[j] = P.ops[K].p[j];
+    return o;
+}
+struct NotRead {};   // stands in for a field this instantiation does not read
+template <bool READ, class V>
+__device__ __forceinline__ auto arg_if(const V& v) {
+    if constexpr (READ) return v;
+    else return NotRead{};
+}
+template <class V>
+__device__ __forceinline__ void hold_in_sgpr(V v) {
+    asm volatile("" ::"s"(v));
+}
+__device__ __forceinline__ void hold_in_sgpr(NotRead) {}
+template <class PIPE, int K, bool WIDTH>
+__device__ __forceinline__ void hold_in_sgpr(OpArgs<PIPE, K, WIDTH> o) {
+    if constexpr (!PIPE::kStatic) hold_in_sgpr(o.kind);
+    if constexpr (WIDTH) hold_in_sgpr(o.aux_width);
+    if constexpr (PIPE::template uses_aux<K>()) hold_in_sgpr(o.aux);
+#pragma unroll
+    for (int j = 0; j < PIPE::template n_params<K>(); j++) hold_in_sgpr(o.p[j]);
+}
+// Operands by value: all of them are read before the first asm statement, so the loads form one group with one wait
+// (an asm statement between two loads splits them into two groups, each with a wait of its own).
+template <class... V>
+__device__ __forceinline__ void hold_in_sgprs(V... v) {
+    (hold_in_sgpr(v), ...);
+}
+template <class PIPE, bool CHECK, bool WIDTH>
+__device__ __forceinline__ void read_entry_args(const StepParams& P) {
+    hold_in_sgprs(P.n_ticks, P.n_ops, P.streaming, P.state_only, P.dt_g, P.dt, arg_if<!PIPE::kStatic>(P.vel_independent),
+                  arg_if<CHECK>(P.accel_in_check),
+                  // the history ring: only a recording launch uses more than the first two, far from here, and there the
+                  // register allocator may still prefer fetching one again to keeping it (an argument load is cheaper to
+                  // repeat than a register is to hold).  They share the cache lines of the fields above.
+                  P.hist_pos, P.hist_ring, P.hist_slot0, P.hist_vel, P.hist_accel, P.hist_force,
+                  op_args<PIPE, 0, WIDTH>(P), op_args<PIPE, 1, WIDTH>(P), op_args<PIPE, 2, WIDTH>(P), op_args<PIPE, 3, WIDTH>(P));
+}
+
 // ---- the kernel --------------------------------------------------------------------------------------
 
 // CHECK: the instantiation a launch with StepParams::accel_in_check uses (first RK4 launch after an upload, once): its
@@ -149,6 +220,17 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
     T* const g_force = static_cast<T*>(P.force) + (size_t)row0 * 6;
     const T* const g_inertia = static_cast<const T*>(P.inertia) + (size_t)row0 * 7;
 
+    // Which instantiations take the entry burst and the fixed-width aux rows: those where the compiler keeps the shape.
+    //   kEntryArgs: the compile-time pipes, and the interpreter under RK4.  The semi-implicit interpreter is so short of scalar
+    //     registers that the register allocator throws the whole burst away and fetches every argument again where it is
+    //     used: it keeps fetching on demand, as before.
+    //   kAuxRows3: not the float interpreter.  Its 12-byte rows become one dwordx3 each, and merging that register triple
+    //     with the zeroes of an absent column makes the compiler wait behind every column: it keeps the run-time width,
+    //     whose twelve single loads go out together (the width is then part of the burst).
+    constexpr bool kEntryArgs = PIPE::kBuiltIn && (PIPE::kStatic || INTEGRATOR == kRk4);
+    constexpr bool kAuxRows3 = kEntryArgs && (PIPE::kStatic || sizeof(T) == 8);
+    if constexpr (kEntryArgs) read_entry_args<PIPE, CHECK, !kAuxRows3>(P);   // every argument, once, before the slab DMA
+
     // systems only and none of them touches a Body column (NoModel::kBodyDead): the Body slabs stay where they are
     constexpr bool kDead = INTEGRATOR == kNone && PIPE::kBodyDead;
     if constexpr (!kDead) {
@@ -163,7 +245,11 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
         }
     }
 
-    // per-entity effector columns: 24-byte rows, read once per launch straight from global
+    // per-entity effector columns: 24-byte rows, read once per launch straight from global, right behind the slab DMA so
+    // that one wait covers both.  kAuxRows3 (above): the row width is 3 at compile time (the host layer refuses any other
+    // column of a built-in op, build_dev_ops) and the three loads of a row go out back to back; with a run-time width the
+    // double-precision kernels put a branch and a wait for everything in flight, the slabs included, in front of the second
+    // and of the third.
     const bool active = t < rows;
     Vec3<T> aux[kMaxOps];
 #pragma unroll
@@ -172,9 +258,14 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
         constexpr int k = decltype(kc)::value;
         if constexpr (PIPE::template uses_aux<k>()) {
             if (k < (int)P.n_ops && P.ops[k].aux != nullptr && active) {
-                const int w = P.ops[k].aux_width ? P.ops[k].aux_width : 3;  // row width of the column (1..3), wave-uniform
-                const T* a = static_cast<const T*>(P.ops[k].aux) + (size_t)(row0 + t) * w;
-                aux[k] = Vec3<T>{a[0], w > 1 ? a[1] : T(0), w > 2 ? a[2] : T(0)};
+                if constexpr (!kAuxRows3) {
+                    const int w = P.ops[k].aux_width ? P.ops[k].aux_width : 3;  // row width of the column (1..3), wave-uniform
+                    const T* a = static_cast<const T*>(P.ops[k].aux) + (size_t)(row0 + t) * w;
+                    aux[k] = Vec3<T>{a[0], w > 1 ? a[1] : T(0), w > 2 ? a[2] : T(0)};
+                } else {
+                    const T* a = static_cast<const T*>(P.ops[k].aux) + (size_t)(row0 + t) * 3;
+                    aux[k] = Vec3<T>{a[0], a[1], a[2]};
+                }
             }
         }
     };
