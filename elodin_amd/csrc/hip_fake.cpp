@@ -1,0 +1,234 @@
+// hip_fake.cpp — a host-only stand-in for the HIP runtime, the kernel launchers and the AQL queue, so that the whole
+// host layer (sixdof_capi.cpp) links and runs under AddressSanitizer without a GPU: `make capi_test`,
+// capi_lifecycle_test.cpp.  Never part of the library.
+//
+// Device memory is calloc'd host memory, copies are memcpy, streams and events are small heap objects, everything
+// completes at once.  The k-th FALLIBLE call (allocations, creations, copies, records, waits, synchronisations,
+// launches) returns hipErrorOutOfMemory when armed; frees and destroys always succeed.  The fake keeps the live
+// allocations, streams, events and page locks, and its launch stubs check that every table a launch is handed lies
+// inside a live allocation of sufficient size.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <set>
+#include <string>
+
+#include "../../include/sixdof_hip.h"
+#include "aql_chain.hpp"
+#include "kernels.hpp"
+
+namespace hip_fake {
+
+std::map<const char*, size_t> g_allocs;
+std::set<void*> g_streams, g_events, g_pins;
+long g_calls = 0, g_fail_at = -1, g_violations = 0;
+bool g_fired = false;
+
+void fail_after(long n) { g_fail_at = n < 0 ? -1 : g_calls + n, g_fired = false; }   // the n-th fallible call from now fails (once); < 0: none
+bool fired() { return g_fired; }
+long calls() { return g_calls; }
+long violations() { return g_violations; }
+size_t live_allocations() { return g_allocs.size(); }
+size_t live_streams() { return g_streams.size(); }
+size_t live_events() { return g_events.size(); }
+size_t live_page_locks() { return g_pins.size(); }
+
+static hipError_t fallible() {
+    if (g_calls++ != g_fail_at) return hipSuccess;
+    g_fired = true;
+    return hipErrorOutOfMemory;
+}
+// [p, p + bytes) lies inside one live allocation
+static bool live(const void* p, size_t bytes) {
+    auto it = g_allocs.upper_bound(static_cast<const char*>(p));
+    if (!p || it == g_allocs.begin()) return false;
+    --it;
+    return static_cast<const char*>(p) + bytes <= it->first + it->second;
+}
+static bool need(bool ok, const char* what) {
+    if (!ok) std::fprintf(stderr, "hip_fake: a launch was handed a table that is not (wholly) a live allocation: %s\n", what), g_violations++;
+    return ok;
+}
+static hipError_t launch(bool ok) {
+    if (hipError_t e = fallible(); e != hipSuccess) return e;
+    return ok ? hipSuccess : hipErrorInvalidValue;
+}
+
+}  // namespace hip_fake
+using namespace hip_fake;
+
+// ---- the runtime ----------------------------------------------------------------------------------------------
+const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory (injected)" : "error"; }
+hipError_t hipGetLastError(void) { return hipSuccess; }
+hipError_t hipGetDeviceCount(int* n) { return *n = 1, hipSuccess; }
+hipError_t hipSetDevice(int) { return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t bytes) {
+    *p = nullptr;
+    if (hipError_t e = fallible(); e != hipSuccess) return e;
+    *p = std::calloc(bytes ? bytes : 1, 1);
+    g_allocs[static_cast<const char*>(*p)] = bytes;
+    return hipSuccess;
+}
+hipError_t hipFree(void* p) {
+    if (!p) return hipSuccess;
+    if (!g_allocs.erase(static_cast<const char*>(p))) std::fprintf(stderr, "hip_fake: hipFree of %p, which is not a live allocation\n", p), g_violations++;
+    std::free(p);   // a second free of the same pointer is AddressSanitizer's to report
+    return hipSuccess;
+}
+static hipError_t create(std::set<void*>& live_set, void** out) {
+    *out = nullptr;
+    if (hipError_t e = fallible(); e != hipSuccess) return e;
+    live_set.insert(*out = std::malloc(8));
+    return hipSuccess;
+}
+static hipError_t destroy(std::set<void*>& live_set, void* p) {
+    if (!live_set.erase(p)) return std::fprintf(stderr, "hip_fake: destroy of %p, which is not live\n", p), g_violations++, hipErrorInvalidValue;
+    std::free(p);
+    return hipSuccess;
+}
+// a stream or event handed to record / wait / synchronise: null or destroyed is an error (the null stream is legal to query only)
+static hipError_t use(bool ok) {
+    if (hipError_t e = fallible(); e != hipSuccess) return e;
+    if (!ok) std::fprintf(stderr, "hip_fake: null or destroyed stream / event\n"), g_violations++;
+    return ok ? hipSuccess : hipErrorInvalidHandle;
+}
+hipError_t hipStreamCreate(hipStream_t* s) { return create(g_streams, reinterpret_cast<void**>(s)); }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return create(g_streams, reinterpret_cast<void**>(s)); }
+hipError_t hipStreamDestroy(hipStream_t s) { return destroy(g_streams, s); }
+hipError_t hipStreamSynchronize(hipStream_t s) { return use(g_streams.count(s)); }
+hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { return use(g_streams.count(s) && g_events.count(e)); }
+hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipErrorNotSupported; }
+hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { return *g = nullptr, hipErrorNotSupported; }
+hipError_t hipGraphInstantiate(hipGraphExec_t*, hipGraph_t, hipGraphNode_t*, char*, size_t) { return hipErrorNotSupported; }
+hipError_t hipGraphDestroy(hipGraph_t) { return hipSuccess; }
+hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }
+hipError_t hipGraphUpload(hipGraphExec_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipErrorNotSupported; }
+hipError_t hipEventCreate(hipEvent_t* e) { return create(g_events, reinterpret_cast<void**>(e)); }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return create(g_events, reinterpret_cast<void**>(e)); }
+hipError_t hipEventDestroy(hipEvent_t e) { return destroy(g_events, e); }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { return use(g_events.count(e) && g_streams.count(s)); }
+hipError_t hipEventSynchronize(hipEvent_t e) { return use(g_events.count(e)); }
+hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { return *ms = 0.f, hipSuccess; }
+hipError_t hipHostRegister(void* p, size_t, unsigned) { return g_pins.insert(p).second ? hipSuccess : hipErrorHostMemoryAlreadyRegistered; }
+hipError_t hipHostUnregister(void* p) { return g_pins.erase(p) ? hipSuccess : hipErrorHostMemoryNotRegistered; }
+// whichever side is device memory must be live; the other side is the caller's (AddressSanitizer watches the memcpy itself)
+static hipError_t copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (hipError_t e = fallible(); e != hipSuccess) return e;
+    const bool dst_dev = kind == hipMemcpyHostToDevice || kind == hipMemcpyDeviceToDevice, src_dev = kind == hipMemcpyDeviceToHost || kind == hipMemcpyDeviceToDevice;
+    if (!need(!dst_dev || live(dst, bytes), "copy destination") || !need(!src_dev || live(src, bytes), "copy source")) return hipErrorInvalidValue;
+    std::memcpy(dst, src, bytes);
+    return hipSuccess;
+}
+hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { return copy(dst, src, bytes, kind); }
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    return need(g_streams.count(s), "copy on a null or destroyed stream") ? copy(dst, src, bytes, kind) : hipErrorInvalidHandle;
+}
+hipError_t hipMemsetAsync(void* dst, int v, size_t bytes, hipStream_t) {
+    if (hipError_t e = fallible(); e != hipSuccess) return e;
+    if (!need(live(dst, bytes), "memset destination")) return hipErrorInvalidValue;
+    std::memset(dst, v, bytes);
+    return hipSuccess;
+}
+
+// ---- the launchers (kernels.hpp): no arithmetic, but every pointer a real kernel would follow is checked ---------
+namespace sixdof {
+
+static bool body_ok(const void* pos, const void* vel, const void* accel, const void* force, const void* inertia, size_t n, size_t es) {
+    return need(live(pos, n * 7 * es), "world_pos") & need(live(vel, n * 6 * es), "world_vel") & need(live(accel, n * 6 * es), "world_accel") &
+           need(live(force, n * 6 * es), "force") & need(live(inertia, n * 7 * es), "inertia");
+}
+static bool ops_ok(const DevOp* ops, uint32_t n_ops, size_t n, size_t es) {
+    bool ok = true;
+    for (uint32_t k = 0; k < n_ops; k++)
+        if (ops[k].aux) ok &= need(live(ops[k].aux, n * (ops[k].aux_width ? ops[k].aux_width : 3) * es), "effector aux column");
+    return ok;
+}
+static bool step_ok(const StepParams& p, int dtype) {
+    const size_t n = p.n, es = dtype == 1 ? 4 : 8;
+    bool ok = body_ok(p.pos, p.vel, p.accel, p.force, p.inertia, n, es) & ops_ok(p.ops, p.n_ops, n, es);
+    if (p.hist_ring) {
+        const size_t r = p.hist_ring;
+        ok &= need(live(p.hist_pos, r * n * 7 * es), "hist_pos") & need(live(p.hist_vel, r * n * 6 * es), "hist_vel") &
+              need(live(p.hist_accel, r * n * 6 * es), "hist_accel") & need(live(p.hist_force, r * n * 6 * es), "hist_force");
+    }
+    for (int k = 0; k < kMaxModelCols; k++) {
+        if (p.model_cols[k]) ok &= need(live(p.model_cols[k], n * es), "program column");
+        if (p.model_hist[k]) ok &= need(live(p.model_hist[k], p.hist_ring * n * es), "program column ring");
+    }
+    return ok;
+}
+static bool pair_ok(const PairParams& p) {
+    const size_t n = p.n, u = sizeof(uint32_t), d = sizeof(double);
+    bool ok = body_ok(p.pos, p.vel, p.accel, p.force, p.inertia, n, 8) & ops_ok(p.ops, p.n_ops, n, 8);
+    if (n) ok &= need(live(p.pack, n * kPackWidth * d), "pack") & need(live(p.partial, n * p.partial_width * p.splits * d), "partial");
+    if (n && p.pack_next) ok &= need(live(p.pack_next, n * kPackWidth * d), "pack_next");
+    if (p.pair_kind != SIXDOF_EFF_ALLPAIRS_GRAVITY_SOFTENED) {
+        ok &= need(live(p.row_start, (n + 1) * u), "row_start");
+        if (ok) ok &= need(p.row_start[n] == p.n_edges, "row_start[n] != n_edges");
+    }
+    if (p.n_edges) ok &= need(live(p.dst, p.n_edges * u), "dst");
+    if (p.n_hubs)
+        ok &= need(live(p.hub_rows, p.n_hubs * u), "hub_rows") & need(live(p.hub_chunk_start, (p.n_hubs + 1) * u), "hub_chunk_start") &
+              need(live(p.chunk_e0, p.n_hub_chunks * u), "chunk_e0") & need(live(p.chunk_row, p.n_hub_chunks * u), "chunk_row") &
+              need(live(p.chunk_partial, size_t(p.n_hub_chunks) * kPartialWidth * d), "chunk_partial");
+    return ok;
+}
+
+StepKernel select_step(const StepParams&, int, int) { return {}; }
+hipError_t launch_step(const StepParams& p, int, int dtype, hipStream_t) { return launch(step_ok(p, dtype)); }
+uint32_t pair_splits_for(uint32_t) { return 1; }
+hipError_t launch_pair_ticks(const PairParams& p, int, uint32_t n_ticks, hipStream_t, uint64_t* launches) { return *launches += 1 + 2 * n_ticks, launch(pair_ok(p)); }
+hipError_t launch_pair_small(const PairParams& p, int, uint32_t, hipStream_t, uint64_t* launches) { return *launches += 1, launch(pair_ok(p)); }
+hipError_t launch_apollo(const ApolloParams&, hipStream_t) { return launch(true); }
+
+static hipError_t move_rows(char* dst, const char* src, const uint32_t* rows, uint32_t m, size_t row, bool gather) {
+    if (!need(live(rows, m * sizeof(uint32_t)), "join rows")) return launch(false);
+    for (uint32_t j = 0; j < m; j++) {
+        char* to = gather ? dst + j * row : dst + rows[j] * row;
+        const char* from = gather ? src + rows[j] * row : src + j * row;
+        if (!need(live(to, row) && live(from, row), "joined column")) return launch(false);
+        std::memcpy(to, from, row);
+    }
+    return launch(true);
+}
+hipError_t launch_gather_rows(void* dst, const void* src, const uint32_t* rows, uint32_t m, uint32_t w, size_t elem, hipStream_t) {
+    return move_rows(static_cast<char*>(dst), static_cast<const char*>(src), rows, m, w * elem, true);
+}
+hipError_t launch_scatter_rows(void* dst, const void* src, const uint32_t* rows, uint32_t m, uint32_t w, size_t elem, hipStream_t) {
+    return move_rows(static_cast<char*>(dst), static_cast<const char*>(src), rows, m, w * elem, false);
+}
+// the gather itself (join_kernels.hip), so that watch reads return what the ring holds
+hipError_t launch_history_gather(const HistoryGatherArgs& a, uint32_t n_components, void* out, const uint32_t* rows, uint64_t m, uint64_t n,
+                                 uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t) {
+    if (!need(live(rows, m * sizeof(uint32_t)), "watch rows")) return launch(false);
+    for (uint32_t c = 0; c < n_components; c++) {
+        const size_t row = a.c[c].w * elem;
+        for (uint64_t e = 0; e < m; e++)
+            for (uint64_t j = 0; j < n_samples; j++) {
+                const char* from = static_cast<const char*>(a.c[c].ring) + (((first_tick + j * every - 1) % ring) * n + rows[e]) * row;
+                char* to = static_cast<char*>(out) + a.c[c].out_offset * elem + (e * n_samples + j) * row;
+                if (!need(live(from, row) && live(to, row), "ring or watch staging")) return launch(false);
+                std::memcpy(to, from, row);
+            }
+    }
+    return launch(true);
+}
+hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags, unsigned long long* count, hipStream_t) {
+    return launch(need(live(pos, n * 7 * elem) && live(vel, n * 6 * elem) && live(count, 8) && (!flags || live(flags, n)), "count_nonfinite buffers"));
+}
+
+// no HSA queue here: the host layer stays on its hipGraph / eager path
+namespace aql {
+Device* acquire(int, std::string* why) { return *why = "no HSA queue in the host-only build", nullptr; }
+void release(Device*) {}
+bool kernel_code(Device*, const void*, uint32_t, KernelCode*, std::string* why) { return *why = "no HSA queue", false; }
+bool run_chain(Device*, const Run*, size_t, double, double*, std::string* why) { return *why = "no HSA queue", false; }
+}  // namespace aql
+
+}  // namespace sixdof

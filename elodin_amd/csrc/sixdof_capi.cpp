@@ -28,6 +28,7 @@
 #include "../../include/sixdof_apollo.h"
 #include "kernels.hpp"
 #include "abi_guard.hpp"
+#include "device_mem.hpp"
 #include "aql_chain.hpp"
 #include "history_plan.hpp"
 #include "step_plan.hpp"
@@ -45,16 +46,22 @@ struct Column {
     size_t bytes = 0;
     std::vector<uint64_t> ids;
     void* host = nullptr;  // borrowed
-    void* dev = nullptr;   // owned: the full column, reference byte layout
+    DeviceBuffer dev;      // the full column, reference byte layout
     // join state: rows of this column that belong to the joined entity set, in joined order.  `live` is what
     // the kernels read and write: == dev when the column IS the joined set, else an owned compact [m,w] copy.
     std::vector<uint32_t> rows;
-    uint32_t* d_rows = nullptr;
-    void* compact = nullptr;
+    DeviceBuffer d_rows, compact;
     void* live = nullptr;
     bool joined = false;   // join resolved for the current binding
-    void* snap = nullptr;  // owned: device snapshot the async telemetry copy reads (sixdof_download_async)
-    bool host_pinned = false;   // host buffer page-locked by us (hipHostRegister)
+    DeviceBuffer snap;     // device snapshot the async telemetry copy reads (sixdof_download_async)
+    PinnedRange host_pinned;    // the host buffer, once page-locked by us
+
+    void drop_join() {
+        d_rows.reset(), compact.reset();
+        rows.clear();
+        live = nullptr;
+        joined = false;
+    }
 };
 
 thread_local std::string g_create_error;
@@ -77,7 +84,7 @@ struct FoldSlot {
     bool wave_ok = false;       // a plain sum that asked for waves: long sources go behind n_lane
     uint32_t count = 1, stride = 0;   // replicas the object was generated for (1, 0: none)
     bool set = false;
-    uint32_t* d_blob = nullptr;       // [src_rows | row_start | dst]
+    DeviceBuffer d_blob;              // [src_rows | row_start | dst]
     FoldTable table{};
 };
 using SetFoldTableFn = int (*)(unsigned, const FoldTable*);
@@ -105,7 +112,7 @@ struct Replay {
     aql::Device* aql_dev = nullptr;
     std::string aql_why;                    // why AQL setup failed (the hipGraph path then stays); not retried
     std::string aql_fault;                  // a chain failed on the queue: every later step fails with this
-    void* aql_args = nullptr;               // device arena of argument blocks (kAqlSlots)
+    DeviceBuffer aql_args;                  // device arena of argument blocks (kAqlSlots)
     std::map<uint64_t, aql::Run> aql_runs;  // by (state_only, accel_in_check, n_ticks): kernel, argument block, grid
     uint64_t aql_slot_key[kAqlSlots] = {};  // the run whose block each spare slot (kAqlSpare0 ..) holds, 0: none
     uint32_t aql_next_spare = kAqlSpare0;   // the spare slot the next new run takes
@@ -124,41 +131,102 @@ struct Replay {
     }
     void release() {
         drop();
-        if (aql_args && aql_fault.empty()) hipFree(aql_args);   // after a failed chain a dispatch may still read it
+        if (!aql_fault.empty()) (void)aql_args.release();   // leaked: after a failed chain a dispatch may still read it
+        aql_args.reset();
         aql::release(aql_dev);
     }
 };
 
+// What sixdof_set_edges replaces as one: built in a local, swapped in after the last call that can fail.
+struct Edges {
+    std::vector<uint32_t> src, dst;              // resolved rows, spawn order
+    DeviceBuffer d_csr_start, d_csr_dst;         // CSR by source, spawn order kept inside a source
+    // hub sources of the edge list (out-degree >= kHubDegree): one device block [hub_rows | hub_chunk_start | chunk_e0 | chunk_row]
+    DeviceBuffer d_hub, d_chunk_partial;
+    uint32_t n_hubs = 0, n_hub_chunks = 0;
+};
+
+// The telemetry ring.  reset() is the state without one: a ring is complete (every buffer allocated) or absent.
+struct History {
+    uint32_t ring = 0;
+    uint64_t first_tick = 0;          // first tick (1-based count) recorded since the ring was enabled
+    DeviceBuffer body[4];             // pos, vel, accel, force
+    std::vector<DeviceBuffer> model;  // one ring per component column of a generated program (same order as custom_model; empty: not recorded)
+    void reset() { *this = History{}; }
+};
+
+// The telemetry D2H lane that overlaps the compute stream: its stream and two events exist together or not at all.
+struct CopyLane {
+    Stream stream;
+    Event ev_snap, ev_copied;
+    bool pending = false;
+    uint64_t stream_lo = 0, stream_hi = 0;   // ticks of the history run whose copy may still be in flight
+    std::vector<PinnedRange> pinned_user;    // caller's buffers page-locked by sixdof_history_stream / sixdof_watch_read, until sixdof_sync
+    hipError_t ensure() {
+        if (stream) return hipSuccess;
+        Stream s;
+        Event a, b;
+        hipError_t e = hipStreamCreateWithFlags(s.out(), hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(a.out(), hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(b.out(), hipEventDisableTiming);
+        if (e != hipSuccess) return e;
+        stream = std::move(s), ev_snap = std::move(a), ev_copied = std::move(b);
+        return hipSuccess;
+    }
+    // page-lock once; if the range cannot be locked the copy still works, staged
+    void pin(void* p, size_t bytes) {
+        for (const PinnedRange& r : pinned_user)
+            if (r.get() == p) return;
+        PinnedRange r;
+        if (r.lock(p, bytes)) pinned_user.push_back(std::move(r));
+    }
+};
+
+// The Body archetype (six_dof.rs:152-159).  `ring`: index of the column's history ring (History::body), -1: not recorded.
+struct BodyCol {
+    const char* name;
+    uint64_t width;
+    uint32_t bit;   // SIXDOF_COL_*
+    int ring;
+    uint64_t id;
+};
+
+// entity id -> row
+using RowMap = std::unordered_map<uint64_t, uint32_t>;
+RowMap row_map(const std::vector<uint64_t>& ids) {
+    RowMap m;
+    m.reserve(ids.size() * 2);
+    for (size_t r = 0; r < ids.size(); r++) m.emplace(ids[r], static_cast<uint32_t>(r));
+    return m;
+}
+// rows[i] = row of ids[i]; returns n, or the index of the first id the map does not hold
+size_t resolve_rows(const RowMap& m, const uint64_t* ids, size_t n, std::vector<uint32_t>* rows) {
+    rows->resize(n);
+    for (size_t i = 0; i < n; i++) {
+        auto it = m.find(ids[i]);
+        if (it == m.end()) return i;
+        (*rows)[i] = it->second;
+    }
+    return n;
+}
+
 }  // namespace
 
+// Members are destroyed in reverse order: streams and events last, after everything that was used on them.
 struct sixdof_handle {
     sixdof_desc desc{};
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t evp0 = nullptr, evp1 = nullptr;  // the pair the PREVIOUS asynchronous step recorded (two pairs alternate)
+    Stream stream;
+    Event ev0, ev1;
+    Event evp0, evp1;  // the pair the PREVIOUS asynchronous step recorded (two pairs alternate)
     bool prev_pending = false;
-    hipStream_t copy_stream = nullptr;          // telemetry D2H, overlaps the compute stream
-    hipEvent_t ev_snap = nullptr, ev_copied = nullptr;
-    bool copy_pending = false;
-    uint64_t stream_lo = 0, stream_hi = 0;      // ticks of the history run whose copy may still be in flight
-    std::vector<void*> pinned_user;             // host buffers page-locked by sixdof_history_stream
+    CopyLane copy;
     bool step_pending = false;                  // SIXDOF_FLAG_ASYNC_STEP: ev1 of the last step not yet read
-    std::vector<hipEvent_t> launch_events;  // SIXDOF_FLAG_TIME_EACH_LAUNCH: 2 per launch
+    std::vector<Event> launch_events;  // SIXDOF_FLAG_TIME_EACH_LAUNCH: 2 per launch
     std::map<uint64_t, Column> cols;  // ascending ComponentId = reference BTreeMap order
     std::vector<sixdof_effector_op> ops;
-    // edges
-    std::vector<uint32_t> edge_src, edge_dst;       // resolved rows, spawn order
-    std::vector<uint32_t> csr_start, csr_dst;       // by source, spawn order kept inside a source
-    uint32_t* d_csr_start = nullptr;
-    uint32_t* d_csr_dst = nullptr;
-    // hub sources of the edge list (out-degree >= kHubDegree): one device block [hub_rows | hub_chunk_start | chunk_e0 | chunk_row]
-    uint32_t* d_hub = nullptr;
-    double* d_chunk_partial = nullptr;
-    uint32_t n_hubs = 0, n_hub_chunks = 0;
-    // pair-path scratch
-    void* d_scratch = nullptr;
-    size_t scratch_bytes = 0;
+    Edges edges;
+    DeviceBuffer d_scratch;            // pair-path scratch
     std::vector<uint64_t> joined_ids;  // intersection of the Body columns' entity ids (query.rs:136-208)
     bool identity_join = true;         // every Body column already is the joined set (query.rs:673,702 fast path)
     uint64_t tick = 0;
@@ -166,9 +234,9 @@ struct sixdof_handle {
     bool resident = false;             // columns uploaded at least once since the last bind
     sixdof_timings last{};   // most recent upload / step / download
     // run-time generated effector pipe
-    void* custom_dl = nullptr;
+    DlHandle custom_dl;
     CustomLaunchFn custom_launch = nullptr;
-    void* pair_dl = nullptr;               // generated edge_fold function (sixdof_set_custom_pair)
+    DlHandle pair_dl;                      // generated edge_fold function (sixdof_set_custom_pair)
     CustomPairLaunchFn pair_launch = nullptr;
     std::vector<uint64_t> custom_aux;      // read-only [n,1..3] columns of a generated effector pipe
     std::vector<uint64_t> custom_model;    // read/write [n,1..16] component columns of a generated program
@@ -178,20 +246,15 @@ struct sixdof_handle {
     // fold stages of a generated program that reads its edges from device memory (empty: none, or a baked object)
     SetFoldTableFn custom_set_fold_table = nullptr;
     std::vector<FoldSlot> custom_folds;
-    // telemetry ring
-    uint32_t hist_ring = 0;
-    uint64_t hist_first_tick = 0;   // first tick (1-based count) recorded since the ring was enabled
-    void* d_hist[4] = {nullptr, nullptr, nullptr, nullptr};  // pos, vel, accel, force
-    std::vector<void*> d_model_hist;      // one ring per component column of a generated program (same order as custom_model)
+    History hist;
     std::vector<unsigned> custom_model_width;   // what the generated code expects per column (0 = unknown), bit 31 = window
     // watch list (sixdof_set_watch): the components and joined rows whose series sixdof_watch_read gathers out of the ring.
     // Only ids and rows are kept: ring base pointers and widths are looked up per read, so the ring may come, go or be
     // re-sized in between.
     std::vector<uint64_t> watch_ids;
-    uint32_t* d_watch_rows = nullptr;
+    DeviceBuffer d_watch_rows;
     size_t watch_m = 0;
-    void* d_watch_stage = nullptr;        // device staging of one read, grown lazily
-    size_t watch_stage_bytes = 0;
+    DeviceBuffer d_watch_stage;           // device staging of one read, grown lazily
     // rollout model (0 = none, 1 = Apollo lander)
     int model = 0;
     std::vector<double> ap_time, ap_alt, ap_rate, ap_pitch, ap_hspeed, ap_downrange;
@@ -199,12 +262,14 @@ struct sixdof_handle {
     uint32_t ap_ticks_per_telemetry = 3;
     uint32_t ap_guidance_period = 5;
     uint64_t ap_max_ticks = 0;
-    double* d_tick_refs = nullptr;
-    size_t tick_refs_cap = 0;
+    DeviceBuffer d_tick_refs;
     Replay replay;
     std::string path;                       // sixdof_step_path's answer
     mutable std::string err;
 
+    BodyCol body[5] = {{"world_pos", 7, SIXDOF_COL_WORLD_POS, 0, 0},     {"world_vel", 6, SIXDOF_COL_WORLD_VEL, 1, 0},
+                       {"world_accel", 6, SIXDOF_COL_WORLD_ACCEL, 2, 0}, {"force", 6, SIXDOF_COL_FORCE, 3, 0},
+                       {"inertia", 7, SIXDOF_COL_INERTIA, -1, 0}};
     uint64_t id_pos, id_vel, id_accel, id_force, id_inertia, id_tick, id_dt;
 
     int fail(int code, const std::string& msg) const {
@@ -225,23 +290,9 @@ struct sixdof_handle {
     }
     size_t elem_size() const { return desc.dtype == SIXDOF_F32 ? 4 : 8; }
     int state_prim() const { return desc.dtype == SIXDOF_F32 ? SIXDOF_PRIM_F32 : SIXDOF_PRIM_F64; }
-    void free_join(Column& c) {
-        if (c.d_rows) hipFree(c.d_rows), c.d_rows = nullptr;
-        if (c.compact) hipFree(c.compact), c.compact = nullptr;
-        c.rows.clear();
-        c.live = nullptr;
-        c.joined = false;
-    }
-    // the tables of the installed program's fold stages; the caller has drained the stream
-    void free_fold_tables() {
-        for (FoldSlot& f : custom_folds)
-            if (f.d_blob) hipFree(f.d_blob);
-        custom_folds.clear();
-        custom_set_fold_table = nullptr;
-    }
     // the caller has drained the compute stream (a gather may still read the table)
     void drop_watch() {
-        if (d_watch_rows) hipFree(d_watch_rows), d_watch_rows = nullptr;
+        d_watch_rows.reset();
         watch_ids.clear();
         watch_m = 0;
     }
@@ -267,28 +318,45 @@ static int resolve_join(sixdof_handle* h, Column* c) {
     if (c->joined) return SIXDOF_OK;
     const size_t m = h->joined_ids.size();
     if (c->ids == h->joined_ids) {
-        c->live = c->dev;
+        c->live = c->dev.get();
         c->joined = true;
         return SIXDOF_OK;
     }
-    std::unordered_map<uint64_t, uint32_t> row_of;
-    row_of.reserve(c->ids.size() * 2);
-    for (size_t r = 0; r < c->ids.size(); r++) row_of.emplace(c->ids[r], static_cast<uint32_t>(r));
-    c->rows.resize(m);
-    for (size_t j = 0; j < m; j++) {
-        auto it = row_of.find(h->joined_ids[j]);
-        if (it == row_of.end())
-            return h->fail(SIXDOF_ERR_ENTITY_MISMATCH, "join: a column does not cover the joined Body entity set");
-        c->rows[j] = it->second;
-    }
+    std::vector<uint32_t> rows;
+    if (resolve_rows(row_map(c->ids), h->joined_ids.data(), m, &rows) != m)
+        return h->fail(SIXDOF_ERR_ENTITY_MISMATCH, "join: a column does not cover the joined Body entity set");
+    DeviceBuffer d_rows, compact;
     if (m) {
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&c->d_rows), m * sizeof(uint32_t)));
-        HIP_TRY(h, hipMemcpy(c->d_rows, c->rows.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMalloc(&c->compact, m * c->width * c->elem));
+        HIP_TRY(h, d_rows.alloc(m * sizeof(uint32_t)));
+        HIP_TRY(h, hipMemcpy(d_rows.get(), rows.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, compact.alloc(m * c->width * c->elem));
     }
-    c->live = c->compact;
+    c->rows.swap(rows);
+    c->d_rows = std::move(d_rows), c->compact = std::move(compact);
+    c->live = c->compact.get();
     c->joined = true;
     return SIXDOF_OK;
+}
+
+// the joined rows of a column whose full copy changed (an upload): full column -> compact copy, on the compute stream
+static int gather_joined(sixdof_handle* h, Column* c) {
+    if (!c->joined || !c->compact) return SIXDOF_OK;
+    hipError_t e = launch_gather_rows(c->compact.get(), c->dev.get(), c->d_rows.get<uint32_t>(), static_cast<uint32_t>(h->joined_ids.size()),
+                                      static_cast<uint32_t>(c->width), c->elem, h->stream.get());
+    return e == hipSuccess ? SIXDOF_OK : h->hip_fail(e, "gather_rows");
+}
+
+// first use of a column after binding: join it onto the Body set and bring its rows over
+static int ensure_joined(sixdof_handle* h, Column* c) {
+    if (c->joined) return SIXDOF_OK;
+    int rc = resolve_join(h, c);
+    return rc != SIXDOF_OK ? rc : gather_joined(h, c);
+}
+
+// H2D of one column, then the gather of its joined rows: enqueued, the caller waits for the compute stream
+static int upload_one(sixdof_handle* h, Column* c) {
+    if (c->bytes) HIP_TRY(h, hipMemcpyAsync(c->dev.get(), c->host, c->bytes, hipMemcpyHostToDevice, h->stream.get()));
+    return gather_joined(h, c);
 }
 
 extern "C" {
@@ -349,16 +417,14 @@ int sixdof_create(const sixdof_desc* d, sixdof_handle** out) try {
     const char* so_env = std::getenv("SIXDOF_STATE_ONLY");   // "0": every launch stores world_accel and force (A/B runs, tests)
     h->replay.state_only_off = so_env && so_env[0] == '0';
     h->device = d->device_ordinal;
-    h->id_pos = cid("world_pos");
-    h->id_vel = cid("world_vel");
-    h->id_accel = cid("world_accel");
-    h->id_force = cid("force");
-    h->id_inertia = cid("inertia");
+    for (BodyCol& b : h->body) b.id = cid(b.name);
+    h->id_pos = h->body[0].id, h->id_vel = h->body[1].id, h->id_accel = h->body[2].id, h->id_force = h->body[3].id;
+    h->id_inertia = h->body[4].id;
     h->id_tick = cid("tick");
     h->id_dt = cid("simulation_time_step");
-    if ((e = hipSetDevice(h->device)) != hipSuccess || (e = hipStreamCreate(&h->stream)) != hipSuccess ||
-        (e = hipEventCreate(&h->ev0)) != hipSuccess || (e = hipEventCreate(&h->ev1)) != hipSuccess ||
-        (e = hipEventCreate(&h->evp0)) != hipSuccess || (e = hipEventCreate(&h->evp1)) != hipSuccess) {
+    if ((e = hipSetDevice(h->device)) != hipSuccess || (e = hipStreamCreate(h->stream.out())) != hipSuccess ||
+        (e = hipEventCreate(h->ev0.out())) != hipSuccess || (e = hipEventCreate(h->ev1.out())) != hipSuccess ||
+        (e = hipEventCreate(h->evp0.out())) != hipSuccess || (e = hipEventCreate(h->evp1.out())) != hipSuccess) {
         g_create_error = std::string("sixdof_create: ") + hipGetErrorString(e);
         sixdof_destroy(h);   // releases whatever part was created
         return SIXDOF_ERR_BACKEND;
@@ -370,47 +436,19 @@ int sixdof_create(const sixdof_desc* d, sixdof_handle** out) try {
 void sixdof_destroy(sixdof_handle* h) try {
     if (!h) return;
     hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
+    if (h->stream) hipStreamSynchronize(h->stream.get());
+    if (h->copy.stream) hipStreamSynchronize(h->copy.stream.get());
     h->replay.release();
-    if (h->copy_stream) hipStreamSynchronize(h->copy_stream);
-    for (auto& kv : h->cols) {
-        h->free_join(kv.second);
-        if (kv.second.dev) hipFree(kv.second.dev);
-        if (kv.second.snap) hipFree(kv.second.snap);
-        if (kv.second.host_pinned) hipHostUnregister(kv.second.host);
-    }
-    for (void* p : h->pinned_user) (void)hipHostUnregister(p);
-    if (h->copy_stream) hipStreamDestroy(h->copy_stream);
-    if (h->ev_snap) hipEventDestroy(h->ev_snap);
-    if (h->ev_copied) hipEventDestroy(h->ev_copied);
-    if (h->d_csr_start) hipFree(h->d_csr_start);
-    if (h->d_csr_dst) hipFree(h->d_csr_dst);
-    if (h->d_hub) hipFree(h->d_hub);
-    if (h->d_chunk_partial) hipFree(h->d_chunk_partial);
-    if (h->d_scratch) hipFree(h->d_scratch);
-    if (h->d_tick_refs) hipFree(h->d_tick_refs);
-    h->free_fold_tables();
-    for (void* p : h->d_hist) if (p) hipFree(p);
-    for (void* p : h->d_model_hist) if (p) hipFree(p);
-    h->drop_watch();
-    if (h->d_watch_stage) hipFree(h->d_watch_stage);
-    if (h->custom_dl) dlclose(h->custom_dl);
-    if (h->pair_dl) dlclose(h->pair_dl);
-    for (hipEvent_t e : h->launch_events) hipEventDestroy(e);
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
-    if (h->evp0) hipEventDestroy(h->evp0);
-    if (h->evp1) hipEventDestroy(h->evp1);
-    if (h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // the owners release the rest (device_mem.hpp), in reverse order of declaration
 } SIXDOF_ABI_CATCH_VALUE(err_of(h), )
 
 int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_cols) try {
     if (!h || (!cols && n_cols)) return SIXDOF_ERR_INVALID_ARGUMENT;
+    h->bound = h->resident = false;   // until the end of this call: a failed bind leaves the handle unbound
     HIP_TRY(h, hipSetDevice(h->device));
     h->replay.drop();
     if (h->d_watch_rows) {      // a watch holds rows of the join this call replaces
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
         h->drop_watch();
     }
     for (size_t i = 0; i < n_cols; i++) {
@@ -426,30 +464,20 @@ int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_co
         col.bytes = static_cast<size_t>(col.width * col.n_rows) * col.elem;
         col.host = c.host_ptr;
         if (c.entity_ids) col.ids.assign(c.entity_ids, c.entity_ids + c.n_rows);
-        Column* old = h->col(c.component_id);
-        if (old) {
-            h->free_join(*old);
-            if (old->dev) {
-                if (old->bytes == col.bytes) col.dev = old->dev;
-                else hipFree(old->dev);
-            }
-            // async-commit state of the previous binding: the snapshot is sized per binding, the page lock belongs to
-            // the previous host buffer
-            if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-            if (old->snap) hipFree(old->snap);
-            if (old->host_pinned) (void)hipHostUnregister(old->host);
+        if (Column* old = h->col(c.component_id)) {
+            if (old->bytes == col.bytes) col.dev = std::move(old->dev);
+            // the copy lane may still read the previous binding's snapshot and write its (page-locked) host buffer
+            if (h->copy.stream) HIP_TRY(h, hipStreamSynchronize(h->copy.stream.get()));
         }
-        if (!col.dev && col.bytes) HIP_TRY(h, hipMalloc(&col.dev, col.bytes));
+        if (!col.dev && col.bytes) HIP_TRY(h, col.dev.alloc(col.bytes));
+        // the previous binding's join tables, snapshot (sized per binding) and page lock (of its host buffer) go with its entry
         h->cols[c.component_id] = std::move(col);
     }
-    // The Body archetype (six_dof.rs:152-159): five columns.  six_dof's queries run over the INTERSECTION of
-    // their entity ids in ascending id order (query.rs:136-208); rows outside it are never touched.
-    const struct { uint64_t id; uint64_t width; const char* name; } body[5] = {
-        {h->id_pos, 7, "world_pos"}, {h->id_vel, 6, "world_vel"}, {h->id_accel, 6, "world_accel"},
-        {h->id_force, 6, "force"},   {h->id_inertia, 7, "inertia"}};
+    // six_dof's queries run over the INTERSECTION of the Body columns' entity ids in ascending id order
+    // (query.rs:136-208); rows outside it are never touched.
     const Column* first = nullptr;
     bool identical = true;
-    for (auto& b : body) {
+    for (auto& b : h->body) {
         const Column* c = h->col(b.id);
         if (!c) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, std::string("bind_columns: missing Body column ") + b.name);
         if (c->prim != h->state_prim())
@@ -466,7 +494,7 @@ int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_co
     } else {
         std::vector<uint64_t> acc(first->ids);
         std::sort(acc.begin(), acc.end());
-        for (auto& b : body) {
+        for (auto& b : h->body) {
             std::vector<uint64_t> ids(h->col(b.id)->ids), out;
             std::sort(ids.begin(), ids.end());
             std::set_intersection(acc.begin(), acc.end(), ids.begin(), ids.end(), std::back_inserter(out));
@@ -482,13 +510,12 @@ int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_co
                        " consecutive rows; the joined " + std::to_string(h->desc.n_entities) + " rows are not a whole number of worlds");
     if (h->joined_ids.size() != h->desc.n_entities)
         return h->fail(SIXDOF_ERR_VALUE_SIZE_MISMATCH, "bind_columns: n_entities does not match the joined Body entity set");
-    for (auto& kv : h->cols) h->free_join(kv.second);
-    for (auto& b : body) {
+    for (auto& kv : h->cols) kv.second.drop_join();
+    for (auto& b : h->body) {
         int rc = resolve_join(h, h->col(b.id));
         if (rc != SIXDOF_OK) return rc;
     }
     h->bound = true;
-    h->resident = false;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -536,17 +563,11 @@ int sixdof_set_edges(sixdof_handle* h, const uint64_t* from_ids, const uint64_t*
     if (!h || ((!from_ids || !to_ids) && n_edges)) return SIXDOF_ERR_INVALID_ARGUMENT;
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_edges: bind Body columns first");
     HIP_TRY(h, hipSetDevice(h->device));
-    std::unordered_map<uint64_t, uint32_t> row_of;   // entity id -> row of the joined Body set
-    row_of.reserve(h->joined_ids.size() * 2);
-    for (size_t r = 0; r < h->joined_ids.size(); r++) row_of.emplace(h->joined_ids[r], static_cast<uint32_t>(r));
-    std::vector<uint32_t> src(n_edges), dst(n_edges);
-    for (size_t e = 0; e < n_edges; e++) {
-        auto a = row_of.find(from_ids[e]), b = row_of.find(to_ids[e]);
-        if (a == row_of.end() || b == row_of.end())
-            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_edges: edge endpoint is not a Body entity");
-        src[e] = a->second;
-        dst[e] = b->second;
-    }
+    Edges ne;   // swapped in at the end: a failed call leaves the handle's edges as they were
+    std::vector<uint32_t>&src = ne.src, &dst = ne.dst;
+    const RowMap row_of = row_map(h->joined_ids);
+    if (resolve_rows(row_of, from_ids, n_edges, &src) != n_edges || resolve_rows(row_of, to_ids, n_edges, &dst) != n_edges)
+        return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_edges: edge endpoint is not a Body entity");
     const uint32_t n = static_cast<uint32_t>(h->desc.n_entities);
     // CSR by source; a stable counting sort keeps each source's out-edges in spawn order, which is
     // the fold order of GraphQuery::edge_fold (graph.rs:113-175,239-361)
@@ -555,17 +576,13 @@ int sixdof_set_edges(sixdof_handle* h, const uint64_t* from_ids, const uint64_t*
     for (uint32_t i = 0; i < n; i++) start[i + 1] += start[i];
     std::vector<uint32_t> cursor(start.begin(), start.end() - 1);
     for (size_t e = 0; e < n_edges; e++) cdst[cursor[src[e]]++] = dst[e];
-    if (h->d_csr_start) hipFree(h->d_csr_start), h->d_csr_start = nullptr;
-    if (h->d_csr_dst) hipFree(h->d_csr_dst), h->d_csr_dst = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_csr_start), (n + 1) * sizeof(uint32_t)));
-    HIP_TRY(h, hipMemcpy(h->d_csr_start, start.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(h, ne.d_csr_start.alloc((n + 1) * sizeof(uint32_t)));
+    HIP_TRY(h, hipMemcpy(ne.d_csr_start.get(), start.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (n_edges) {
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_csr_dst), n_edges * sizeof(uint32_t)));
-        HIP_TRY(h, hipMemcpy(h->d_csr_dst, cdst.data(), n_edges * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, ne.d_csr_dst.alloc(n_edges * sizeof(uint32_t)));
+        HIP_TRY(h, hipMemcpy(ne.d_csr_dst.get(), cdst.data(), n_edges * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     // hub sources: the fold kernels give them whole waves (pair_kernel.hpp 2c)
-    if (h->d_hub) hipFree(h->d_hub), h->d_hub = nullptr;
-    if (h->d_chunk_partial) hipFree(h->d_chunk_partial), h->d_chunk_partial = nullptr;
     std::vector<uint32_t> hub_rows, hub_chunk_start{0}, chunk_e0, chunk_row;
     const char* no_hubs = std::getenv("SIXDOF_NO_HUBS");   // A/B knob: "1" folds every source with one lane
     for (uint32_t i = 0; i < n && !(no_hubs && no_hubs[0] == '1'); i++) {
@@ -578,22 +595,19 @@ int sixdof_set_edges(sixdof_handle* h, const uint64_t* from_ids, const uint64_t*
         }
         hub_chunk_start.push_back(static_cast<uint32_t>(chunk_e0.size()));
     }
-    h->n_hubs = static_cast<uint32_t>(hub_rows.size());
-    h->n_hub_chunks = static_cast<uint32_t>(chunk_e0.size());
-    if (h->n_hubs) {
+    ne.n_hubs = static_cast<uint32_t>(hub_rows.size());
+    ne.n_hub_chunks = static_cast<uint32_t>(chunk_e0.size());
+    if (ne.n_hubs) {
         std::vector<uint32_t> blob;
         blob.insert(blob.end(), hub_rows.begin(), hub_rows.end());
         blob.insert(blob.end(), hub_chunk_start.begin(), hub_chunk_start.end());
         blob.insert(blob.end(), chunk_e0.begin(), chunk_e0.end());
         blob.insert(blob.end(), chunk_row.begin(), chunk_row.end());
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_hub), blob.size() * sizeof(uint32_t)));
-        HIP_TRY(h, hipMemcpy(h->d_hub, blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_chunk_partial), static_cast<size_t>(h->n_hub_chunks) * kPartialWidth * sizeof(double)));
+        HIP_TRY(h, ne.d_hub.alloc(blob.size() * sizeof(uint32_t)));
+        HIP_TRY(h, hipMemcpy(ne.d_hub.get(), blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(h, ne.d_chunk_partial.alloc(static_cast<size_t>(ne.n_hub_chunks) * kPartialWidth * sizeof(double)));
     }
-    h->edge_src.swap(src);
-    h->edge_dst.swap(dst);
-    h->csr_start.swap(start);
-    h->csr_dst.swap(cdst);
+    std::swap(h->edges, ne);   // the previous tables are freed as `ne` goes
     h->replay.drop();
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
@@ -613,10 +627,10 @@ int sixdof_get_join_rows(const sixdof_handle* h, uint64_t component_id, uint32_t
 
 int sixdof_get_edge_rows(const sixdof_handle* h, uint32_t* src_rows, uint32_t* dst_rows, size_t cap, size_t* n_out) try {
     if (!h || !n_out) return SIXDOF_ERR_INVALID_ARGUMENT;
-    *n_out = h->edge_src.size();
-    if (cap < h->edge_src.size()) return h->fail(SIXDOF_ERR_VALUE_SIZE_MISMATCH, "get_edge_rows: buffer too small");
-    if (src_rows) std::memcpy(src_rows, h->edge_src.data(), h->edge_src.size() * sizeof(uint32_t));
-    if (dst_rows) std::memcpy(dst_rows, h->edge_dst.data(), h->edge_dst.size() * sizeof(uint32_t));
+    *n_out = h->edges.src.size();
+    if (cap < h->edges.src.size()) return h->fail(SIXDOF_ERR_VALUE_SIZE_MISMATCH, "get_edge_rows: buffer too small");
+    if (src_rows) std::memcpy(src_rows, h->edges.src.data(), h->edges.src.size() * sizeof(uint32_t));
+    if (dst_rows) std::memcpy(dst_rows, h->edges.dst.data(), h->edges.dst.size() * sizeof(uint32_t));
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -627,16 +641,9 @@ int sixdof_upload(sixdof_handle* h) try {
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "upload: no columns bound");
     HIP_TRY(h, hipSetDevice(h->device));
     const double t_up = now_ms();
-    for (auto& kv : h->cols) {
-        Column& c = kv.second;
-        if (c.bytes) HIP_TRY(h, hipMemcpyAsync(c.dev, c.host, c.bytes, hipMemcpyHostToDevice, h->stream));
-        if (c.joined && c.compact) {
-            hipError_t e = launch_gather_rows(c.compact, c.dev, c.d_rows, static_cast<uint32_t>(h->joined_ids.size()),
-                                              static_cast<uint32_t>(c.width), c.elem, h->stream);
-            if (e != hipSuccess) return h->hip_fail(e, "gather_rows");
-        }
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (auto& kv : h->cols)
+        if (int rc = upload_one(h, &kv.second); rc != SIXDOF_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
     h->last.h2d_upload_ms = now_ms() - t_up;
     h->resident = true;
     h->accel_is_host_data = true;
@@ -646,8 +653,8 @@ int sixdof_upload(sixdof_handle* h) try {
 // joined rows -> their places in the full column (before any D2H of that column)
 static int scatter_back(sixdof_handle* h, Column* c) {
     if (c->joined && c->compact) {
-        hipError_t e = launch_scatter_rows(c->dev, c->compact, c->d_rows, static_cast<uint32_t>(h->joined_ids.size()),
-                                           static_cast<uint32_t>(c->width), c->elem, h->stream);
+        hipError_t e = launch_scatter_rows(c->dev.get(), c->compact.get(), c->d_rows.get<uint32_t>(), static_cast<uint32_t>(h->joined_ids.size()),
+                                           static_cast<uint32_t>(c->width), c->elem, h->stream.get());
         if (e != hipSuccess) return h->hip_fail(e, "scatter_rows");
     }
     return SIXDOF_OK;
@@ -658,20 +665,15 @@ int sixdof_download(sixdof_handle* h, uint32_t mask) try {
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "download: no columns bound");
     HIP_TRY(h, hipSetDevice(h->device));
     const double t_dn = now_ms();
-    const struct { uint32_t bit; uint64_t id; } sel[5] = {{SIXDOF_COL_WORLD_POS, h->id_pos},
-                                                        {SIXDOF_COL_WORLD_VEL, h->id_vel},
-                                                        {SIXDOF_COL_WORLD_ACCEL, h->id_accel},
-                                                        {SIXDOF_COL_FORCE, h->id_force},
-                                                        {SIXDOF_COL_INERTIA, h->id_inertia}};
-    for (auto& s : sel) {
-        if (!(mask & s.bit)) continue;
-        Column* c = h->col(s.id);
+    for (auto& b : h->body) {
+        if (!(mask & b.bit)) continue;
+        Column* c = h->col(b.id);
         if (!c) continue;
         int rc = scatter_back(h, c);
         if (rc != SIXDOF_OK) return rc;
-        if (c->bytes) HIP_TRY(h, hipMemcpyAsync(c->host, c->dev, c->bytes, hipMemcpyDeviceToHost, h->stream));
+        if (c->bytes) HIP_TRY(h, hipMemcpyAsync(c->host, c->dev.get(), c->bytes, hipMemcpyDeviceToHost, h->stream.get()));
     }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
     h->last.d2h_download_ms = now_ms() - t_dn;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
@@ -680,49 +682,38 @@ int sixdof_download_async(sixdof_handle* h, uint32_t mask) try {
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "download_async: no columns bound");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->copy_stream) {
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_snap, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied, hipEventDisableTiming));
-    }
-    const struct { uint32_t bit; uint64_t id; } sel[5] = {{SIXDOF_COL_WORLD_POS, h->id_pos},
-                                                        {SIXDOF_COL_WORLD_VEL, h->id_vel},
-                                                        {SIXDOF_COL_WORLD_ACCEL, h->id_accel},
-                                                        {SIXDOF_COL_FORCE, h->id_force},
-                                                        {SIXDOF_COL_INERTIA, h->id_inertia}};
+    CopyLane& lane = h->copy;
+    HIP_TRY(h, lane.ensure());
     // the previous copy must have drained the snapshot buffers before they are overwritten (device-side wait)
-    if (h->copy_pending) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied, 0));
+    if (lane.pending) HIP_TRY(h, hipStreamWaitEvent(h->stream.get(), lane.ev_copied.get(), 0));
     Column* picked[5];
     int n_picked = 0;
-    for (auto& s : sel) {
-        if (!(mask & s.bit)) continue;
-        Column* c = h->col(s.id);
+    for (auto& b : h->body) {
+        if (!(mask & b.bit)) continue;
+        Column* c = h->col(b.id);
         if (!c || !c->bytes) continue;
         int rc = scatter_back(h, c);
         if (rc != SIXDOF_OK) return rc;
-        if (!c->snap) HIP_TRY(h, hipMalloc(&c->snap, c->bytes));
-        HIP_TRY(h, hipMemcpyAsync(c->snap, c->dev, c->bytes, hipMemcpyDeviceToDevice, h->stream));
-        if (!c->host_pinned) {   // page-lock once; if the range cannot be locked the copy below still works, staged
-            if (hipHostRegister(c->host, c->bytes, hipHostRegisterDefault) == hipSuccess) c->host_pinned = true;
-            else (void)hipGetLastError();
-        }
+        if (!c->snap) HIP_TRY(h, c->snap.alloc(c->bytes));
+        HIP_TRY(h, hipMemcpyAsync(c->snap.get(), c->dev.get(), c->bytes, hipMemcpyDeviceToDevice, h->stream.get()));
+        if (!c->host_pinned) c->host_pinned.lock(c->host, c->bytes);   // once; an unlockable range is copied staged
         picked[n_picked++] = c;
     }
-    HIP_TRY(h, hipEventRecord(h->ev_snap, h->stream));
-    HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->ev_snap, 0));
+    HIP_TRY(h, hipEventRecord(lane.ev_snap.get(), h->stream.get()));
+    HIP_TRY(h, hipStreamWaitEvent(lane.stream.get(), lane.ev_snap.get(), 0));
     for (int k = 0; k < n_picked; k++)
-        HIP_TRY(h, hipMemcpyAsync(picked[k]->host, picked[k]->snap, picked[k]->bytes, hipMemcpyDeviceToHost, h->copy_stream));
-    HIP_TRY(h, hipEventRecord(h->ev_copied, h->copy_stream));
-    h->copy_pending = true;
+        HIP_TRY(h, hipMemcpyAsync(picked[k]->host, picked[k]->snap.get(), picked[k]->bytes, hipMemcpyDeviceToHost, lane.stream.get()));
+    HIP_TRY(h, hipEventRecord(lane.ev_copied.get(), lane.stream.get()));
+    lane.pending = true;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
 int sixdof_download_wait(sixdof_handle* h) try {
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
-    if (!h->copy_pending) return SIXDOF_OK;
+    if (!h->copy.pending) return SIXDOF_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const double t0 = now_ms();
-    HIP_TRY(h, hipEventSynchronize(h->ev_copied));
+    HIP_TRY(h, hipEventSynchronize(h->copy.ev_copied.get()));
     h->last.d2h_download_ms = now_ms() - t0;     // the part of the copy the host actually waited for
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
@@ -730,16 +721,15 @@ int sixdof_download_wait(sixdof_handle* h) try {
 int sixdof_sync(sixdof_handle* h) try {
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->copy_stream) HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
+    if (h->copy.stream) HIP_TRY(h, hipStreamSynchronize(h->copy.stream.get()));
     float ms0 = 0.f;
-    if (h->step_pending && hipEventElapsedTime(&ms0, h->ev0, h->ev1) == hipSuccess) h->last.kernel_device_ms = ms0;
+    if (h->step_pending && hipEventElapsedTime(&ms0, h->ev0.get(), h->ev1.get()) == hipSuccess) h->last.kernel_device_ms = ms0;
     h->step_pending = h->prev_pending = false;
-    h->copy_pending = false;
-    h->stream_lo = 1, h->stream_hi = 0;
+    h->copy.pending = false;
+    h->copy.stream_lo = 1, h->copy.stream_hi = 0;
     // page locks taken on the caller's history buffers end here: the caller may free them after sixdof_sync
-    for (void* p : h->pinned_user) (void)hipHostUnregister(p);
-    h->pinned_user.clear();
+    h->copy.pinned_user.clear();
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -751,7 +741,7 @@ int sixdof_get_tick(const sixdof_handle* h, uint64_t* tick) try {
 int sixdof_set_tick(sixdof_handle* h, uint64_t tick) try {
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
     h->tick = tick;
-    h->hist_first_tick = tick + 1;
+    h->hist.first_tick = tick + 1;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 int sixdof_set_ticks_per_launch(sixdof_handle* h, uint32_t k) try {
@@ -770,9 +760,9 @@ int sixdof_set_flags(sixdof_handle* h, uint32_t flags) try {
 void* sixdof_device_column(sixdof_handle* h, uint64_t component_id) try {
     if (!h) return nullptr;
     Column* c = h->col(component_id);
-    return c ? (c->live ? c->live : c->dev) : nullptr;
+    return c ? (c->live ? c->live : c->dev.get()) : nullptr;
 } SIXDOF_ABI_CATCH_VALUE(err_of(h), nullptr)
-void* sixdof_stream(sixdof_handle* h) { return h ? static_cast<void*>(h->stream) : nullptr; }
+void* sixdof_stream(sixdof_handle* h) { return h ? static_cast<void*>(h->stream.get()) : nullptr; }
 
 }  // extern "C"
 
@@ -793,15 +783,7 @@ int build_dev_ops(sixdof_handle* h, DevOp* out, uint32_t* n_out, uint32_t* vel_i
             if (!c) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "step: column read by the generated pipe is not bound");
             if (c->width < 1 || c->width > 3 || c->prim != h->state_prim())
                 return h->fail(SIXDOF_ERR_VALUE_SIZE_MISMATCH, "step: generated-pipe columns must be [n,1..3] of the state dtype");
-            if (!c->joined) {
-                int rc = resolve_join(h, c);
-                if (rc != SIXDOF_OK) return rc;
-                if (c->compact) {
-                    hipError_t e = launch_gather_rows(c->compact, c->dev, c->d_rows, static_cast<uint32_t>(h->joined_ids.size()),
-                                                      static_cast<uint32_t>(c->width), c->elem, h->stream);
-                    if (e != hipSuccess) return h->hip_fail(e, "gather_rows");
-                }
-            }
+            if (int rc = ensure_joined(h, c); rc != SIXDOF_OK) return rc;
             DevOp d{};
             d.aux = c->live;
             d.aux_width = static_cast<int32_t>(c->width);
@@ -823,14 +805,7 @@ int build_dev_ops(sixdof_handle* h, DevOp* out, uint32_t* n_out, uint32_t* vel_i
             // them never read DevOp::aux_width, which stays 0 here (step_kernel.hpp, kAuxRows3)
             if (c->width != 3 || c->prim != h->state_prim())
                 return h->fail(SIXDOF_ERR_VALUE_SIZE_MISMATCH, "step: effector aux column must be [n,3] of the state dtype");
-            if (!c->joined) {   // first use after binding: join it onto the Body set and bring its rows over
-                int rc = resolve_join(h, c);
-                if (rc != SIXDOF_OK) return rc;
-                if (c->compact) {
-                    hipError_t e = launch_gather_rows(c->compact, c->dev, c->d_rows, static_cast<uint32_t>(h->joined_ids.size()), 3, c->elem, h->stream);
-                    if (e != hipSuccess) return h->hip_fail(e, "gather_rows");
-                }
-            }
+            if (int rc = ensure_joined(h, c); rc != SIXDOF_OK) return rc;
             d.aux = c->live;
         }
         if (o.kind == SIXDOF_EFF_BALL_DRAG) *vel_independent = 0;
@@ -880,12 +855,12 @@ int fill_step_params(sixdof_handle* h, StepParams* P) {
 #endif
     }
     P->streaming = policy;
-    P->hist_ring = h->hist_ring;
-    if (h->hist_ring) {
-        P->hist_pos = h->d_hist[0];
-        P->hist_vel = h->d_hist[1];
-        P->hist_accel = h->d_hist[2];
-        P->hist_force = h->d_hist[3];
+    P->hist_ring = h->hist.ring;
+    if (h->hist.ring) {
+        P->hist_pos = h->hist.body[0].get();
+        P->hist_vel = h->hist.body[1].get();
+        P->hist_accel = h->hist.body[2].get();
+        P->hist_force = h->hist.body[3].get();
     }
     for (size_t k = 0; k < h->custom_model.size(); k++) {
         Column* c = h->col(h->custom_model[k]);
@@ -900,17 +875,13 @@ int fill_step_params(sixdof_handle* h, StepParams* P) {
         if (!c->joined) {
             int rc = resolve_join(h, c);
             if (rc != SIXDOF_OK) return rc;
-            if (c->compact) {
-                if ((expect >> 29) & 1u)      // the gather / scatter kernels move [n,w] rows
-                    return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: a program built for element-major columns needs every column on "
-                                                           "the executor's own entity set (no entity-set join)");
-                hipError_t e = launch_gather_rows(c->compact, c->dev, c->d_rows, static_cast<uint32_t>(h->joined_ids.size()),
-                                                  static_cast<uint32_t>(c->width), c->elem, h->stream);
-                if (e != hipSuccess) return h->hip_fail(e, "gather_rows");
-            }
+            if (c->compact && ((expect >> 29) & 1u))      // the gather / scatter kernels move [n,w] rows
+                return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: a program built for element-major columns needs every column on "
+                                                       "the executor's own entity set (no entity-set join)");
+            if (rc = gather_joined(h, c); rc != SIXDOF_OK) return rc;
         }
         P->model_cols[k] = c->live;
-        P->model_hist[k] = (h->hist_ring && k < h->d_model_hist.size()) ? h->d_model_hist[k] : nullptr;
+        P->model_hist[k] = (h->hist.ring && k < h->hist.model.size()) ? h->hist.model[k].get() : nullptr;
     }
     P->tick0 = h->tick;
     return build_dev_ops(h, P->ops, &P->n_ops, &P->vel_independent);
@@ -925,9 +896,9 @@ hipError_t launch_any(sixdof_handle* h, const StepParams& P) {
         // the object keeps the tables it launches with per thread (one object may serve several handles): hand this handle's over
         for (size_t k = 0; k < h->custom_folds.size(); k++)
             if (h->custom_folds[k].needs_table) h->custom_set_fold_table(static_cast<unsigned>(k), h->custom_folds[k].set ? &h->custom_folds[k].table : nullptr);
-        return static_cast<hipError_t>(h->custom_launch(&P, h->desc.integrator, h->desc.dtype, h->stream));
+        return static_cast<hipError_t>(h->custom_launch(&P, h->desc.integrator, h->desc.dtype, h->stream.get()));
     }
-    return launch_step(P, h->desc.integrator, h->desc.dtype, h->stream);
+    return launch_step(P, h->desc.integrator, h->desc.dtype, h->stream.get());
 }
 
 int fill_pair_params(sixdof_handle* h, PairParams* P) {
@@ -943,12 +914,8 @@ int fill_pair_params(sixdof_handle* h, PairParams* P) {
     const size_t pack_bytes = align_up(sizeof(double) * kPackWidth * n, 256);
     const size_t partial_bytes = align_up(sizeof(double) * pwidth * n * splits, 256);
     const size_t total = pack_bytes + partial_bytes + (allpairs ? 0 : pack_bytes);      // edge lists: a second pack buffer (the one-launch tick ping-pongs)
-    if (total > h->scratch_bytes) {
-        if (h->d_scratch) hipFree(h->d_scratch), h->d_scratch = nullptr;
-        HIP_TRY(h, hipMalloc(&h->d_scratch, total ? total : 256));
-        h->scratch_bytes = total;
-    }
-    char* base = static_cast<char*>(h->d_scratch);
+    if (total > h->d_scratch.bytes()) HIP_TRY(h, h->d_scratch.alloc(total));   // free first; on failure empty
+    char* base = h->d_scratch.get<char>();
     P->pos = h->col(h->id_pos)->live;
     P->vel = h->col(h->id_vel)->live;
     P->accel = h->col(h->id_accel)->live;
@@ -966,18 +933,19 @@ int fill_pair_params(sixdof_handle* h, PairParams* P) {
     P->p0 = pop.p[0];
     P->p1 = pop.p[1];
     if (pop.kind != SIXDOF_EFF_ALLPAIRS_GRAVITY_SOFTENED) {
-        if (!h->d_csr_start) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "step: edge effector without sixdof_set_edges");
-        P->row_start = h->d_csr_start;
-        P->dst = h->d_csr_dst;
-        P->n_edges = static_cast<uint32_t>(h->edge_src.size());
-        P->n_hubs = h->n_hubs;
-        P->n_hub_chunks = h->n_hub_chunks;
-        if (h->n_hubs) {
-            P->hub_rows = h->d_hub;
-            P->hub_chunk_start = h->d_hub + h->n_hubs;
-            P->chunk_e0 = h->d_hub + h->n_hubs + (h->n_hubs + 1);
-            P->chunk_row = P->chunk_e0 + h->n_hub_chunks;
-            P->chunk_partial = h->d_chunk_partial;
+        const Edges& ed = h->edges;
+        if (!ed.d_csr_start) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "step: edge effector without sixdof_set_edges");
+        P->row_start = ed.d_csr_start.get<uint32_t>();
+        P->dst = ed.d_csr_dst.get<uint32_t>();
+        P->n_edges = static_cast<uint32_t>(ed.src.size());
+        P->n_hubs = ed.n_hubs;
+        P->n_hub_chunks = ed.n_hub_chunks;
+        if (ed.n_hubs) {
+            P->hub_rows = ed.d_hub.get<uint32_t>();
+            P->hub_chunk_start = P->hub_rows + ed.n_hubs;
+            P->chunk_e0 = P->hub_chunk_start + (ed.n_hubs + 1);
+            P->chunk_row = P->chunk_e0 + ed.n_hub_chunks;
+            P->chunk_partial = ed.d_chunk_partial.get<double>();
         }
     }
     uint32_t vi = 0;
@@ -1007,16 +975,14 @@ double ref_interp(double t, const std::vector<double>& xs, const std::vector<dou
 // device on the compute stream, into the tick's ring slot — every tick is there, in the layout sixdof_history_read /
 // _stream expect.  (The fused per-entity kernel records from registers instead, step_kernel.hpp.)
 int snapshot_tick_to_ring(sixdof_handle* h, uint64_t ticks_done) {
-    if (!h->hist_ring) return SIXDOF_OK;
+    if (!h->hist.ring) return SIXDOF_OK;
     const size_t n = h->desc.n_entities, es = h->elem_size();
-    const size_t slot = static_cast<size_t>((ticks_done - 1) % h->hist_ring);
-    const uint64_t ids[4] = {h->id_pos, h->id_vel, h->id_accel, h->id_force};
-    const size_t widths[4] = {7, 6, 6, 6};
+    const size_t slot = static_cast<size_t>((ticks_done - 1) % h->hist.ring);
     for (int k = 0; k < 4; k++) {
-        const size_t block = n * widths[k] * es;
+        const size_t block = n * h->body[k].width * es;
         if (!block) continue;
-        HIP_TRY(h, hipMemcpyAsync(static_cast<char*>(h->d_hist[k]) + slot * block, h->col(ids[k])->live, block,
-                                  hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->hist.body[k].get<char>() + slot * block, h->col(h->body[k].id)->live, block,
+                                  hipMemcpyDeviceToDevice, h->stream.get()));
     }
     return SIXDOF_OK;
 }
@@ -1030,15 +996,7 @@ int step_apollo(sixdof_handle* h, uint64_t n_ticks, uint64_t* launches) {
         if (!c[k]) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, std::string("step: Apollo model column not bound: ") + names[k]);
         if (c[k]->width != widths[k] || c[k]->prim != SIXDOF_PRIM_F64)
             return h->fail(SIXDOF_ERR_VALUE_SIZE_MISMATCH, std::string("step: bad shape for ") + names[k]);
-        if (!c[k]->joined) {
-            int rc = resolve_join(h, c[k]);
-            if (rc != SIXDOF_OK) return rc;
-            if (c[k]->compact) {
-                hipError_t e = launch_gather_rows(c[k]->compact, c[k]->dev, c[k]->d_rows, static_cast<uint32_t>(h->joined_ids.size()),
-                                                  static_cast<uint32_t>(c[k]->width), c[k]->elem, h->stream);
-                if (e != hipSuccess) return h->hip_fail(e, "gather_rows");
-            }
-        }
+        if (int rc = ensure_joined(h, c[k]); rc != SIXDOF_OK) return rc;
     }
     ApolloParams P{};
     P.pos = static_cast<double*>(h->col(h->id_pos)->live);
@@ -1056,12 +1014,9 @@ int step_apollo(sixdof_handle* h, uint64_t n_ticks, uint64_t* launches) {
     P.guidance_period = h->ap_guidance_period;
     P.ticks_per_telemetry = h->ap_ticks_per_telemetry;
     P.dt = h->desc.simulation_time_step;
-    const uint32_t K = h->hist_ring ? 1u : h->desc.ticks_per_launch;   // recording: one tick per launch, see snapshot_tick_to_ring
-    if (K > h->tick_refs_cap) {
-        if (h->d_tick_refs) hipFree(h->d_tick_refs), h->d_tick_refs = nullptr;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_tick_refs), static_cast<size_t>(K) * 8 * sizeof(double)));
-        h->tick_refs_cap = K;
-    }
+    const uint32_t K = h->hist.ring ? 1u : h->desc.ticks_per_launch;   // recording: one tick per launch, see snapshot_tick_to_ring
+    if (const size_t need = static_cast<size_t>(K) * 8 * sizeof(double); need > h->d_tick_refs.bytes())
+        HIP_TRY(h, h->d_tick_refs.alloc(need));   // free first; on failure empty
     std::vector<double> refs(static_cast<size_t>(K) * 8);
     uint64_t done = 0;
     while (done < n_ticks) {
@@ -1079,17 +1034,17 @@ int step_apollo(sixdof_handle* h, uint64_t n_ticks, uint64_t* launches) {
             r[6] = r[7] = 0.0;
         }
         // stream-ordered: the previous launch has consumed the buffer before this copy executes
-        HIP_TRY(h, hipMemcpyAsync(h->d_tick_refs, refs.data(), static_cast<size_t>(k) * 8 * sizeof(double),
-                                  hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));  // `refs` is reused by the next chunk
-        P.tick_refs = h->d_tick_refs;
+        HIP_TRY(h, hipMemcpyAsync(h->d_tick_refs.get(), refs.data(), static_cast<size_t>(k) * 8 * sizeof(double),
+                                  hipMemcpyHostToDevice, h->stream.get()));
+        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));  // `refs` is reused by the next chunk
+        P.tick_refs = h->d_tick_refs.get<double>();
         P.n_ticks = k;
         P.tick0 = h->tick + done;
-        hipError_t e = launch_apollo(P, h->stream);
+        hipError_t e = launch_apollo(P, h->stream.get());
         if (e != hipSuccess) return h->hip_fail(e, "launch_apollo");
         (*launches)++;
         done += k;
-        if (h->hist_ring) {
+        if (h->hist.ring) {
             int rc = snapshot_tick_to_ring(h, h->tick + done);
             if (rc != SIXDOF_OK) return rc;
         }
@@ -1131,19 +1086,17 @@ int sixdof_count_nonfinite(sixdof_handle* h, uint64_t* count, uint8_t* row_flags
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "count_nonfinite: no columns bound");
     HIP_TRY(h, hipSetDevice(h->device));
     const uint32_t n = static_cast<uint32_t>(h->desc.n_entities);
-    unsigned long long* d_count = nullptr;
-    uint8_t* d_flags = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&d_count), sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(d_count, 0, sizeof(unsigned long long), h->stream);
-    if (e == hipSuccess && row_flags && n) e = hipMalloc(reinterpret_cast<void**>(&d_flags), n);
+    DeviceBuffer d_count, d_flags;
+    HIP_TRY(h, d_count.alloc(sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(d_count.get(), 0, sizeof(unsigned long long), h->stream.get());
+    if (e == hipSuccess && row_flags && n) e = d_flags.alloc(n);
     if (e == hipSuccess)
-        e = launch_nonfinite(h->col(h->id_pos)->live, h->col(h->id_vel)->live, n, h->elem_size(), d_flags, d_count, h->stream);
+        e = launch_nonfinite(h->col(h->id_pos)->live, h->col(h->id_vel)->live, n, h->elem_size(), d_flags.get<uint8_t>(),
+                             d_count.get<unsigned long long>(), h->stream.get());
     unsigned long long host_count = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&host_count, d_count, sizeof(host_count), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && d_flags) e = hipMemcpyAsync(row_flags, d_flags, n, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d_count);
-    if (d_flags) hipFree(d_flags);
+    if (e == hipSuccess) e = hipMemcpyAsync(&host_count, d_count.get(), sizeof(host_count), hipMemcpyDeviceToHost, h->stream.get());
+    if (e == hipSuccess && d_flags) e = hipMemcpyAsync(row_flags, d_flags.get(), n, hipMemcpyDeviceToHost, h->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream.get());
     if (e != hipSuccess) return h->hip_fail(e, "count_nonfinite");
     *count = host_count;
     return SIXDOF_OK;
@@ -1151,31 +1104,25 @@ int sixdof_count_nonfinite(sixdof_handle* h, uint64_t* count, uint8_t* row_flags
 
 int sixdof_set_custom_pipe(sixdof_handle* h, const char* so_path, const uint64_t* aux_ids, size_t n_aux) try {
     if (!h || !so_path || (!aux_ids && n_aux)) return SIXDOF_ERR_INVALID_ARGUMENT;
-    void* dl = dlopen(so_path, RTLD_NOW | RTLD_LOCAL);
+    DlHandle owned;   // closed again by every early return
+    void* dl = *owned.out() = dlopen(so_path, RTLD_NOW | RTLD_LOCAL);
     if (!dl) return h->fail(SIXDOF_ERR_BACKEND, std::string("set_custom_pipe: dlopen failed: ") + dlerror());
     auto abi = reinterpret_cast<CustomAbiFn>(dlsym(dl, "sixdof_custom_abi"));
     auto layout = reinterpret_cast<CustomLayoutFn>(dlsym(dl, "sixdof_custom_layout"));
     auto launch = reinterpret_cast<CustomLaunchFn>(dlsym(dl, "sixdof_custom_launch"));
-    if (!abi || !layout || !launch || abi() != sizeof(StepParams)) {
-        dlclose(dl);
+    if (!abi || !layout || !launch || abi() != sizeof(StepParams))
         return h->fail(SIXDOF_ERR_BACKEND, "set_custom_pipe: not a generated pipe for this library build (StepParams layout differs)");
-    }
     auto col_widths = reinterpret_cast<void (*)(unsigned*)>(dlsym(dl, "sixdof_custom_column_widths"));
     // a program that exchanges data between the entities of a world inside the wavefront (a whole-world StableHLO tick with one lane
     // per entity: elodin_amd/stablehlo.py, manifest "rows_per_world") lays a world out as that many consecutive rows
     auto rows_multiple = reinterpret_cast<unsigned (*)()>(dlsym(dl, "sixdof_custom_rows_multiple"));
-    if (rows_multiple && rows_multiple() > 1 && h->desc.n_entities % rows_multiple() != 0) {
-        const unsigned m = rows_multiple();
-        dlclose(dl);
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "set_custom_pipe: the program lays a world out as " + std::to_string(m) +
+    if (rows_multiple && rows_multiple() > 1 && h->desc.n_entities % rows_multiple() != 0)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "set_custom_pipe: the program lays a world out as " + std::to_string(rows_multiple()) +
                        " consecutive rows; " + std::to_string(h->desc.n_entities) + " rows are not a whole number of worlds");
-    }
     const unsigned lay = layout();
     const size_t k_aux = lay & 0xff, k_model = (lay >> 8) & 0xff;
-    if (k_aux > static_cast<size_t>(kMaxOps) || k_model > static_cast<size_t>(kMaxModelCols) || k_aux + k_model != n_aux) {
-        dlclose(dl);
+    if (k_aux > static_cast<size_t>(kMaxOps) || k_model > static_cast<size_t>(kMaxModelCols) || k_aux + k_model != n_aux)
         return h->fail(SIXDOF_ERR_VALUE_SIZE_MISMATCH, "set_custom_pipe: column list does not match the generated code's layout");
-    }
     // fold stages that read their edges from device memory (optional exports; an object without them bakes its edges)
     auto fold_count = reinterpret_cast<unsigned (*)()>(dlsym(dl, "sixdof_custom_fold_count"));
     auto fold_info = reinterpret_cast<int (*)(unsigned, unsigned*)>(dlsym(dl, "sixdof_custom_fold_info"));
@@ -1185,24 +1132,18 @@ int sixdof_set_custom_pipe(sixdof_handle* h, const char* so_path, const uint64_t
         folds.resize(fold_count());
         for (size_t k = 0; k < folds.size(); k++) {
             unsigned info[4] = {0, 0, 0, 0};
-            if (fold_info(static_cast<unsigned>(k), info) != 0 || info[3] != sizeof(FoldTable)) {
-                dlclose(dl);
+            if (fold_info(static_cast<unsigned>(k), info) != 0 || info[3] != sizeof(FoldTable))
                 return h->fail(SIXDOF_ERR_BACKEND, "set_custom_pipe: the object's fold tables are not this library build's (FoldTable layout differs)");
-            }
             folds[k].needs_table = (info[0] & 1u) != 0;
             folds[k].wave_ok = (info[0] & 2u) != 0;
             folds[k].count = info[1];
             folds[k].stride = info[2];
         }
     }
-    if (h->stream) (void)hipStreamSynchronize(h->stream);      // nothing in flight reads the tables of the program being replaced
-    h->free_fold_tables();
-    if (!folds.empty()) {
-        h->custom_folds.swap(folds);
-        h->custom_set_fold_table = set_fold_table;
-    }
-    if (h->custom_dl) dlclose(h->custom_dl);
-    h->custom_dl = dl;
+    HIP_TRY(h, hipStreamSynchronize(h->stream.get()));      // nothing in flight reads the tables of the program being replaced
+    h->custom_set_fold_table = folds.empty() ? nullptr : set_fold_table;
+    h->custom_folds = std::move(folds);   // frees the previous program's tables
+    h->custom_dl = std::move(owned);      // and closes its object
     h->custom_launch = launch;
     h->custom_rows_multiple = rows_multiple ? rows_multiple() : 1;      // checked again when the join is (re)sized: sixdof_bind_columns
     h->custom_aux.assign(aux_ids, aux_ids + k_aux);
@@ -1234,17 +1175,10 @@ int sixdof_set_fold_edges(sixdof_handle* h, uint32_t fold_index, const uint64_t*
         return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "set_fold_edges: the program was generated for " + std::to_string(f.count) + " replicas of " +
                        std::to_string(f.stride) + " rows; the handle has " + std::to_string(n) + " rows");
     const uint32_t row_limit = replicated ? f.stride : static_cast<uint32_t>(std::min<uint64_t>(n, 0xFFFFFFFFull));
-    std::unordered_map<uint64_t, uint32_t> row_of;   // entity id -> row of the joined Body set
-    row_of.reserve(h->joined_ids.size() * 2);
-    for (size_t r = 0; r < h->joined_ids.size(); r++) row_of.emplace(h->joined_ids[r], static_cast<uint32_t>(r));
-    std::vector<uint32_t> src(n_edges), dst(n_edges);
-    for (size_t e = 0; e < n_edges; e++) {
-        auto a = row_of.find(from_ids[e]), b = row_of.find(to_ids[e]);
-        if (a == row_of.end() || b == row_of.end())
-            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_fold_edges: edge endpoint is not an entity of this handle");
-        src[e] = a->second;
-        dst[e] = b->second;
-    }
+    std::vector<uint32_t> src, dst;
+    const RowMap row_of = row_map(h->joined_ids);
+    if (resolve_rows(row_of, from_ids, n_edges, &src) != n_edges || resolve_rows(row_of, to_ids, n_edges, &dst) != n_edges)
+        return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_fold_edges: edge endpoint is not an entity of this handle");
     // one block [src_rows (n_src) | row_start (n_src + 1) | dst (n_edges)], built for the most sources there can be
     std::vector<uint32_t> o_src(n_edges), o_start(n_edges + 1), o_dst(n_edges);
     uint32_t n_src = 0, n_lane = 0;
@@ -1259,17 +1193,14 @@ int sixdof_set_fold_edges(sixdof_handle* h, uint32_t fold_index, const uint64_t*
     blob.insert(blob.end(), o_start.begin(), o_start.begin() + n_src + 1);
     blob.insert(blob.end(), o_dst.begin(), o_dst.end());
     HIP_TRY(h, hipSetDevice(h->device));
-    uint32_t* d_new = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&d_new), blob.size() * sizeof(uint32_t)));
-    hipError_t e = hipMemcpyAsync(d_new, blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream);
+    DeviceBuffer fresh;
+    HIP_TRY(h, fresh.alloc(blob.size() * sizeof(uint32_t)));
+    hipError_t e = hipMemcpyAsync(fresh.get(), blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream.get());
     // drains the batches that still read the old table, and the copy itself (its source is a local)
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        hipFree(d_new);
-        return h->hip_fail(e, "set_fold_edges: upload");
-    }
-    if (f.d_blob) hipFree(f.d_blob);
-    f.d_blob = d_new;
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream.get());
+    if (e != hipSuccess) return h->hip_fail(e, "set_fold_edges: upload");
+    f.d_blob = std::move(fresh);
+    const uint32_t* d_new = f.d_blob.get<uint32_t>();
     f.table.src_rows = d_new;
     f.table.row_start = d_new + n_src;
     f.table.dst = d_new + static_cast<size_t>(n_src) * 2 + 1;
@@ -1283,16 +1214,14 @@ int sixdof_set_fold_edges(sixdof_handle* h, uint32_t fold_index, const uint64_t*
 int sixdof_set_custom_pair(sixdof_handle* h, const char* so_path) try {
     if (!h || !so_path) return SIXDOF_ERR_INVALID_ARGUMENT;
     if (h->custom_launch) return h->fail(SIXDOF_ERR_UNSUPPORTED, "set_custom_pair: a generated per-entity pipe is installed; pair folds combine with built-in ops only");
-    void* dl = dlopen(so_path, RTLD_NOW | RTLD_LOCAL);
+    DlHandle owned;
+    void* dl = *owned.out() = dlopen(so_path, RTLD_NOW | RTLD_LOCAL);
     if (!dl) return h->fail(SIXDOF_ERR_BACKEND, std::string("set_custom_pair: dlopen failed: ") + dlerror());
     auto abi = reinterpret_cast<CustomPairAbiFn>(dlsym(dl, "sixdof_custom_pair_abi"));
     auto launch = reinterpret_cast<CustomPairLaunchFn>(dlsym(dl, "sixdof_custom_pair_launch"));
-    if (!abi || !launch || abi() != sizeof(PairParams)) {
-        dlclose(dl);
+    if (!abi || !launch || abi() != sizeof(PairParams))
         return h->fail(SIXDOF_ERR_BACKEND, "set_custom_pair: not a generated pair fold for this library build (PairParams layout differs)");
-    }
-    if (h->pair_dl) dlclose(h->pair_dl);
-    h->pair_dl = dl;
+    h->pair_dl = std::move(owned);   // closes the previous object
     h->pair_launch = launch;
     // an object generated for one launch shape only (codegen.build_pair(small=...)) says which: step follows the object
     auto only_small = reinterpret_cast<int (*)()>(dlsym(dl, "sixdof_custom_pair_only_small"));
@@ -1309,123 +1238,40 @@ int sixdof_set_history(sixdof_handle* h, uint32_t ring_ticks) try {
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_history: bind Body columns first");
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (void*& p : h->d_hist) {
-        if (p) hipFree(p);
-        p = nullptr;
-    }
-    for (void* p : h->d_model_hist) if (p) hipFree(p);
-    h->d_model_hist.clear();
-    h->hist_ring = 0;
+    HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
+    h->hist.reset();   // free first (rings can be gigabytes): from here to the end of a successful call there is no ring
     h->replay.drop();
     if (ring_ticks == 0) return SIXDOF_OK;
     const size_t n = h->desc.n_entities, es = h->elem_size();
-    const size_t widths[4] = {7, 6, 6, 6};
+    History fresh;     // freed as a whole by any failure below
     for (int k = 0; k < 4; k++) {
-        const size_t bytes = static_cast<size_t>(ring_ticks) * n * widths[k] * es;
-        hipError_t e = hipMalloc(&h->d_hist[k], bytes ? bytes : 16);
-        if (e != hipSuccess) {
-            for (void*& p : h->d_hist) {
-                if (p) hipFree(p);
-                p = nullptr;
-            }
-            return h->hip_fail(e, "set_history: hipMalloc of the ring");
-        }
+        const size_t bytes = static_cast<size_t>(ring_ticks) * n * h->body[k].width * es;
+        if (hipError_t e = fresh.body[k].alloc(bytes ? bytes : 16); e != hipSuccess) return h->hip_fail(e, "set_history: hipMalloc of the ring");
     }
     for (uint64_t id : h->custom_model) {      // component columns of a generated program are recorded too
         const Column* c = h->col(id);
-        void* ring = nullptr;
-        const size_t m_idx = h->d_model_hist.size();
+        const size_t m_idx = fresh.model.size();
         const bool window = m_idx < h->custom_model_width.size() && (h->custom_model_width[m_idx] >> 31);
+        fresh.model.emplace_back();
         if (c && !window) {   // a window column is its own history (and far too wide to copy per tick)
             const size_t bytes = static_cast<size_t>(ring_ticks) * n * c->width * es;
-            hipError_t e = hipMalloc(&ring, bytes ? bytes : 16);
-            if (e != hipSuccess) return h->hip_fail(e, "set_history: hipMalloc of a component ring");
+            if (hipError_t e = fresh.model.back().alloc(bytes ? bytes : 16); e != hipSuccess)
+                return h->hip_fail(e, "set_history: hipMalloc of a component ring");
         }
-        h->d_model_hist.push_back(ring);
     }
-    h->hist_ring = ring_ticks;
-    h->hist_first_tick = h->tick + 1;
+    fresh.ring = ring_ticks;
+    fresh.first_tick = h->tick + 1;
+    h->hist = std::move(fresh);
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
-int sixdof_history_read(sixdof_handle* h, uint64_t component_id, uint64_t tick, void* host_dst) try {
-    if (!h || !host_dst) return SIXDOF_ERR_INVALID_ARGUMENT;
-    if (!h->hist_ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_read: no history ring (sixdof_set_history)");
-    int k = -1;
-    size_t w = 6;
-    if (component_id == h->id_pos) k = 0, w = 7;
-    else if (component_id == h->id_vel) k = 1;
-    else if (component_id == h->id_accel) k = 2;
-    else if (component_id == h->id_force) k = 3;
-    const void* ring_base = k >= 0 ? h->d_hist[k] : nullptr;
-    if (k < 0) {
-        for (size_t m = 0; m < h->custom_model.size() && m < h->d_model_hist.size(); m++)
-            if (h->custom_model[m] == component_id && h->d_model_hist[m]) {
-                ring_base = h->d_model_hist[m];
-                w = h->col(component_id)->width;
-            }
-        if (!ring_base)
-            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "history_read: only world_pos / world_vel / world_accel / force and the component columns of a generated program are recorded");
-    }
-    if (tick < h->hist_first_tick || tick > h->tick || tick + h->hist_ring <= h->tick)
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_read: tick is not in the ring");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t block = static_cast<size_t>(h->desc.n_entities) * w * h->elem_size();
-    const size_t slot = static_cast<size_t>((tick - 1) % h->hist_ring);
-    if (block) HIP_TRY(h, hipMemcpyAsync(host_dst, static_cast<const char*>(ring_base) + slot * block, block, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SIXDOF_OK;
-} SIXDOF_ABI_CATCH(err_of(h))
-
-int sixdof_history_stream(sixdof_handle* h, uint64_t first_tick, uint64_t n_ticks, void* const host_dst[4]) try {
-    if (!h || !host_dst) return SIXDOF_ERR_INVALID_ARGUMENT;
-    if (!h->hist_ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_stream: no history ring (sixdof_set_history)");
-    if (n_ticks == 0) return SIXDOF_OK;
-    const uint64_t last = first_tick + n_ticks - 1;
-    if (first_tick < h->hist_first_tick || last > h->tick || first_tick + h->hist_ring <= h->tick || n_ticks > h->hist_ring)
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_stream: ticks are not (all) in the ring");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->copy_stream) {
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_snap, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied, hipEventDisableTiming));
-    }
-    HIP_TRY(h, hipEventRecord(h->ev_snap, h->stream));            // everything recorded so far is in the ring after this
-    HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->ev_snap, 0));
-    const size_t n = h->desc.n_entities, es = h->elem_size();
-    for (int k = 0; k < 4; k++) {
-        if (!host_dst[k]) continue;
-        const size_t block = n * (k == 0 ? 7 : 6) * es;
-        if (!block) continue;
-        if (std::find(h->pinned_user.begin(), h->pinned_user.end(), host_dst[k]) == h->pinned_user.end()) {
-            if (hipHostRegister(host_dst[k], block * n_ticks, hipHostRegisterDefault) == hipSuccess) h->pinned_user.push_back(host_dst[k]);
-            else (void)hipGetLastError();
-        }
-        // the run is contiguous in the ring except where it wraps: at most two copies per column
-        const size_t slot0 = static_cast<size_t>((first_tick - 1) % h->hist_ring);
-        const size_t head = std::min<size_t>(n_ticks, h->hist_ring - slot0);
-        char* dst = static_cast<char*>(host_dst[k]);
-        const char* ring = static_cast<const char*>(h->d_hist[k]);
-        HIP_TRY(h, hipMemcpyAsync(dst, ring + slot0 * block, head * block, hipMemcpyDeviceToHost, h->copy_stream));
-        if (head < n_ticks)
-            HIP_TRY(h, hipMemcpyAsync(dst + head * block, ring, (n_ticks - head) * block, hipMemcpyDeviceToHost, h->copy_stream));
-    }
-    HIP_TRY(h, hipEventRecord(h->ev_copied, h->copy_stream));
-    h->copy_pending = true;
-    h->stream_lo = first_tick;
-    h->stream_hi = last;
-    return SIXDOF_OK;
-} SIXDOF_ABI_CATCH(err_of(h))
-
-// Ring and row width of a watchable component: the four recorded Body columns and the non-window component columns of the
-// installed program — what sixdof_history_read accepts.  *ring_base is null while no ring is enabled.
+// Ring and row width of a recorded component: the four recorded Body columns and the non-window component columns of the
+// installed program — what sixdof_history_read accepts and sixdof_set_watch watches.  *ring_base is null while no ring is enabled.
 static bool watch_lookup(const sixdof_handle* h, uint64_t id, const void** ring_base, size_t* w) {
-    const uint64_t body[4] = {h->id_pos, h->id_vel, h->id_accel, h->id_force};
-    for (int k = 0; k < 4; k++)
-        if (id == body[k]) {
-            *ring_base = h->hist_ring ? h->d_hist[k] : nullptr;
-            *w = k == 0 ? 7 : 6;
+    for (auto& b : h->body)
+        if (id == b.id && b.ring >= 0) {
+            *ring_base = h->hist.ring ? h->hist.body[b.ring].get() : nullptr;
+            *w = b.width;
             return true;
         }
     for (size_t m = 0; m < h->custom_model.size(); m++) {
@@ -1433,12 +1279,65 @@ static bool watch_lookup(const sixdof_handle* h, uint64_t id, const void** ring_
         const bool window = m < h->custom_model_width.size() && (h->custom_model_width[m] >> 31);
         const Column* c = h->col(id);
         if (window || !c) return false;
-        *ring_base = h->hist_ring && m < h->d_model_hist.size() ? h->d_model_hist[m] : nullptr;
+        *ring_base = h->hist.ring && m < h->hist.model.size() ? h->hist.model[m].get() : nullptr;
         *w = static_cast<size_t>(c->width);
         return true;
     }
     return false;
 }
+
+int sixdof_history_read(sixdof_handle* h, uint64_t component_id, uint64_t tick, void* host_dst) try {
+    if (!h || !host_dst) return SIXDOF_ERR_INVALID_ARGUMENT;
+    const History& hs = h->hist;
+    if (!hs.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_read: no history ring (sixdof_set_history)");
+    const void* ring_base = nullptr;
+    size_t w = 0;
+    if (!watch_lookup(h, component_id, &ring_base, &w) || !ring_base)
+        return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "history_read: only world_pos / world_vel / world_accel / force and the component columns of a generated program are recorded");
+    if (tick < hs.first_tick || tick > h->tick || tick + hs.ring <= h->tick)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_read: tick is not in the ring");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t block = static_cast<size_t>(h->desc.n_entities) * w * h->elem_size();
+    const size_t slot = static_cast<size_t>((tick - 1) % hs.ring);
+    if (block) HIP_TRY(h, hipMemcpyAsync(host_dst, static_cast<const char*>(ring_base) + slot * block, block, hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
+    return SIXDOF_OK;
+} SIXDOF_ABI_CATCH(err_of(h))
+
+int sixdof_history_stream(sixdof_handle* h, uint64_t first_tick, uint64_t n_ticks, void* const host_dst[4]) try {
+    if (!h || !host_dst) return SIXDOF_ERR_INVALID_ARGUMENT;
+    const History& hs = h->hist;
+    if (!hs.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_stream: no history ring (sixdof_set_history)");
+    if (n_ticks == 0) return SIXDOF_OK;
+    const uint64_t last = first_tick + n_ticks - 1;
+    if (first_tick < hs.first_tick || last > h->tick || first_tick + hs.ring <= h->tick || n_ticks > hs.ring)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_stream: ticks are not (all) in the ring");
+    HIP_TRY(h, hipSetDevice(h->device));
+    CopyLane& lane = h->copy;
+    HIP_TRY(h, lane.ensure());
+    HIP_TRY(h, hipEventRecord(lane.ev_snap.get(), h->stream.get()));            // everything recorded so far is in the ring after this
+    HIP_TRY(h, hipStreamWaitEvent(lane.stream.get(), lane.ev_snap.get(), 0));
+    const size_t n = h->desc.n_entities, es = h->elem_size();
+    for (int k = 0; k < 4; k++) {
+        if (!host_dst[k]) continue;
+        const size_t block = n * h->body[k].width * es;
+        if (!block) continue;
+        lane.pin(host_dst[k], block * n_ticks);
+        // the run is contiguous in the ring except where it wraps: at most two copies per column
+        const size_t slot0 = static_cast<size_t>((first_tick - 1) % hs.ring);
+        const size_t head = std::min<size_t>(n_ticks, hs.ring - slot0);
+        char* dst = static_cast<char*>(host_dst[k]);
+        const char* ring = hs.body[k].get<char>();
+        HIP_TRY(h, hipMemcpyAsync(dst, ring + slot0 * block, head * block, hipMemcpyDeviceToHost, lane.stream.get()));
+        if (head < n_ticks)
+            HIP_TRY(h, hipMemcpyAsync(dst + head * block, ring, (n_ticks - head) * block, hipMemcpyDeviceToHost, lane.stream.get()));
+    }
+    HIP_TRY(h, hipEventRecord(lane.ev_copied.get(), lane.stream.get()));
+    lane.pending = true;
+    lane.stream_lo = first_tick;
+    lane.stream_hi = last;
+    return SIXDOF_OK;
+} SIXDOF_ABI_CATCH(err_of(h))
 
 int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, const uint64_t* entity_ids,
                      size_t n_entities) try {
@@ -1454,43 +1353,28 @@ int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_c
         if (!watch_lookup(h, component_ids[k], &ring_base, &w))
             return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_watch: only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
     }
-    std::vector<uint32_t> rows(n_entities);
-    if (n_entities) {
-        std::unordered_map<uint64_t, uint32_t> row_of;   // entity id -> row of the joined Body set
-        row_of.reserve(h->joined_ids.size() * 2);
-        for (size_t r = 0; r < h->joined_ids.size(); r++) row_of.emplace(h->joined_ids[r], static_cast<uint32_t>(r));
-        for (size_t e = 0; e < n_entities; e++) {
-            auto it = row_of.find(entity_ids[e]);
-            if (it == row_of.end())
-                return h->fail(SIXDOF_ERR_ENTITY_MISMATCH, "set_watch: entity " + std::to_string(entity_ids[e]) + " is not in the joined Body entity set");
-            rows[e] = it->second;
-        }
-    }
+    std::vector<uint32_t> rows;
+    if (const size_t bad = resolve_rows(row_map(h->joined_ids), entity_ids, n_entities, &rows); bad != n_entities)
+        return h->fail(SIXDOF_ERR_ENTITY_MISMATCH, "set_watch: entity " + std::to_string(entity_ids[bad]) + " is not in the joined Body entity set");
     std::vector<uint64_t> ids(component_ids, component_ids + n_components);
-    uint32_t* d_rows = nullptr;
+    DeviceBuffer d_rows;
     if (n_entities) {
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&d_rows), n_entities * sizeof(uint32_t)));
-        if (hipError_t e = hipMemcpy(d_rows, rows.data(), n_entities * sizeof(uint32_t), hipMemcpyHostToDevice); e != hipSuccess) {
-            hipFree(d_rows);
-            return h->hip_fail(e, "set_watch: upload of the row table");
-        }
+        HIP_TRY(h, d_rows.alloc(n_entities * sizeof(uint32_t)));
+        HIP_TRY(h, hipMemcpy(d_rows.get(), rows.data(), n_entities * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    if (hipError_t e = hipStreamSynchronize(h->stream); e != hipSuccess) {   // a gather in flight reads the old table
-        if (d_rows) hipFree(d_rows);
-        return h->hip_fail(e, "set_watch: hipStreamSynchronize");
-    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream.get()));   // a gather in flight reads the old table
     h->drop_watch();
     h->watch_ids.swap(ids);
-    h->d_watch_rows = d_rows;
+    h->d_watch_rows = std::move(d_rows);
     h->watch_m = n_entities;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
 // Ordering of the gather after the batch that recorded the ticks it reads.  With a ring enabled a handle neither replays
 // hipGraphs nor submits AQL chains (graph_eligible needs !hist_ring): every recording launch — the step kernel, the pair
-// and model kernels and their snapshot_tick_to_ring copies — is an eager launch on h->stream, so the gather, launched on
-// h->stream, follows the batch's last launch by stream order, asynchronous steps included.  Were a ring ever recorded
-// through the other two paths: hipGraphLaunch replays on h->stream too (stream order again), and an AQL chain is waited
+// and model kernels and their snapshot_tick_to_ring copies — is an eager launch on h->stream.get(), so the gather, launched on
+// h->stream.get(), follows the batch's last launch by stream order, asynchronous steps included.  Were a ring ever recorded
+// through the other two paths: hipGraphLaunch replays on h->stream.get() too (stream order again), and an AQL chain is waited
 // for on the host before sixdof_step returns (aql::run_chain spins on its last packet), i.e. before this call can start.
 // The ring is read on the compute stream only; the copy stream reads the staging buffer.  So the next batch, also on
 // the compute stream, may overwrite the slots with no further wait, and stream_lo / stream_hi — the overwrite protection
@@ -1500,11 +1384,11 @@ int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples,
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
     if (flags & ~SIXDOF_WATCH_ASYNC) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: unknown flags");
     if (h->watch_ids.empty()) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: no watch (sixdof_set_watch)");
-    if (!h->hist_ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: no history ring (sixdof_set_history)");
+    if (!h->hist.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: no history ring (sixdof_set_history)");
     if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: every must be at least 1");
     if (n_samples == 0) return SIXDOF_OK;
     if (!host_dst) return SIXDOF_ERR_INVALID_ARGUMENT;
-    if (!sampled_range_ok(first_tick, n_samples, every, h->hist_first_tick, h->tick, h->hist_ring))
+    if (!sampled_range_ok(first_tick, n_samples, every, h->hist.first_tick, h->tick, h->hist.ring))
         return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: ticks are not (all) in the ring");
     const size_t n_comp = h->watch_ids.size(), es = h->elem_size(), m = h->watch_m;
     // per component: ring base and width as they are NOW, and its block in the staging buffer (256-byte aligned)
@@ -1522,22 +1406,16 @@ int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples,
     }
     HIP_TRY(h, hipSetDevice(h->device));
     const bool async = (flags & SIXDOF_WATCH_ASYNC) != 0;
-    if (async && !h->copy_stream) {
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_snap, hipEventDisableTiming));
-        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copied, hipEventDisableTiming));
-    }
-    if (stage > h->watch_stage_bytes) {
+    CopyLane& lane = h->copy;
+    if (async) HIP_TRY(h, lane.ensure());
+    if (stage > h->d_watch_stage.bytes()) {
         // the copy stream may still read the old buffer (a previous asynchronous read), the compute stream may still write it
-        if (h->copy_pending) HIP_TRY(h, hipStreamSynchronize(h->copy_stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_watch_stage) hipFree(h->d_watch_stage), h->d_watch_stage = nullptr;
-        h->watch_stage_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->d_watch_stage, stage));
-        h->watch_stage_bytes = stage;
+        if (lane.pending) HIP_TRY(h, hipStreamSynchronize(lane.stream.get()));
+        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
+        HIP_TRY(h, h->d_watch_stage.alloc(stage));   // free first; on failure empty
     }
     // one staging buffer: the previous asynchronous read's copies must have drained it before it is overwritten (device-side wait)
-    if (h->copy_pending) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied, 0));
+    if (lane.pending) HIP_TRY(h, hipStreamWaitEvent(h->stream.get(), lane.ev_copied.get(), 0));
     for (size_t k0 = 0; k0 < n_comp; k0 += kHistoryGatherMax) {
         const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kHistoryGatherMax, n_comp - k0));
         HistoryGatherArgs a{};
@@ -1546,30 +1424,27 @@ int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples,
             a.c[k].out_offset = parts[k0 + k].offset / es;
             a.c[k].w = static_cast<uint32_t>(parts[k0 + k].w);
         }
-        hipError_t e = launch_history_gather(a, cnt, h->d_watch_stage, h->d_watch_rows, m, h->desc.n_entities, first_tick, n_samples,
-                                             every, h->hist_ring, es, h->stream);
+        hipError_t e = launch_history_gather(a, cnt, h->d_watch_stage.get(), h->d_watch_rows.get<uint32_t>(), m, h->desc.n_entities, first_tick, n_samples,
+                                             every, h->hist.ring, es, h->stream.get());
         if (e != hipSuccess) return h->hip_fail(e, "history_gather");
     }
-    const char* staged = static_cast<const char*>(h->d_watch_stage);
+    const char* staged = h->d_watch_stage.get<char>();
     if (!async) {
         for (const Part& p : parts)
-            if (p.bytes) HIP_TRY(h, hipMemcpyAsync(host_dst[&p - parts.data()], staged + p.offset, p.bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+            if (p.bytes) HIP_TRY(h, hipMemcpyAsync(host_dst[&p - parts.data()], staged + p.offset, p.bytes, hipMemcpyDeviceToHost, h->stream.get()));
+        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
         return SIXDOF_OK;
     }
-    HIP_TRY(h, hipEventRecord(h->ev_snap, h->stream));            // the series are in the staging buffer after this
-    HIP_TRY(h, hipStreamWaitEvent(h->copy_stream, h->ev_snap, 0));
+    HIP_TRY(h, hipEventRecord(lane.ev_snap.get(), h->stream.get()));            // the series are in the staging buffer after this
+    HIP_TRY(h, hipStreamWaitEvent(lane.stream.get(), lane.ev_snap.get(), 0));
     for (size_t k = 0; k < n_comp; k++) {
         if (!parts[k].bytes) continue;
-        if (std::find(h->pinned_user.begin(), h->pinned_user.end(), host_dst[k]) == h->pinned_user.end()) {
-            if (hipHostRegister(host_dst[k], parts[k].bytes, hipHostRegisterDefault) == hipSuccess) h->pinned_user.push_back(host_dst[k]);
-            else (void)hipGetLastError();
-        }
-        HIP_TRY(h, hipMemcpyAsync(host_dst[k], staged + parts[k].offset, parts[k].bytes, hipMemcpyDeviceToHost, h->copy_stream));
+        lane.pin(host_dst[k], parts[k].bytes);
+        HIP_TRY(h, hipMemcpyAsync(host_dst[k], staged + parts[k].offset, parts[k].bytes, hipMemcpyDeviceToHost, lane.stream.get()));
     }
     // re-recorded behind whatever the copy stream already carried: one sixdof_download_wait covers a history_stream copy too
-    HIP_TRY(h, hipEventRecord(h->ev_copied, h->copy_stream));
-    h->copy_pending = true;
+    HIP_TRY(h, hipEventRecord(lane.ev_copied.get(), lane.stream.get()));
+    lane.pending = true;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -1580,8 +1455,8 @@ int sixdof_download_column(sixdof_handle* h, uint64_t component_id) try {
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = scatter_back(h, c);
     if (rc != SIXDOF_OK) return rc;
-    if (c->bytes) HIP_TRY(h, hipMemcpyAsync(c->host, c->dev, c->bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (c->bytes) HIP_TRY(h, hipMemcpyAsync(c->host, c->dev.get(), c->bytes, hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -1593,19 +1468,14 @@ int sixdof_upload_column(sixdof_handle* h, uint64_t component_id) try {
     if (!c) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "upload_column: unknown component");
     if (!h->resident) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "upload_column: nothing is resident yet (sixdof_upload first)");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (c->bytes) HIP_TRY(h, hipMemcpyAsync(c->dev, c->host, c->bytes, hipMemcpyHostToDevice, h->stream));
-    if (c->joined && c->compact) {
-        hipError_t e = launch_gather_rows(c->compact, c->dev, c->d_rows, static_cast<uint32_t>(h->joined_ids.size()),
-                                          static_cast<uint32_t>(c->width), c->elem, h->stream);
-        if (e != hipSuccess) return h->hip_fail(e, "gather_rows");
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = upload_one(h, c); rc != SIXDOF_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
     if (component_id == h->id_accel) h->accel_is_host_data = true;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
 bool graph_eligible(const sixdof_handle* h) {
-    return (h->desc.flags & SIXDOF_FLAG_USE_GRAPH) && !(h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) && !h->hist_ring &&
+    return (h->desc.flags & SIXDOF_FLAG_USE_GRAPH) && !(h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) && !h->hist.ring &&
            (h->custom_model.empty() || h->custom_tick_free) && h->model == 0 && !h->has_pair_op();
 }
 
@@ -1620,7 +1490,7 @@ static bool opens_with_check(const sixdof_handle* h, uint64_t n_ticks) {
 // overwrites them unread.  Launch i of a batch of L carries the flag iff i < L - 1 and it is not the accel-check launch:
 // the LAST launch of every call stores all four columns, and after any call they hold what they always held.
 static bool state_only_eligible(const sixdof_handle* h) {
-    return !h->replay.state_only_off && !h->custom_launch && !h->hist_ring && h->model == 0 && !h->has_pair_op();
+    return !h->replay.state_only_off && !h->custom_launch && !h->hist.ring && h->model == 0 && !h->has_pair_op();
 }
 
 constexpr size_t kGraphCacheMax = 8;
@@ -1648,20 +1518,20 @@ int ensure_graph(sixdof_handle* h, const StepParams& P, uint32_t len, Chain vari
     StepParams Q = P;
     Q.state_only = variant == Chain::kAll ? 0u : 1u;
     hipGraph_t g = nullptr;
-    HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    HIP_TRY(h, hipStreamBeginCapture(h->stream.get(), hipStreamCaptureModeThreadLocal));
     hipError_t le = hipSuccess;
     for (uint32_t i = 0; i < len && le == hipSuccess; i++) {
         if (i + 1 == len && variant == Chain::kClosing) Q.state_only = 0;
         le = launch_any(h, Q);
     }
-    hipError_t ce = hipStreamEndCapture(h->stream, &g);
+    hipError_t ce = hipStreamEndCapture(h->stream.get(), &g);
     if (le != hipSuccess) return h->hip_fail(le, "launch_step (capture)");
     if (ce != hipSuccess) return h->hip_fail(ce, "hipStreamEndCapture");
     hipGraphExec_t exec = nullptr;
     hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     hipGraphDestroy(g);
     if (ie != hipSuccess) return h->hip_fail(ie, "hipGraphInstantiate");
-    (void)hipGraphUpload(exec, h->stream);   // move the one-off device-side setup out of the first replay
+    (void)hipGraphUpload(exec, h->stream.get());   // move the one-off device-side setup out of the first replay
     graphs[graph_key(len, variant)] = exec;
     *out = exec;
     return SIXDOF_OK;
@@ -1735,7 +1605,7 @@ static bool aql_run(sixdof_handle* h, const StepParams& P, uint32_t check, uint3
     aql::Run r;
     if (!aql::kernel_code(rp.aql_dev, k.fn, sizeof(StepParams), &r.code, &rp.aql_why)) return false;
     if (r.code.kernarg_align > 256) return rp.aql_why = "kernarg alignment above 256 bytes", false;
-    char* slot = static_cast<char*>(rp.aql_args) + slot_index * kAqlSlotBytes;
+    char* slot = rp.aql_args.get<char>() + slot_index * kAqlSlotBytes;
     hipError_t e = hipMemcpy(slot, &Q, sizeof(Q), hipMemcpyHostToDevice);
     if (e != hipSuccess) return rp.aql_why = std::string("hipMemcpy (argument block): ") + hipGetErrorString(e), false;
     r.kernarg = slot;
@@ -1799,8 +1669,8 @@ static Route choose_path(sixdof_handle* h, uint64_t n_ticks, StepParams* P, aql:
     if (replay) rp.rekey(*P);
     const BatchPlan plan = plan_batch(n_ticks, K, opens_with_check(h, n_ticks), replay);
     if (!why && !rp.aql_dev && (rp.aql_dev = aql::acquire(h->device, &rp.aql_why))) {   // the queue and the arena, once
-        if (hipError_t e = hipMalloc(&rp.aql_args, kAqlSlots * kAqlSlotBytes); e != hipSuccess)
-            rp.aql_args = nullptr, rp.aql_why = std::string("hipMalloc: ") + hipGetErrorString(e);
+        if (hipError_t e = rp.aql_args.alloc(kAqlSlots * kAqlSlotBytes); e != hipSuccess)
+            rp.aql_why = std::string("hipMalloc: ") + hipGetErrorString(e);
     }
     if (!why && (!rp.aql_why.empty() || !aql_batch(h, *P, plan, runs))) why = rp.aql_why.c_str();
     return {why ? Path::kRigid : Path::kAql, why, SIXDOF_OK, plan};
@@ -1818,7 +1688,7 @@ static int prepare_batch(sixdof_handle* h, const Route& r, const StepParams& P, 
         if (r.path == Path::kAql) (void)aql_batch(h, P, b, runs);   // on failure the step takes the hipGraph path
         else if (int rc = ensure_plan_graphs(h, P, b, unused); rc != SIXDOF_OK) return rc;
     }
-    if (r.path != Path::kAql) HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (r.path != Path::kAql) HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
     return SIXDOF_OK;
 }
 
@@ -1833,7 +1703,7 @@ int prepare_graph(sixdof_handle* h) {
     if (r.path == Path::kAql) return prepare_batch(h, r, P, 2 * uint64_t(h->desc.ticks_per_launch));
     hipGraphExec_t unused = nullptr;
     int rc = ensure_graph(h, P, kGraphLen, state_only_eligible(h) ? Chain::kStateOnly : Chain::kAll, &unused);
-    if (rc == SIXDOF_OK) (void)hipStreamSynchronize(h->stream);
+    if (rc == SIXDOF_OK) (void)hipStreamSynchronize(h->stream.get());
     return rc;
 }
 
@@ -1879,20 +1749,20 @@ static int step_pair(sixdof_handle* h, uint64_t n_ticks, uint64_t* launches) {
             return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "step: the pair object was generated for the one-launch small-graph kernel (<= " +
                            std::to_string(kPairSmallMax) + " rows) but the joined graph has " + std::to_string(P.n) + " rows");
     }
-    const uint32_t K = h->hist_ring ? 1u : (small ? h->desc.ticks_per_launch : 1u << 20);
+    const uint32_t K = h->hist.ring ? 1u : (small ? h->desc.ticks_per_launch : 1u << 20);
     // the integrate kernel leaves the next tick's pack rows (this call only: PairParams::packed); the built-in small-graph
     // kernel packs in-launch
     const bool sets_packed = custom || !small;
     for (uint64_t done = 0; done < n_ticks;) {
         const uint32_t k = static_cast<uint32_t>(std::min<uint64_t>(K, n_ticks - done));
         if (custom) {
-            hipError_t e = static_cast<hipError_t>(h->pair_launch(&P, h->desc.integrator, k, small ? 1 : 0, h->stream, launches));
+            hipError_t e = static_cast<hipError_t>(h->pair_launch(&P, h->desc.integrator, k, small ? 1 : 0, h->stream.get(), launches));
             if (e != hipSuccess) return h->hip_fail(e, "custom pair launch");
         } else if (small) {
-            hipError_t e = launch_pair_small(P, h->desc.integrator, k, h->stream, launches);
+            hipError_t e = launch_pair_small(P, h->desc.integrator, k, h->stream.get(), launches);
             if (e != hipSuccess) return h->hip_fail(e, "launch_pair_small");
         } else {
-            hipError_t e = launch_pair_ticks(P, h->desc.integrator, k, h->stream, launches);
+            hipError_t e = launch_pair_ticks(P, h->desc.integrator, k, h->stream.get(), launches);
             if (e != hipSuccess) return h->hip_fail(e, "launch_pair_ticks");
         }
         done += k;
@@ -1911,9 +1781,9 @@ static int step_rigid(sixdof_handle* h, const StepParams& P, const BatchPlan& b,
         const uint64_t need = 2 * b.launches();
         if (need > 8192) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "step: TIME_EACH_LAUNCH supports <= 4096 launches per call");
         while (h->launch_events.size() < need) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(h, hipEventCreate(&e));
-            h->launch_events.push_back(e);
+            Event e;
+            HIP_TRY(h, hipEventCreate(e.out()));
+            h->launch_events.push_back(std::move(e));
         }
     }
     // one eager launch of `ticks` ticks; every launch before it ran K ticks.  State-only unless it is the accel-check launch
@@ -1923,10 +1793,10 @@ static int step_rigid(sixdof_handle* h, const StepParams& P, const BatchPlan& b,
         Q.n_ticks = ticks;
         Q.state_only = may_skip && !Q.accel_in_check && *launches + 1 < b.launches();
         Q.tick0 = Q.hist_slot0 = h->tick + *launches * K;
-        if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * *launches], h->stream));
+        if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * *launches].get(), h->stream.get()));
         hipError_t e = launch_any(h, Q);
         if (e != hipSuccess) return h->hip_fail(e, "launch_step");
-        if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * *launches + 1], h->stream));
+        if (time_each) HIP_TRY(h, hipEventRecord(h->launch_events[2 * *launches + 1].get(), h->stream.get()));
         ++*launches;
         return SIXDOF_OK;
     };
@@ -1944,9 +1814,9 @@ static int step_rigid(sixdof_handle* h, const StepParams& P, const BatchPlan& b,
         ChainReplay replays[5];
         if (int rc = ensure_plan_graphs(h, P, b, replays); rc != SIXDOF_OK) return rc;
         // a capture may just have happened after ev0 was recorded: re-record so the pair brackets real work only
-        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        HIP_TRY(h, hipEventRecord(h->ev0.get(), h->stream.get()));
         for (const ChainReplay& r : replays)
-            for (uint64_t i = 0; i < r.times; i++) HIP_TRY(h, hipGraphLaunch(r.graph, h->stream));
+            for (uint64_t i = 0; i < r.times; i++) HIP_TRY(h, hipGraphLaunch(r.graph, h->stream.get()));
         *launches += c.launches();
     }
     h->last.graph_launches = b.chains.launches();
@@ -1960,7 +1830,7 @@ static int step_aql(sixdof_handle* h, const BatchPlan& b, const aql::Run runs[kA
     Replay& rp = h->replay;
     if (!rp.aql_fault.empty()) return h->fail(SIXDOF_ERR_BACKEND, rp.aql_fault);
     // the chain bypasses the HIP stream: let what was enqueued there (and on the null stream it waits for) finish first
-    for (hipStream_t s : {h->stream, static_cast<hipStream_t>(nullptr)}) {
+    for (hipStream_t s : {h->stream.get(), static_cast<hipStream_t>(nullptr)}) {
         const hipError_t q = hipStreamQuery(s);
         if (q == hipErrorNotReady) HIP_TRY(h, hipStreamSynchronize(s));
         else if (q != hipSuccess) return h->hip_fail(q, "hipStreamQuery");
@@ -1989,19 +1859,19 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
         std::swap(h->step_pending, h->prev_pending);
         if (h->step_pending) {
             float ms_prev = 0.f;
-            HIP_TRY(h, hipEventSynchronize(h->ev1));
-            if (hipEventElapsedTime(&ms_prev, h->ev0, h->ev1) == hipSuccess) h->last.kernel_device_ms = ms_prev;
+            HIP_TRY(h, hipEventSynchronize(h->ev1.get()));
+            if (hipEventElapsedTime(&ms_prev, h->ev0.get(), h->ev1.get()) == hipSuccess) h->last.kernel_device_ms = ms_prev;
             h->step_pending = false;
         }
     }
-    if (h->hist_ring && h->copy_pending && h->stream_hi >= h->stream_lo && n_ticks) {
+    if (h->hist.ring && h->copy.pending && h->copy.stream_hi >= h->copy.stream_lo && n_ticks) {
         // ticks tick+1 .. tick+n land in slots (t-1) % ring: hold the compute stream back only if that range reaches a
         // slot the copy stream may still be reading
-        const uint64_t ring = h->hist_ring, in_flight = h->stream_hi - h->stream_lo + 1;
-        const uint64_t a = h->tick % ring, b = (h->stream_lo - 1) % ring;       // first slot written / first slot read
+        const uint64_t ring = h->hist.ring, in_flight = h->copy.stream_hi - h->copy.stream_lo + 1;
+        const uint64_t a = h->tick % ring, b = (h->copy.stream_lo - 1) % ring;       // first slot written / first slot read
         const uint64_t gap_ab = (b + ring - a) % ring, gap_ba = (a + ring - b) % ring;
         const bool overlap = n_ticks + in_flight > ring || gap_ab < std::min<uint64_t>(n_ticks, ring) || gap_ba < in_flight;
-        if (overlap) HIP_TRY(h, hipStreamWaitEvent(h->stream, h->ev_copied, 0));
+        if (overlap) HIP_TRY(h, hipStreamWaitEvent(h->stream.get(), h->copy.ev_copied.get(), 0));
     }
     if (h->desc.integrator == SIXDOF_INTEGRATOR_NONE && (!h->custom_launch || h->model != 0 || h->has_pair_op()))
         return h->fail(SIXDOF_ERR_UNSUPPORTED, "step: SIXDOF_INTEGRATOR_NONE runs generated system programs only (sixdof_set_custom_pipe)");
@@ -2012,24 +1882,24 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
     if (r.rc != SIXDOF_OK) return r.rc;
     // an AQL chain waits for itself and times itself from its packets: no event pair on the HIP stream
     const bool aql = r.path == Path::kAql;
-    if (!aql) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    if (!aql) HIP_TRY(h, hipEventRecord(h->ev0.get(), h->stream.get()));
     const int rc = aql                       ? step_aql(h, r.plan, runs, n_ticks, &launches)
                    : r.path == Path::kApollo ? step_apollo(h, n_ticks, &launches)
                    : r.path == Path::kPair   ? step_pair(h, n_ticks, &launches)
                                              : step_rigid(h, P, r.plan, n_ticks, &launches);
     if (rc != SIXDOF_OK) return rc;
-    if (!aql) HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    if (!aql) HIP_TRY(h, hipEventRecord(h->ev1.get(), h->stream.get()));
     if (!async_step && !aql) {
         // short batches finish in tens of microseconds: poll for that long before paying a blocking wait's wake-up
         const double spin_until = now_ms() + 0.25;
-        hipError_t q = hipEventQuery(h->ev1);
-        while (q == hipErrorNotReady && now_ms() < spin_until) q = hipEventQuery(h->ev1);
+        hipError_t q = hipEventQuery(h->ev1.get());
+        while (q == hipErrorNotReady && now_ms() < spin_until) q = hipEventQuery(h->ev1.get());
         if (q != hipSuccess) {
             (void)hipGetLastError();
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
         }
         float ms0 = 0.f;
-        hipEventElapsedTime(&ms0, h->ev0, h->ev1);
+        hipEventElapsedTime(&ms0, h->ev0.get(), h->ev1.get());
         h->last.kernel_device_ms = ms0;
     }
     h->tick += n_ticks;  // increment_sim_tick (globals.rs:42-44), once per tick
@@ -2041,7 +1911,7 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
     if ((h->desc.flags & SIXDOF_FLAG_TIME_EACH_LAUNCH) && !h->has_pair_op()) {
         for (uint64_t i = 0; i < launches && 2 * i + 1 < h->launch_events.size(); i++) {
             float one = 0.f;
-            if (hipEventElapsedTime(&one, h->launch_events[2 * i], h->launch_events[2 * i + 1]) == hipSuccess) h->last.kernel_sum_ms += one;
+            if (hipEventElapsedTime(&one, h->launch_events[2 * i].get(), h->launch_events[2 * i + 1].get()) == hipSuccess) h->last.kernel_sum_ms += one;
         }
     }
     if (tm) *tm = h->last;
@@ -2100,11 +1970,9 @@ void sixdof_tick(const uint8_t* const* inputs, uint8_t* const* outputs) try {
         if (in[i] == h->id_tick) std::memcpy(&tick, inputs[i], 8);
         else if (in[i] == h->id_dt) std::memcpy(&h->desc.simulation_time_step, inputs[i], 8);
         else if (Column* c = h->col(in[i])) {
-            if (c->bytes) hipMemcpyAsync(c->dev, inputs[i], c->bytes, hipMemcpyHostToDevice, h->stream);
+            if (c->bytes) hipMemcpyAsync(c->dev.get(), inputs[i], c->bytes, hipMemcpyHostToDevice, h->stream.get());
             if (in[i] == h->id_accel) h->accel_is_host_data = true;   // a_in is host data on every TickFn call (rk4.rs:96-100)
-            if (c->joined && c->compact)
-                launch_gather_rows(c->compact, c->dev, c->d_rows, static_cast<uint32_t>(h->joined_ids.size()),
-                                   static_cast<uint32_t>(c->width), c->elem, h->stream);
+            (void)gather_joined(h, c);
         }
     }
     h->tick = tick;
@@ -2117,10 +1985,10 @@ void sixdof_tick(const uint8_t* const* inputs, uint8_t* const* outputs) try {
         else if (out[i] == h->id_dt) std::memcpy(outputs[i], &h->desc.simulation_time_step, 8);
         else if (Column* c = h->col(out[i])) {
             scatter_back(h, c);
-            if (c->bytes) hipMemcpyAsync(outputs[i], c->dev, c->bytes, hipMemcpyDeviceToHost, h->stream);
+            if (c->bytes) hipMemcpyAsync(outputs[i], c->dev.get(), c->bytes, hipMemcpyDeviceToHost, h->stream.get());
         }
     }
-    hipStreamSynchronize(h->stream);
+    hipStreamSynchronize(h->stream.get());
 } SIXDOF_ABI_CATCH_VALUE(err_of(g_tick_handle), )      // TickFn returns nothing: the message is on the bound handle
 
 }  // extern "C"

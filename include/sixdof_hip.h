@@ -215,10 +215,13 @@ int sixdof_create(const sixdof_desc* desc, sixdof_handle** out);
 void sixdof_destroy(sixdof_handle* h);
 const char* sixdof_last_error(const sixdof_handle* h); /* h may be NULL: last create error */
 
+/* Same-size columns keep their device copies.  A failed call (after the argument check) leaves the handle UNBOUND: every
+ * column bound so far owns valid device memory or none, step / upload / download refuse, and a later bind succeeds. */
 int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_cols);
 int sixdof_set_effectors(sixdof_handle* h, const sixdof_effector_op* ops, size_t n_ops);
 /* Edges as (from entity id, to entity id) in spawn order; resolved to row indices against the
- * bound Body entity ids (query.rs:599-621 gathers by constant u32 indices). */
+ * bound Body entity ids (query.rs:599-621 gathers by constant u32 indices).  The new tables are built next to the old
+ * ones and swapped in last: a failed call leaves the handle's edges (sixdof_get_edge_rows, what the step reads) unchanged. */
 int sixdof_set_edges(sixdof_handle* h, const uint64_t* from_ids, const uint64_t* to_ids, size_t n_edges);
 /* Join tables: row of joined entity j inside column `component_id` — the constant u32 gather indices the
  * reference bakes at compile time (query.rs:599-621).  six_dof runs over the INTERSECTION of the Body columns'
@@ -243,7 +246,9 @@ int sixdof_download(sixdof_handle* h, uint32_t column_mask);
  * copies the snapshot into the bound host buffers on a second stream; the host buffers are page-locked on
  * first use (hipHostRegister) so the copy is a real DMA.  The next sixdof_step may be issued immediately.
  * download_wait blocks until the host buffers hold that snapshot.  One snapshot in flight: a second
- * download_async first waits (on the device) for the previous copy to have left the snapshot buffers. */
+ * download_async first waits (on the device) for the previous copy to have left the snapshot buffers.
+ * The copy stream and its two events are created on first use, all three or none: a call that fails there (or anywhere
+ * else) leaves nothing pending and the next call starts afresh. */
 int sixdof_download_async(sixdof_handle* h, uint32_t column_mask);
 int sixdof_download_wait(sixdof_handle* h);
 int sixdof_sync(sixdof_handle* h);   /* both streams idle */
@@ -385,7 +390,9 @@ int sixdof_build_fold_table(const uint32_t* src_rows, const uint32_t* dst_rows, 
  * (sixdof_set_custom_pipe) every component column of the program is recorded the same way and can be read
  * back by its component id.  Worlds stepped by the pair (edge_fold / all-pairs) kernels or by a rollout model are
  * recorded too: with a ring enabled they run one tick per launch and the four output columns are copied into the
- * tick's slot on the device (the model's own columns are not recorded).  ring_ticks = 0 disables and frees the ring. */
+ * tick's slot on the device (the model's own columns are not recorded).  ring_ticks = 0 disables and frees the ring.
+ * The previous ring is freed FIRST (rings can be gigabytes).  A failed call, a component ring's allocation included,
+ * leaves NO ring: every ring buffer is freed and the history calls answer as before the first sixdof_set_history. */
 int sixdof_set_history(sixdof_handle* h, uint32_t ring_ticks);
 /* Copy the [n,w] block of `component_id` as it was after `tick` ticks into host_dst.  Fails with
  * SIXDOF_ERR_INVALID_ARGUMENT if that tick is not (or no longer) in the ring. */
@@ -396,7 +403,9 @@ int sixdof_history_read(sixdof_handle* h, uint64_t component_id, uint64_t tick, 
  * once the copies are enqueued; sixdof_download_wait blocks until they have landed.  With SIXDOF_FLAG_ASYNC_STEP and a
  * ring of at least two batches the copy of batch i overlaps the compute of batch i+1: a later sixdof_step only waits
  * (on the device) when it is about to overwrite ring slots that are still being read.  The host buffers must stay
- * allocated until sixdof_sync, which also releases their page locks. */
+ * allocated until sixdof_sync, which also releases their page locks.  A failed call: the copy lane as for
+ * sixdof_download_async (whole or absent); copies already enqueued may still land, so the buffers stay allocated until
+ * sixdof_sync all the same; the ring is untouched and the call may be repeated. */
 int sixdof_history_stream(sixdof_handle* h, uint64_t first_tick, uint64_t n_ticks, void* const host_dst[4]);
 
 /* ---- watch lists: time series of chosen (entity, component) pairs out of the ring ----------------------------
@@ -419,7 +428,9 @@ int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_c
  * have landed, and the buffers must stay allocated until sixdof_sync, as for sixdof_history_stream.  Either way the ring
  * is read on the compute stream, so a later sixdof_step may overwrite the slots without waiting for the copy.
  * n_samples = 0 is a no-op.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied: no watch, no ring, every = 0, or a
- * sampled tick that is not (or no longer) in the ring. */
+ * sampled tick that is not (or no longer) in the ring.  A call that fails in the runtime leaves the watch and the ring as
+ * they were; if the staging buffer could not be grown there is none (size 0) and the next read allocates it again; the
+ * copy lane as for sixdof_download_async.  host_dst of a failed asynchronous read stays allocated until sixdof_sync. */
 int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples, uint64_t every, void* const host_dst[],
                       uint32_t flags);
 
