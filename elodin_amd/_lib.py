@@ -25,6 +25,8 @@ FLAG_USE_GRAPH = 1
 FLAG_TIME_EACH_LAUNCH = 2
 FLAG_ASYNC_STEP = 4
 WATCH_ASYNC = 1      # sixdof_watch_read flags
+ENVELOPE_ASYNC = 1   # sixdof_history_envelope flags
+ENVELOPE_MAX_BINS = 512   # period * width one call reduces (csrc/envelope_plan.hpp: kEnvelopeMaxBins)
 
 EFF_CONST_WRENCH = 1
 EFF_UNIFORM_GRAVITY = 2
@@ -139,6 +141,8 @@ SYMBOLS = {
     "sixdof_history_stream": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]),
     "sixdof_set_watch": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t]),
     "sixdof_watch_read": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.c_uint32]),
+    "sixdof_history_envelope": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                          C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_set_model_apollo": (C.c_int, [_H, C.c_void_p]),
     "sixdof_download_column": (C.c_int, [_H, C.c_uint64]),
     "sixdof_upload_column": (C.c_int, [_H, C.c_uint64]),

@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import enum
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence
 
 import os
 import numpy as np
@@ -819,6 +819,29 @@ class Exec:
         for key, (e, comp) in zip(keys, pairs):
             series = np.array(blocks[comp][ents.index(e)], dtype=np.float64)
             out[key] = series[:, 0] if series.shape[1] == 1 else series
+        return out
+
+    def history_envelope(self, components, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> Dict[str, Any]:
+        """The dispersion of ALL entities over time: {"time": seconds, component: {"count", "min", "max", "mean", "m2", "std":
+        [samples, period, w]}} for world ticks first_tick, first_tick + every, ... <= last_tick, reduced on the device out of the
+        ring (enable_history) — five numbers per element and tick cross the link, not every row.  Entry [j, g, c] covers
+        element c of the executor rows r with r % period == g; non-finite elements are skipped and show in count."""
+        comps = [components] if isinstance(components, str) else list(components)
+        side = getattr(self, "_side", None)
+        for comp in comps:
+            if side is not None and comp in side._world._components:
+                raise NotImplementedError(f"history_envelope: {comp}: {comp} also lives on entities stepped by a side executor")
+            if comp in getattr(self, "_partial", {}):
+                raise NotImplementedError(f"history_envelope: {comp}: {comp} lives on fewer entities than the executor's rows")
+            if comp in getattr(self._hip, "_windows", {}):
+                raise NotImplementedError(f"history_envelope: {comp}: {comp} is a window component, the ring does not copy it per tick")
+        s = getattr(self, "_substeps", 1)
+        first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
+        if every < 1:
+            raise ValueError("history_envelope: every must be at least 1")
+        last_sample = first_tick + (last_tick - first_tick) // every * every if last_tick >= first_tick else first_tick - 1
+        out: Dict[str, Any] = dict(self._hip.history_envelope(comps, first_tick * s, last_sample * s, every * s, period))
+        out["time"] = np.arange(first_tick, last_sample + 1, every, dtype=np.float64) * self._dt
         return out
 
     def column_ids(self, name: str) -> np.ndarray:

@@ -15,9 +15,12 @@
 #include <map>
 #include <set>
 #include <string>
+#include <vector>
 
 #include "../../include/sixdof_hip.h"
 #include "aql_chain.hpp"
+#include "envelope_plan.hpp"
+#include "history_plan.hpp"
 #include "kernels.hpp"
 
 namespace hip_fake {
@@ -181,7 +184,22 @@ static bool pair_ok(const PairParams& p) {
 }
 
 StepKernel select_step(const StepParams&, int, int) { return {}; }
-hipError_t launch_step(const StepParams& p, int, int dtype, hipStream_t) { return launch(step_ok(p, dtype)); }
+// no arithmetic, but a recording launch leaves the (unchanged) Body columns in the ring slots of its ticks, as the kernel does:
+// what reads the ring (history_read, watch_read, history_envelope) then sees what was uploaded before the step
+hipError_t launch_step(const StepParams& p, int, int dtype, hipStream_t) {
+    const bool ok = step_ok(p, dtype);
+    if (ok && p.hist_ring && p.hist_pos) {
+        const size_t es = dtype == 1 ? 4 : 8;
+        const void* live_col[4] = {p.pos, p.vel, p.accel, p.force};
+        void* rings[4] = {p.hist_pos, p.hist_vel, p.hist_accel, p.hist_force};
+        for (uint32_t t = 0; t < p.n_ticks; t++)
+            for (int k = 0; k < 4; k++) {
+                const size_t block = size_t(p.n) * (k == 0 ? 7 : 6) * es;
+                std::memcpy(static_cast<char*>(rings[k]) + (p.hist_slot0 + t) % p.hist_ring * block, live_col[k], block);
+            }
+    }
+    return launch(ok);
+}
 uint32_t pair_splits_for(uint32_t) { return 1; }
 hipError_t launch_pair_ticks(const PairParams& p, int, uint32_t n_ticks, hipStream_t, uint64_t* launches) { return *launches += 1 + 2 * n_ticks, launch(pair_ok(p)); }
 hipError_t launch_pair_small(const PairParams& p, int, uint32_t, hipStream_t, uint64_t* launches) { return *launches += 1, launch(pair_ok(p)); }
@@ -216,6 +234,50 @@ hipError_t launch_history_gather(const HistoryGatherArgs& a, uint32_t n_componen
                 if (!need(live(from, row) && live(to, row), "ring or watch staging")) return launch(false);
                 std::memcpy(to, from, row);
             }
+    }
+    return launch(true);
+}
+// the reduction itself (envelope_kernels.hip), serially: envelope_plan.hpp's arithmetic in the kernels' geometry and merge order
+hipError_t launch_history_envelope(const EnvelopeArgs& a, uint32_t n_components, double* out, void* partial, uint64_t partial_stride, uint64_t n,
+                                   uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring,
+                                   size_t elem, hipStream_t) {
+    if (n_components == 0 || n_components > kEnvelopeMaxComponents || n_samples > 65535 || period == 0) return launch(false);
+    EnvelopePartial* part = static_cast<EnvelopePartial*>(partial);
+    if (!need(live(part, n_samples * partial_stride * sizeof(EnvelopePartial)), "envelope partial records")) return launch(false);
+    std::vector<EnvelopePartial> rec(kEnvelopeThreads);
+    for (uint32_t k = 0; k < n_components && n; k++) {
+        const EnvelopeDesc& d = a.c[k];
+        if (!envelope_supported(d.w, period)) return launch(false);
+        const EnvelopeGeom g = envelope_geom(n, d.w, period);
+        const uint64_t total = n * d.w;
+        if (!need(d.partial_offset + uint64_t(g.blocks) * g.bins <= partial_stride, "envelope partial records of one sample")) return launch(false);
+        for (uint64_t j = 0; j < n_samples; j++) {
+            const char* src = static_cast<const char*>(d.ring) + sample_slot(first_tick, sample0 + j, every, ring) * total * elem;
+            double* to = out + d.out_offset + (sample0 + j) * period * kEnvelopeStats * d.w;
+            if (!need(live(src, total * elem) && live(to, size_t(period) * kEnvelopeStats * d.w * sizeof(double)), "ring or envelope staging")) return launch(false);
+            EnvelopePartial* mine = part + j * partial_stride + d.partial_offset;
+            for (uint32_t b = 0; b < g.blocks; b++) {                       // stage 1
+                for (uint32_t t = 0; t < g.tile; t++) {
+                    EnvelopePartial acc = envelope_empty();
+                    for (uint64_t i = uint64_t(b) * g.tile + t; i < total; i += uint64_t(g.blocks) * g.tile) {
+                        double x;
+                        if (elem == 8) std::memcpy(&x, src + i * 8, 8);
+                        else { float f; std::memcpy(&f, src + i * 4, 4); x = f; }
+                        envelope_accumulate(acc, x);
+                    }
+                    rec[t] = acc;
+                }
+                for (uint32_t bin = 0; bin < g.bins; bin++) {
+                    envelope_tree_fold(&rec[bin], g.per_bin, g.bins);
+                    mine[uint64_t(b) * g.bins + bin] = rec[bin];
+                }
+            }
+            for (uint32_t bin = 0; bin < g.bins; bin++) {                   // stage 2
+                EnvelopePartial r = mine[bin];
+                for (uint32_t b = 1; b < g.blocks; b++) r = envelope_merge(r, mine[uint64_t(b) * g.bins + bin]);
+                envelope_emit(r, to + uint64_t(bin / d.w) * kEnvelopeStats * d.w + bin % d.w, d.w);
+            }
+        }
     }
     return launch(true);
 }

@@ -158,6 +158,23 @@ hipError_t launch_history_gather(const HistoryGatherArgs& a, uint32_t n_componen
                                  uint64_t m, uint64_t n, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                                  uint64_t ring, size_t elem, hipStream_t s);
 
+// ---- ring envelopes: count / min / max / mean / m2 across the rows of every sampled tick (envelope_kernels.hip) -----
+constexpr uint32_t kEnvelopeMaxComponents = 32;   // components one launch covers (blockIdx.z)
+struct EnvelopeDesc {
+    const void* ring;         // [ring][n, w] blocks of this component
+    uint64_t out_offset;      // where its [n_samples][period][5][w] block starts in `out`, in doubles
+    uint64_t partial_offset;  // where its [blocks][period * w] records of one sample start in a sample's partial records
+    uint32_t w;
+    uint32_t reserved;
+};
+struct EnvelopeArgs { EnvelopeDesc c[kEnvelopeMaxComponents]; };   // by value: 1 KiB of kernel arguments
+// Samples sample0 .. sample0 + n_samples - 1 (n_samples < 65,536) of the range first_tick, first_tick + every, ...: stage 1 writes
+// `partial_stride` records (envelope_plan.hpp: EnvelopePartial) per sample into `partial`, stage 2 merges them in index order into
+// `out`.  The caller has validated the range (sampled_range_ok), n % period == 0 and envelope_supported(w, period).
+hipError_t launch_history_envelope(const EnvelopeArgs& a, uint32_t n_components, double* out, void* partial, uint64_t partial_stride,
+                                   uint64_t n, uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples,
+                                   uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
+
 hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags,
                             unsigned long long* count, hipStream_t s);
 

@@ -30,6 +30,7 @@
 #include "abi_guard.hpp"
 #include "device_mem.hpp"
 #include "aql_chain.hpp"
+#include "envelope_plan.hpp"
 #include "history_plan.hpp"
 #include "step_plan.hpp"
 
@@ -152,6 +153,8 @@ struct History {
     uint64_t first_tick = 0;          // first tick (1-based count) recorded since the ring was enabled
     DeviceBuffer body[4];             // pos, vel, accel, force
     std::vector<DeviceBuffer> model;  // one ring per component column of a generated program (same order as custom_model; empty: not recorded)
+    // sixdof_history_envelope: device staging of one read's output and the stage-1 partial records, grown lazily, freed with the ring
+    DeviceBuffer env_stage, env_partial;
     void reset() { *this = History{}; }
 };
 
@@ -1441,6 +1444,101 @@ int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples,
         if (!parts[k].bytes) continue;
         lane.pin(host_dst[k], parts[k].bytes);
         HIP_TRY(h, hipMemcpyAsync(host_dst[k], staged + parts[k].offset, parts[k].bytes, hipMemcpyDeviceToHost, lane.stream.get()));
+    }
+    // re-recorded behind whatever the copy stream already carried: one sixdof_download_wait covers a history_stream copy too
+    HIP_TRY(h, hipEventRecord(lane.ev_copied.get(), lane.stream.get()));
+    lane.pending = true;
+    return SIXDOF_OK;
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// The envelopes of sampled ticks: ordering, ring reads and the copy lane exactly as for sixdof_watch_read above — the two
+// reduction launches go on the compute stream behind the batch that recorded the ticks, only the staging buffer is read from
+// the copy stream.  Stateless: components and widths are looked up per call.
+int sixdof_history_envelope(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
+                            uint64_t n_samples, uint64_t every, uint32_t period, double* const host_dst[], uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    if (flags & ~SIXDOF_ENVELOPE_ASYNC) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: unknown flags");
+    if (!h->hist.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: no history ring (sixdof_set_history)");
+    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: every must be at least 1");
+    if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: period must be at least 1");
+    const uint64_t n = h->desc.n_entities;
+    if (n % period != 0)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+    if (n_samples == 0 || n_components == 0) return SIXDOF_OK;
+    if (!component_ids || !host_dst) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: null argument");
+    if (!sampled_range_ok(first_tick, n_samples, every, h->hist.first_tick, h->tick, h->hist.ring))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: ticks are not (all) in the ring");
+    // per component: ring base and width as they are NOW, its block in the staging buffer and its records in a sample's partials
+    struct Part { const void* ring; size_t w, doubles, offset, partial_offset; };
+    std::vector<Part> parts(n_components);
+    size_t stage = 0, partial_stride = 0, launch_records = 0;
+    for (size_t k = 0; k < n_components; k++) {
+        Part& p = parts[k];
+        if (!watch_lookup(h, component_ids[k], &p.ring, &p.w) || !p.ring)
+            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "history_envelope: only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
+        if (!host_dst[k]) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: null host buffer");
+        if (!envelope_supported(p.w, period))
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: period " + std::to_string(period) + " x width " + std::to_string(p.w) +
+                                                            " exceeds the " + std::to_string(kEnvelopeMaxBins) + " (group, element) bins one block keeps apart");
+        const EnvelopeGeom g = envelope_geom(n, static_cast<uint32_t>(p.w), period);
+        p.doubles = static_cast<size_t>(n_samples) * period * kEnvelopeStats * p.w;
+        p.offset = stage;
+        stage += (p.doubles + 31) / 32 * 32;              // 256-byte aligned blocks
+        if (k % kEnvelopeMaxComponents == 0) launch_records = 0;   // every launch of at most 32 components reuses the records
+        p.partial_offset = launch_records;
+        launch_records += static_cast<size_t>(g.blocks) * g.bins;
+        partial_stride = std::max(partial_stride, launch_records);
+    }
+    if (n == 0) {      // nothing to reduce: count 0, statistics NaN
+        for (size_t k = 0; k < n_components; k++)
+            for (size_t i = 0; i < parts[k].doubles; i++) host_dst[k][i] = i / parts[k].w % kEnvelopeStats == 0 ? 0.0 : std::nan("");
+        return SIXDOF_OK;
+    }
+    // samples per launch: the partial records of one launch stay within a fixed budget, and the grid's y extent below 2^16
+    constexpr size_t kPartialBudget = size_t(64) << 20;
+    const size_t per_sample = partial_stride * sizeof(EnvelopePartial);
+    const uint64_t chunk = std::min<uint64_t>({n_samples, 65535, std::max<size_t>(1, kPartialBudget / per_sample)});
+    HIP_TRY(h, hipSetDevice(h->device));
+    const bool async = (flags & SIXDOF_ENVELOPE_ASYNC) != 0;
+    CopyLane& lane = h->copy;
+    if (async) HIP_TRY(h, lane.ensure());
+    History& hs = h->hist;
+    if (stage * sizeof(double) > hs.env_stage.bytes() || chunk * per_sample > hs.env_partial.bytes()) {
+        // the copy stream may still read the old staging buffer (a previous asynchronous read), the compute stream may still use both
+        if (lane.pending) HIP_TRY(h, hipStreamSynchronize(lane.stream.get()));
+        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
+        if (stage * sizeof(double) > hs.env_stage.bytes()) HIP_TRY(h, hs.env_stage.alloc(stage * sizeof(double)));   // free first; on failure empty
+        if (chunk * per_sample > hs.env_partial.bytes()) HIP_TRY(h, hs.env_partial.alloc(chunk * per_sample));
+    }
+    // one staging buffer: the previous asynchronous read's copies must have drained it before it is overwritten (device-side wait)
+    if (lane.pending) HIP_TRY(h, hipStreamWaitEvent(h->stream.get(), lane.ev_copied.get(), 0));
+    for (size_t k0 = 0; k0 < n_components; k0 += kEnvelopeMaxComponents) {
+        const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kEnvelopeMaxComponents, n_components - k0));
+        EnvelopeArgs a{};
+        for (uint32_t k = 0; k < cnt; k++) {
+            a.c[k].ring = parts[k0 + k].ring;
+            a.c[k].out_offset = parts[k0 + k].offset;
+            a.c[k].partial_offset = parts[k0 + k].partial_offset;
+            a.c[k].w = static_cast<uint32_t>(parts[k0 + k].w);
+        }
+        for (uint64_t s0 = 0; s0 < n_samples; s0 += chunk) {
+            hipError_t e = launch_history_envelope(a, cnt, hs.env_stage.get<double>(), hs.env_partial.get(), partial_stride, n, period, first_tick, s0,
+                                                   std::min<uint64_t>(chunk, n_samples - s0), every, hs.ring, h->elem_size(), h->stream.get());
+            if (e != hipSuccess) return h->hip_fail(e, "history_envelope");
+        }
+    }
+    const double* staged = hs.env_stage.get<double>();
+    if (!async) {
+        for (size_t k = 0; k < n_components; k++)
+            HIP_TRY(h, hipMemcpyAsync(host_dst[k], staged + parts[k].offset, parts[k].doubles * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
+        return SIXDOF_OK;
+    }
+    HIP_TRY(h, hipEventRecord(lane.ev_snap.get(), h->stream.get()));            // the envelopes are in the staging buffer after this
+    HIP_TRY(h, hipStreamWaitEvent(lane.stream.get(), lane.ev_snap.get(), 0));
+    for (size_t k = 0; k < n_components; k++) {
+        lane.pin(host_dst[k], parts[k].doubles * sizeof(double));
+        HIP_TRY(h, hipMemcpyAsync(host_dst[k], staged + parts[k].offset, parts[k].doubles * sizeof(double), hipMemcpyDeviceToHost, lane.stream.get()));
     }
     // re-recorded behind whatever the copy stream already carried: one sixdof_download_wait covers a history_stream copy too
     HIP_TRY(h, hipEventRecord(lane.ev_copied.get(), lane.stream.get()));

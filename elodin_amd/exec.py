@@ -553,6 +553,89 @@ class HipExec:
             self.sync()          # also drops the page locks on `bufs` before they go out of scope
         return time.perf_counter() - t0
 
+    # ---- ring envelopes: count / min / max / mean / spread across the rows of every sampled tick -------------------
+    ENVELOPE_STATS = ("count", "min", "max", "mean", "m2")
+
+    def _envelope_buffers(self, names, n_samples: int, period: int):
+        for name in names:
+            if name in self._windows:
+                raise ValueError(f"{name} is a window component: it is its own history (HipExec.component), the ring does not copy it per tick")
+        width = lambda name: 7 if name == "world_pos" else (self._aux[name].shape[1] if name in self._aux else 6)
+        raw = [np.empty((n_samples, max(period, 1), 5, width(name)), dtype=np.float64) for name in names]
+        ptrs = (C.c_void_p * max(1, len(names)))(*[a.ctypes.data for a in raw])
+        comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
+        return raw, ptrs, comp
+
+    @classmethod
+    def _envelope_dict(cls, names, raw) -> dict:
+        """[s, period, 5, w] blocks -> {name: {statistic: [s, period, w]}}, count as int64, std = sqrt(m2 / count) added."""
+        out = {}
+        for name, a in zip(names, raw):
+            d = {k: a[:, :, i, :] for i, k in enumerate(cls.ENVELOPE_STATS)}
+            with np.errstate(invalid="ignore", divide="ignore"):
+                d["std"] = np.sqrt(d["m2"] / d["count"])
+            d["count"] = d["count"].astype(np.int64)
+            out[name] = d
+        return out
+
+    def history_envelope(self, names: Sequence[str], first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> dict:
+        """{name: {"count": int64 [s, period, w], "min", "max", "mean", "m2", "std": f64 [s, period, w]}} over the rows of ticks
+        first_tick, first_tick + every, ... <= last_tick, reduced on the device out of the ring: entry [j, g, c] covers element c
+        of the rows r with r % period == g (period = 1: all rows).  Non-finite elements are skipped and show as count below
+        n / period; count == 0 leaves the statistics NaN.  Accumulated in f64; m2 is the sum of squared deviations from the mean
+        and std = sqrt(m2 / count).  Stateless: no watch is involved."""
+        names = [names] if isinstance(names, str) else list(names)
+        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
+        n_samples = (last_tick - first_tick) // every + 1 if every > 0 and last_tick >= first_tick else 0
+        raw, ptrs, comp = self._envelope_buffers(names, n_samples, period)
+        rc = self._lib.sixdof_history_envelope(self._h, comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), first_tick, n_samples, every,
+                                               max(period, 0), ptrs, 0)
+        if rc != L.OK:
+            _raise(self._h, rc, "sixdof_history_envelope")
+        return self._envelope_dict(names, raw)
+
+    def stream_envelope(self, names: Sequence[str], n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, consume=None,
+                        flags: int = 0) -> float:
+        """stream_series for envelopes: every `every`-th tick of every batch reduced on the compute stream and copied on the copy
+        stream into one of two host buffer sets while the next batch computes; a ring one batch deep is enough (enabled here
+        unless enable_history already made one at least that large).  `consume(batch_index, first_tick, {name: {statistic:
+        [ticks_per_batch // every, period, w]}})` sees a batch once it has landed — first_tick is the batch's first SAMPLED
+        tick; the arrays are views of buffers reused two batches later.  Returns the wall time in seconds."""
+        import time
+        names = [names] if isinstance(names, str) else list(names)
+        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
+        if every < 1 or ticks_per_batch < 1 or ticks_per_batch % every != 0:
+            raise ValueError(f"stream_envelope: ticks_per_batch ({ticks_per_batch}) must be a positive multiple of every ({every})")
+        if period < 1:
+            raise ValueError("stream_envelope: period must be at least 1")
+        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
+            self.enable_history(ticks_per_batch)
+        n_samples = ticks_per_batch // every
+        raw, ptrs, comps = zip(*[self._envelope_buffers(names, n_samples, period) for _ in range(2)])
+        comp_p = comps[0].ctypes.data_as(C.POINTER(C.c_uint64))
+        self.sync()              # nothing of an earlier streaming run is in flight
+        self.set_flags(flags | L.FLAG_ASYNC_STEP)
+        t0 = time.perf_counter()
+        try:
+            first = []
+            for i in range(n_batches):
+                first.append(self.tick + every)                          # samples end on the batch's last tick
+                self.invoke_batch(ticks_per_batch)                       # enqueue batch i
+                if i > 0:
+                    self.download_wait()                                 # batch i-1 has landed in raw[(i-1) % 2]
+                    if consume is not None:
+                        consume(i - 1, first[i - 1], self._envelope_dict(names, raw[(i - 1) % 2]))
+                rc = self._lib.sixdof_history_envelope(self._h, comp_p, len(names), first[i], n_samples, every, period, ptrs[i % 2], L.ENVELOPE_ASYNC)
+                if rc != L.OK:
+                    _raise(self._h, rc, "sixdof_history_envelope")
+            self.download_wait()
+            if consume is not None and n_batches:
+                consume(n_batches - 1, first[-1], self._envelope_dict(names, raw[(n_batches - 1) % 2]))
+        finally:
+            self.set_flags(flags)
+            self.sync()          # also drops the page locks on `raw` before they go out of scope
+        return time.perf_counter() - t0
+
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))
 

@@ -310,6 +310,13 @@ class Campaign:
         """[n_runs * entities carrying it, w] rows of a component, run-major."""
         return np.asarray(self.exec.column_array(component))
 
+    def envelope(self, components, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
+        """The dispersion of the runs over time, out of the device ring (self.exec.enable_history): {"time": seconds, component:
+        {"count", "min", "max", "mean", "m2", "std": [sample, entity-of-run, w]}} over world ticks first_tick, first_tick + every,
+        ... <= last_tick.  Runs are entities_per_run consecutive rows, so entry [j, e, c] is taken over entity e of every run;
+        a diverged run's non-finite elements are skipped and show as count below n_runs."""
+        return self.exec.history_envelope(components, first_tick, last_tick, every, period=self.entities_per_run)
+
     def result_table(self, names: Sequence[str]) -> np.ndarray:
         """The runs' `el.monte_carlo.result(...)` records as [n_runs, len(names)] (NaN where a run reported nothing)."""
         out = np.full((self.n_runs, len(names)), np.nan)

@@ -434,6 +434,30 @@ int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_c
 int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples, uint64_t every, void* const host_dst[],
                       uint32_t flags);
 
+/* ---- ring envelopes: the dispersion of ALL rows over time ------------------------------------------------------
+ * What a dispersion plot or a go/no-go table of a campaign wants per tick and component element is how many runs are still
+ * finite, their minimum, maximum, mean and spread — five numbers, reduced on the device, not n rows.
+ *
+ * For sample j (the state after tick first_tick + j * every), component k (the ones sixdof_history_read accepts; anything
+ * else: SIXDOF_ERR_COMPONENT_NOT_FOUND) and group g < period, the rows r with r % period == g are reduced per element c < w_k.
+ * period = 1: all rows; period = E: entity e of every run of a campaign whose runs are E consecutive rows.  host_dst[k]
+ * receives [n_samples][period][5][w_k] doubles, the five in the order count, min, max, mean, m2:
+ *   count   elements that are finite (non-finite elements are skipped, never propagated; count < rows / period shows them)
+ *   min max mean   over those elements;  m2 = sum (x - mean)^2 over them (variance = m2 / count).  count = 0: all four NaN.
+ * Accumulated in f64 whatever the handle's dtype.  No floating-point atomics; the launch geometry and merge order depend on
+ * (n, w_k, period) only, so the values of one (tick, component) are bit-identical whichever range, `every`, component list or
+ * flags read them.
+ * flags = 0: returns when the data is in host_dst.  SIXDOF_ENVELOPE_ASYNC: the rules of SIXDOF_WATCH_ASYNC — the copies go on the
+ * copy stream, sixdof_download_wait blocks until they have landed, host_dst stays allocated (and page-locked) until
+ * sixdof_sync.  Either way the ring is read on the compute stream: a later sixdof_step may overwrite the slots at once.
+ * n_samples = 0 is a no-op.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied: no ring, every = 0, period = 0, a row count that
+ * is no multiple of period, period * w_k above 512 (the bins one block of the kernel keeps apart), a sampled tick that is
+ * not (or no longer) in the ring, unknown flags, a null buffer.  A call that fails in the runtime leaves the ring as it was; a
+ * staging or partial buffer that could not be grown is absent (size 0) and the next call allocates it again. */
+#define SIXDOF_ENVELOPE_ASYNC 1u
+int sixdof_history_envelope(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
+                            uint64_t n_samples, uint64_t every, uint32_t period, double* const host_dst[], uint32_t flags);
+
 /* ---- rollout models: systems piped AROUND six_dof, fused with it (the pipes of examples/<name>/sim.py) ------------- */
 struct sixdof_apollo_tables; /* include/sixdof_apollo.h */
 /* Select the Apollo-lander rollout model (examples/apollo-lander/sim.py:517-526 + the guidance sidecar
