@@ -781,6 +781,16 @@ class Exec:
         """Keep the last `ring_ticks` world ticks of every recorded column in the device ring history_series reads."""
         self._hip.enable_history(int(ring_ticks) * getattr(self, "_substeps", 1))
 
+    def _refuse_unrecorded(self, who: str, what: str, comp: str) -> None:
+        """The ring of the main executor holds one row per executor row of `comp`, every tick: not so for these."""
+        side = getattr(self, "_side", None)
+        if side is not None and comp in side._world._components:
+            raise NotImplementedError(f"{who}: {what}: {comp} also lives on entities stepped by a side executor")
+        if comp in getattr(self, "_partial", {}):
+            raise NotImplementedError(f"{who}: {what}: {comp} lives on fewer entities than the executor's rows")
+        if comp in getattr(self._hip, "_windows", {}):
+            raise NotImplementedError(f"{who}: {what}: {comp} is a window component, the ring does not copy it per tick")
+
     def history_series(self, keys, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, np.ndarray]:
         """The dict shape of history() — "time" plus one series per "entity.component" key — for world ticks first_tick,
         first_tick + every, ... <= last_tick, read out of the device ring (enable_history) through a watch list: only the
@@ -788,17 +798,11 @@ class Exec:
         watch (HipExec.set_watch) when the keys differ from the previous call's."""
         keys = [keys] if isinstance(keys, str) else list(keys)
         by_name = {v: k for k, v in self._world._names.items()}
-        side = getattr(self, "_side", None)
         hip_ids = {int(e) for e in self._hip.entity_ids}
         pairs = []
         for key in keys:
             ent, _, comp = key.partition(".")
-            if side is not None and comp in side._world._components:
-                raise NotImplementedError(f"history_series: {key}: {comp} also lives on entities stepped by a side executor")
-            if comp in getattr(self, "_partial", {}):
-                raise NotImplementedError(f"history_series: {key}: {comp} lives on fewer entities than the executor's rows")
-            if comp in getattr(self._hip, "_windows", {}):
-                raise NotImplementedError(f"history_series: {key}: {comp} is a window component, the ring does not copy it per tick")
+            self._refuse_unrecorded("history_series", key, comp)
             if ent not in by_name or int(by_name[ent]) not in hip_ids:
                 raise KeyError(key)
             pairs.append((int(by_name[ent]), comp))
@@ -827,14 +831,8 @@ class Exec:
         ring (enable_history) — five numbers per element and tick cross the link, not every row.  Entry [j, g, c] covers
         element c of the executor rows r with r % period == g; non-finite elements are skipped and show in count."""
         comps = [components] if isinstance(components, str) else list(components)
-        side = getattr(self, "_side", None)
         for comp in comps:
-            if side is not None and comp in side._world._components:
-                raise NotImplementedError(f"history_envelope: {comp}: {comp} also lives on entities stepped by a side executor")
-            if comp in getattr(self, "_partial", {}):
-                raise NotImplementedError(f"history_envelope: {comp}: {comp} lives on fewer entities than the executor's rows")
-            if comp in getattr(self._hip, "_windows", {}):
-                raise NotImplementedError(f"history_envelope: {comp}: {comp} is a window component, the ring does not copy it per tick")
+            self._refuse_unrecorded("history_envelope", comp, comp)
         s = getattr(self, "_substeps", 1)
         first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
         if every < 1:

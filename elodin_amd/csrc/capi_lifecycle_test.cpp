@@ -198,7 +198,7 @@ struct Bound {
 // sixdof_download_async must work.
 void case_copy_lane() {
     Bound b;
-    hip_fake::fail_after(1);   // 0: the copy stream, 1: its first event
+    hip_fake::fail_after(2 * 5 + 1);   // the five snapshots (allocation, device copy) come first; then 10: the copy stream, 11: its first event
     if (sixdof_download_async(b.h, SIXDOF_COL_ALL) == SIXDOF_OK || !hip_fake::fired()) complain("copy lane: the injected fault did not fail download_async");
     hip_fake::fail_after(-1);
     if (sixdof_download_async(b.h, SIXDOF_COL_ALL) != SIXDOF_OK) complain(std::string("copy lane: download_async does not work on the retry: ") + sixdof_last_error(b.h));

@@ -5,7 +5,8 @@
 // The ring is filled through the pair path, whose per-tick device copies the fake performs (f32: by the fake's recording step
 // launch): before every one-tick step the host columns are rewritten and uploaded, so tick t holds what upload t carried.  Checked: the values against a long-double
 // two-pass reference, every refusal with nothing copied, bit-identity of a range's samples with single-sample reads, and
-// every fallible runtime call of the entry point failed once.
+// every fallible runtime call of the entry point failed once.  The readers that share its copy lane and staging rules ride
+// along: sixdof_watch_read in the same fault sweep, both pending on one lane, sixdof_history_stream across the ring's wrap.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -203,24 +204,102 @@ void refusals() {
     if (sixdof_history_envelope(wide.h, &vel, 1, 4, 1, 1, 48, bdst, 0) != SIXDOF_OK) complain(std::string("period 48 x width 6: ") + sixdof_last_error(wide.h));
 }
 
+// Two staged readers pending on one copy lane: an asynchronous watch read, an asynchronous envelope read behind it and — with
+// `regrow` — a second, larger watch read whose staging buffer has to grow while the first two are pending, then ONE
+// sixdof_download_wait.  Everything equals the blocking reads of the same ranges byte for byte, and sixdof_sync ends the page locks.
+void two_readers_one_lane(bool regrow) {
+    const std::string what = regrow ? "two readers, staging regrown while pending" : "two readers on one lane";
+    Recorded<double> r(24, 4, 6, false);   // recording since tick 3: the ring of 4 holds 3 .. 6, tick 5 in slot 0
+    const uint64_t comp[2] = {sixdof_component_id("world_pos"), sixdof_component_id("world_vel")}, who[3] = {1, 12, 24};
+    if (sixdof_set_watch(r.h, comp, 2, who, 3) != SIXDOF_OK) return complain(what + ": set_watch: " + sixdof_last_error(r.h));
+    // [0] watch 3, 5   [1] envelope 4, 5, 6 in two groups   [2] watch 3 .. 6;   [.][0] asynchronous, [.][1] blocking
+    std::vector<double> out[3][2][2];
+    auto read = [&](int which, int blocking) {
+        const uint64_t samples = which == 0 ? 2 : which == 1 ? 3 : 4;
+        void* dst[2];
+        for (int k = 0; k < 2; k++) {
+            out[which][blocking][k].assign(which == 1 ? out_doubles(samples, 2, kWidths[k]) : 3 * samples * kWidths[k], -7.0);
+            dst[k] = out[which][blocking][k].data();
+        }
+        const int rc = which == 1 ? sixdof_history_envelope(r.h, comp, 2, 4, samples, 1, 2, reinterpret_cast<double**>(dst), blocking ? 0u : SIXDOF_ENVELOPE_ASYNC)
+                                  : sixdof_watch_read(r.h, 3, samples, which == 0 ? 2 : 1, dst, blocking ? 0u : SIXDOF_WATCH_ASYNC);
+        if (rc != SIXDOF_OK) complain(what + ": read " + std::to_string(which) + ": " + sixdof_last_error(r.h));
+    };
+    const int n_reads = regrow ? 3 : 2;
+    for (int which = 0; which < n_reads; which++) read(which, 0);
+    if (sixdof_download_wait(r.h) != SIXDOF_OK || sixdof_sync(r.h) != SIXDOF_OK) complain(what + ": download_wait / sync: " + sixdof_last_error(r.h));
+    if (hip_fake::live_page_locks()) complain(what + ": " + std::to_string(hip_fake::live_page_locks()) + " page locks are alive after sixdof_sync");
+    for (int which = 0; which < n_reads; which++) {
+        read(which, 1);
+        for (int k = 0; k < 2; k++) {
+            const std::vector<double>&got = out[which][0][k], &want = out[which][1][k];
+            if (std::memcmp(got.data(), want.data(), want.size() * sizeof(double)) != 0) complain(what + ": read " + std::to_string(which) + " differs from the blocking read of its range");
+            if (want[0] == -7.0 || want.back() == -7.0) complain(what + ": the blocking read " + std::to_string(which) + " filled nothing");
+        }
+    }
+    // the watch read is the ring's rows themselves: entity 12 (row 11), tick 5 is sample 1 of read 0
+    if (std::memcmp(&out[0][0][0][(1 * 2 + 1) * 7], &r.truth[0][5 - 1][11 * 7], 7 * sizeof(double)) != 0) complain(what + ": the watch read is not what was uploaded before tick 5");
+}
+
+// sixdof_history_stream across the ring's wrap: ticks 3 .. 6 of a ring of 4 (slots 2 3 0 1) equal four sixdof_history_reads.
+void stream_across_the_wrap() {
+    Recorded<double> r(24, 4, 6, false);
+    std::vector<double> run[4], one;
+    void* dst[4];
+    for (int k = 0; k < 4; k++) run[k].assign(4 * r.n * kWidths[k], -7.0), dst[k] = run[k].data();
+    if (sixdof_history_stream(r.h, 3, 4, dst) != SIXDOF_OK || sixdof_download_wait(r.h) != SIXDOF_OK) return complain(std::string("history_stream across the wrap: ") + sixdof_last_error(r.h));
+    for (int k = 0; k < 4; k++)
+        for (uint64_t t = 3; t <= 6; t++) {
+            one.assign(r.n * kWidths[k], -9.0);
+            if (sixdof_history_read(r.h, sixdof_component_id(kNames[k]), t, one.data()) != SIXDOF_OK) return complain(std::string("history_read: ") + sixdof_last_error(r.h));
+            if (std::memcmp(&run[k][(t - 3) * one.size()], one.data(), one.size() * sizeof(double)) != 0)
+                complain(std::string("history_stream across the wrap: ") + kNames[k] + " tick " + std::to_string(t) + " differs from history_read");
+            if (std::memcmp(one.data(), r.truth[k][t - 1].data(), one.size() * sizeof(double)) != 0)
+                complain(std::string("history_read: ") + kNames[k] + " tick " + std::to_string(t) + " is not what was uploaded before it");
+        }
+    const uint64_t top = ~uint64_t(0);
+    if (sixdof_history_stream(r.h, 2, top, dst) != SIXDOF_ERR_INVALID_ARGUMENT || sixdof_history_stream(r.h, 3, 5, dst) != SIXDOF_ERR_INVALID_ARGUMENT ||
+        sixdof_history_stream(r.h, 2, 4, dst) != SIXDOF_ERR_INVALID_ARGUMENT || sixdof_history_read(r.h, sixdof_component_id("force"), 7, one.data()) != SIXDOF_ERR_INVALID_ARGUMENT)
+        complain("history_stream / history_read accept ticks that are not in the ring");
+    if (sixdof_sync(r.h) != SIXDOF_OK) complain("history_stream across the wrap: sync");
+}
+
+// What the fault sweep reads: ticks 4, 6, 8 of world_pos and force, as envelopes in four groups or as the watched rows.
+struct SweptRead {
+    const char* name;
+    int (*setup)(sixdof_handle*, const uint64_t comp[2]);                      // before the fault is armed
+    size_t (*doubles)(int k);
+    int (*read)(sixdof_handle*, const uint64_t comp[2], void* const dst[2], bool async);
+};
+const uint64_t kSweptEntities[3] = {1, 17, 40};
+const SweptRead kSweptReads[2] = {
+    {"envelope", [](sixdof_handle*, const uint64_t*) { return int(SIXDOF_OK); }, [](int k) { return out_doubles(3, 4, k ? 6 : 7); },
+     [](sixdof_handle* h, const uint64_t* comp, void* const dst[2], bool async) {
+         return sixdof_history_envelope(h, comp, 2, 4, 3, 2, 4, reinterpret_cast<double* const*>(dst), async ? SIXDOF_ENVELOPE_ASYNC : 0u);
+     }},
+    {"watch", [](sixdof_handle* h, const uint64_t* comp) { return sixdof_set_watch(h, comp, 2, kSweptEntities, 3); }, [](int k) { return size_t(3 * 3 * (k ? 6 : 7)); },
+     [](sixdof_handle* h, const uint64_t*, void* const dst[2], bool async) { return sixdof_watch_read(h, 4, 3, 2, dst, async ? SIXDOF_WATCH_ASYNC : 0u); }},
+};
+
 // Each fallible runtime call of a blocking and of an asynchronous read is failed once: the status is returned with a message,
 // the call succeeds when repeated, its values are the fault-free run's, and nothing outlives the handle.
-void failure_injection() {
+void failure_injection(const SweptRead& swept) {
     const uint64_t comp[2] = {sixdof_component_id("world_pos"), sixdof_component_id("force")};
     std::vector<double> want[2];
     long n_calls = 0;
     for (long fault = -1; fault < n_calls || fault < 0; fault++) {
-        const std::string run = "fault at call " + std::to_string(fault);
+        const std::string run = std::string(swept.name) + ": fault at call " + std::to_string(fault);
         {
             Recorded<double> r(40, 8, 9, true);
+            if (swept.setup(r.h, comp) != SIXDOF_OK) complain(run + ": setup: " + sixdof_last_error(r.h));
             std::vector<double> out[2][2];
             int failed = 0;
             const long calls0 = hip_fake::calls();
             hip_fake::fail_after(fault);
             for (int a = 0; a < 2; a++) {   // blocking, then asynchronous: the second grows neither buffer
-                double* dst[2];
-                for (int k = 0; k < 2; k++) out[a][k].assign(out_doubles(3, 4, k ? 6 : 7), -1.0), dst[k] = out[a][k].data();
-                auto read = [&] { return sixdof_history_envelope(r.h, comp, 2, 4, 3, 2, 4, dst, a ? SIXDOF_ENVELOPE_ASYNC : 0u); };
+                void* dst[2];
+                for (int k = 0; k < 2; k++) out[a][k].assign(swept.doubles(k), -1.0), dst[k] = out[a][k].data();
+                auto read = [&] { return swept.read(r.h, comp, dst, a != 0); };
                 int rc = read();
                 if (rc != SIXDOF_OK) {
                     if (!hip_fake::fired() || failed || !*sixdof_last_error(r.h)) complain(run + ": a read failed with no fault of the test's behind it: " + sixdof_last_error(r.h));
@@ -238,6 +317,7 @@ void failure_injection() {
                 n_calls = hip_fake::calls() - calls0;
                 for (int k = 0; k < 2; k++) want[k] = out[0][k];
                 if (failed) complain("fault-free run failed");
+                if (want[0][0] == -1.0 || want[1].back() == -1.0) complain(run + ": the fault-free read filled nothing");
             } else if (failed != 1) {
                 complain(run + ": " + std::to_string(failed) + " steps reported it");
             }
@@ -247,7 +327,7 @@ void failure_injection() {
         }
         if (hip_fake::live_allocations() || hip_fake::live_streams() || hip_fake::live_events() || hip_fake::live_page_locks()) complain(run + ": something outlives sixdof_destroy");
     }
-    std::printf("envelope_host_test: %ld fallible calls of a blocking and an asynchronous read, each failed once\n", n_calls);
+    std::printf("envelope_host_test: %ld fallible calls of a blocking and an asynchronous %s read, each failed once\n", n_calls, swept.name);
 }
 
 }  // namespace
@@ -261,7 +341,10 @@ int main() {
     values_case<double>(1, 4, 4, 4, 1, 1, false);
     values_case<double>(65, 4, 4, 3, 1, 5, false);
     refusals();
-    failure_injection();
+    two_readers_one_lane(false);
+    two_readers_one_lane(true);
+    stream_across_the_wrap();
+    for (const SweptRead& swept : kSweptReads) failure_injection(swept);
     if (hip_fake::violations()) complain(std::to_string(hip_fake::violations()) + " violations reported by the fake runtime");
     if (g_failures) return std::fprintf(stderr, "envelope_host_test: %d failures\n", g_failures), 1;
     std::printf("envelope_host_test: ok\n");

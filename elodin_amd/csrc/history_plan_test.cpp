@@ -1,5 +1,6 @@
 // history_plan_test.cpp — host unit test of history_plan.hpp: the validity rule of a sampled range at its edges, and the
-// slot sequence of wrapping, strided ranges against a brute-force twin that simulates the ring slot by slot.  No GPU.
+// slot sequence of wrapping, strided ranges against a brute-force twin that simulates the ring slot by slot, and the rule at
+// every = 1 against the hand-written predicate sixdof_history_read / sixdof_history_stream used to carry.  No GPU.
 // Prints "history plan test ok" on success (tests/test_history_plan.py).
 #include <cstdio>
 #include <cstdlib>
@@ -104,6 +105,34 @@ void test_against_brute_force() {
     CHECK(checked > 10000 && valid > 500);
 }
 
+// What sixdof_history_stream (and, with n_ticks = 1, sixdof_history_read) checked by hand before they took the shared rule:
+// the specification the rule is held to at every = 1.  In 64 bits, wrap included, as that code computed it.
+bool contiguous_run_ok(uint64_t first_tick, uint64_t n_ticks, uint64_t hist_first_tick, uint64_t tick, uint64_t ring) {
+    const uint64_t last = first_tick + n_ticks - 1;
+    return !(first_tick < hist_first_tick || last > tick || first_tick + ring <= tick || n_ticks > ring);
+}
+
+void test_contiguous_runs_classified_as_before() {
+    uint64_t valid = 0;
+    for (uint64_t ring = 1; ring <= 5; ring++)
+        for (uint64_t hf = 1; hf <= 4; hf++)
+            for (uint64_t tick = 0; tick <= 9; tick++)
+                for (uint64_t first = 0; first <= 11; first++)
+                    for (uint64_t n = 1; n <= 7; n++) {
+                        const bool ok = sampled_range_ok(first, n, 1, hf, tick, ring);
+                        CHECK(ok == contiguous_run_ok(first, n, hf, tick, ring));
+                        valid += ok;
+                    }
+    CHECK(valid > 100);
+    // where only the hand-written form could wrap (first_tick + n_ticks - 1 == 0): it refused through n_ticks > ring
+    const uint64_t top = UINT64_MAX;
+    for (uint64_t ring : {uint64_t(1), uint64_t(4), uint64_t(1) << 32})
+        for (uint64_t tick : {uint64_t(2), uint64_t(5), top - 1}) {
+            CHECK(!contiguous_run_ok(2, top, 1, tick, ring));
+            CHECK(!sampled_range_ok(2, top, 1, 1, tick, ring));
+        }
+}
+
 void test_wrapping_strided_sequence() {
     // ring 10, ticks 18 .. 27 wrap: slots 7 8 9 0 1 .. 6
     const uint64_t want1[10] = {7, 8, 9, 0, 1, 2, 3, 4, 5, 6};
@@ -123,6 +152,7 @@ void test_wrapping_strided_sequence() {
 int main() {
     test_rule_edges();
     test_against_brute_force();
+    test_contiguous_runs_classified_as_before();
     test_wrapping_strided_sequence();
     std::printf("history plan test ok\n");
     return 0;

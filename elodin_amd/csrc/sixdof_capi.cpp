@@ -159,12 +159,37 @@ struct History {
 };
 
 // The telemetry D2H lane that overlaps the compute stream: its stream and two events exist together or not at all.
+// Every asynchronous read-back (sixdof_download_async, sixdof_history_stream, StagedRead::deliver) is
+//     [hold]  what its copies read is made ready on the compute stream  begin  copy ...  end
+// and a failure anywhere leaves `pending` as it was: nothing new to wait for, the next call starts afresh.
 struct CopyLane {
     Stream stream;
     Event ev_snap, ev_copied;
     bool pending = false;
     uint64_t stream_lo = 0, stream_hi = 0;   // ticks of the history run whose copy may still be in flight
     std::vector<PinnedRange> pinned_user;    // caller's buffers page-locked by sixdof_history_stream / sixdof_watch_read, until sixdof_sync
+    // Before `compute` overwrites a buffer the copies of an earlier read take their data from (snapshots, a staging buffer):
+    // those copies must have drained it.  A device-side wait; the host goes on.
+    hipError_t hold(hipStream_t compute) { return pending ? hipStreamWaitEvent(compute, ev_copied.get(), 0) : hipSuccess; }
+    // The copies that follow start once everything enqueued on `compute` so far has completed.
+    hipError_t begin(hipStream_t compute) {
+        hipError_t e = ensure();
+        if (e == hipSuccess) e = hipEventRecord(ev_snap.get(), compute);
+        if (e == hipSuccess) e = hipStreamWaitEvent(stream.get(), ev_snap.get(), 0);
+        return e;
+    }
+    // One D2H on the copy stream; [dst, dst + pin_bytes) is page-locked first (0: the caller's business).
+    hipError_t copy(void* dst, const void* src, size_t bytes, size_t pin_bytes) {
+        if (pin_bytes) pin(dst, pin_bytes);
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream.get());
+    }
+    // ev_copied is re-recorded behind whatever the copy stream already carried: one sixdof_download_wait covers every read
+    // enqueued before it, of whichever kind.
+    hipError_t end() {
+        hipError_t e = hipEventRecord(ev_copied.get(), stream.get());
+        if (e == hipSuccess) pending = true;
+        return e;
+    }
     hipError_t ensure() {
         if (stream) return hipSuccess;
         Stream s;
@@ -686,9 +711,7 @@ int sixdof_download_async(sixdof_handle* h, uint32_t mask) try {
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "download_async: no columns bound");
     HIP_TRY(h, hipSetDevice(h->device));
     CopyLane& lane = h->copy;
-    HIP_TRY(h, lane.ensure());
-    // the previous copy must have drained the snapshot buffers before they are overwritten (device-side wait)
-    if (lane.pending) HIP_TRY(h, hipStreamWaitEvent(h->stream.get(), lane.ev_copied.get(), 0));
+    HIP_TRY(h, lane.hold(h->stream.get()));   // the snapshot buffers are overwritten below
     Column* picked[5];
     int n_picked = 0;
     for (auto& b : h->body) {
@@ -702,12 +725,9 @@ int sixdof_download_async(sixdof_handle* h, uint32_t mask) try {
         if (!c->host_pinned) c->host_pinned.lock(c->host, c->bytes);   // once; an unlockable range is copied staged
         picked[n_picked++] = c;
     }
-    HIP_TRY(h, hipEventRecord(lane.ev_snap.get(), h->stream.get()));
-    HIP_TRY(h, hipStreamWaitEvent(lane.stream.get(), lane.ev_snap.get(), 0));
-    for (int k = 0; k < n_picked; k++)
-        HIP_TRY(h, hipMemcpyAsync(picked[k]->host, picked[k]->snap.get(), picked[k]->bytes, hipMemcpyDeviceToHost, lane.stream.get()));
-    HIP_TRY(h, hipEventRecord(lane.ev_copied.get(), lane.stream.get()));
-    lane.pending = true;
+    HIP_TRY(h, lane.begin(h->stream.get()));
+    for (int k = 0; k < n_picked; k++) HIP_TRY(h, lane.copy(picked[k]->host, picked[k]->snap.get(), picked[k]->bytes, 0));
+    HIP_TRY(h, lane.end());
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -980,7 +1000,7 @@ double ref_interp(double t, const std::vector<double>& xs, const std::vector<dou
 int snapshot_tick_to_ring(sixdof_handle* h, uint64_t ticks_done) {
     if (!h->hist.ring) return SIXDOF_OK;
     const size_t n = h->desc.n_entities, es = h->elem_size();
-    const size_t slot = static_cast<size_t>((ticks_done - 1) % h->hist.ring);
+    const size_t slot = static_cast<size_t>(history_slot(ticks_done, h->hist.ring));
     for (int k = 0; k < 4; k++) {
         const size_t block = n * h->body[k].width * es;
         if (!block) continue;
@@ -1237,6 +1257,13 @@ int sixdof_set_custom_pair(sixdof_handle* h, const char* so_path) try {
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
+// Column m of the installed program if the ring records it, else null: a window column is its own history (and far too wide
+// to copy per tick), an unbound one has nothing to record.
+static const Column* recorded_model_column(const sixdof_handle* h, size_t m) {
+    const bool window = m < h->custom_model_width.size() && (h->custom_model_width[m] >> 31);
+    return window ? nullptr : h->col(h->custom_model[m]);
+}
+
 int sixdof_set_history(sixdof_handle* h, uint32_t ring_ticks) try {
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_history: bind Body columns first");
@@ -1245,23 +1272,17 @@ int sixdof_set_history(sixdof_handle* h, uint32_t ring_ticks) try {
     h->hist.reset();   // free first (rings can be gigabytes): from here to the end of a successful call there is no ring
     h->replay.drop();
     if (ring_ticks == 0) return SIXDOF_OK;
-    const size_t n = h->desc.n_entities, es = h->elem_size();
     History fresh;     // freed as a whole by any failure below
-    for (int k = 0; k < 4; k++) {
-        const size_t bytes = static_cast<size_t>(ring_ticks) * n * h->body[k].width * es;
-        if (hipError_t e = fresh.body[k].alloc(bytes ? bytes : 16); e != hipSuccess) return h->hip_fail(e, "set_history: hipMalloc of the ring");
-    }
-    for (uint64_t id : h->custom_model) {      // component columns of a generated program are recorded too
-        const Column* c = h->col(id);
-        const size_t m_idx = fresh.model.size();
-        const bool window = m_idx < h->custom_model_width.size() && (h->custom_model_width[m_idx] >> 31);
-        fresh.model.emplace_back();
-        if (c && !window) {   // a window column is its own history (and far too wide to copy per tick)
-            const size_t bytes = static_cast<size_t>(ring_ticks) * n * c->width * es;
-            if (hipError_t e = fresh.model.back().alloc(bytes ? bytes : 16); e != hipSuccess)
-                return h->hip_fail(e, "set_history: hipMalloc of a component ring");
-        }
-    }
+    auto alloc_ring = [&](DeviceBuffer& ring, uint64_t width) {
+        const size_t bytes = static_cast<size_t>(ring_ticks) * h->desc.n_entities * width * h->elem_size();
+        return ring.alloc(bytes ? bytes : 16);
+    };
+    for (int k = 0; k < 4; k++)
+        if (hipError_t e = alloc_ring(fresh.body[k], h->body[k].width); e != hipSuccess) return h->hip_fail(e, "set_history: hipMalloc of the ring");
+    fresh.model.resize(h->custom_model.size());
+    for (size_t m = 0; m < h->custom_model.size(); m++)      // component columns of a generated program are recorded too
+        if (const Column* c = recorded_model_column(h, m))
+            if (hipError_t e = alloc_ring(fresh.model[m], c->width); e != hipSuccess) return h->hip_fail(e, "set_history: hipMalloc of a component ring");
     fresh.ring = ring_ticks;
     fresh.first_tick = h->tick + 1;
     h->hist = std::move(fresh);
@@ -1279,9 +1300,8 @@ static bool watch_lookup(const sixdof_handle* h, uint64_t id, const void** ring_
         }
     for (size_t m = 0; m < h->custom_model.size(); m++) {
         if (h->custom_model[m] != id) continue;
-        const bool window = m < h->custom_model_width.size() && (h->custom_model_width[m] >> 31);
-        const Column* c = h->col(id);
-        if (window || !c) return false;
+        const Column* c = recorded_model_column(h, m);
+        if (!c) return false;
         *ring_base = h->hist.ring && m < h->hist.model.size() ? h->hist.model[m].get() : nullptr;
         *w = static_cast<size_t>(c->width);
         return true;
@@ -1297,11 +1317,11 @@ int sixdof_history_read(sixdof_handle* h, uint64_t component_id, uint64_t tick, 
     size_t w = 0;
     if (!watch_lookup(h, component_id, &ring_base, &w) || !ring_base)
         return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "history_read: only world_pos / world_vel / world_accel / force and the component columns of a generated program are recorded");
-    if (tick < hs.first_tick || tick > h->tick || tick + hs.ring <= h->tick)
+    if (!sampled_range_ok(tick, 1, 1, hs.first_tick, h->tick, hs.ring))
         return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_read: tick is not in the ring");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t block = static_cast<size_t>(h->desc.n_entities) * w * h->elem_size();
-    const size_t slot = static_cast<size_t>((tick - 1) % hs.ring);
+    const size_t slot = static_cast<size_t>(history_slot(tick, hs.ring));
     if (block) HIP_TRY(h, hipMemcpyAsync(host_dst, static_cast<const char*>(ring_base) + slot * block, block, hipMemcpyDeviceToHost, h->stream.get()));
     HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
     return SIXDOF_OK;
@@ -1312,33 +1332,28 @@ int sixdof_history_stream(sixdof_handle* h, uint64_t first_tick, uint64_t n_tick
     const History& hs = h->hist;
     if (!hs.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_stream: no history ring (sixdof_set_history)");
     if (n_ticks == 0) return SIXDOF_OK;
-    const uint64_t last = first_tick + n_ticks - 1;
-    if (first_tick < hs.first_tick || last > h->tick || first_tick + hs.ring <= h->tick || n_ticks > hs.ring)
+    if (!sampled_range_ok(first_tick, n_ticks, 1, hs.first_tick, h->tick, hs.ring))
         return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_stream: ticks are not (all) in the ring");
     HIP_TRY(h, hipSetDevice(h->device));
     CopyLane& lane = h->copy;
-    HIP_TRY(h, lane.ensure());
-    HIP_TRY(h, hipEventRecord(lane.ev_snap.get(), h->stream.get()));            // everything recorded so far is in the ring after this
-    HIP_TRY(h, hipStreamWaitEvent(lane.stream.get(), lane.ev_snap.get(), 0));
+    HIP_TRY(h, lane.begin(h->stream.get()));            // everything recorded so far is in the ring after this
     const size_t n = h->desc.n_entities, es = h->elem_size();
     for (int k = 0; k < 4; k++) {
         if (!host_dst[k]) continue;
         const size_t block = n * h->body[k].width * es;
         if (!block) continue;
-        lane.pin(host_dst[k], block * n_ticks);
         // the run is contiguous in the ring except where it wraps: at most two copies per column
-        const size_t slot0 = static_cast<size_t>((first_tick - 1) % hs.ring);
+        const size_t slot0 = static_cast<size_t>(history_slot(first_tick, hs.ring));
         const size_t head = std::min<size_t>(n_ticks, hs.ring - slot0);
         char* dst = static_cast<char*>(host_dst[k]);
         const char* ring = hs.body[k].get<char>();
-        HIP_TRY(h, hipMemcpyAsync(dst, ring + slot0 * block, head * block, hipMemcpyDeviceToHost, lane.stream.get()));
-        if (head < n_ticks)
-            HIP_TRY(h, hipMemcpyAsync(dst + head * block, ring, (n_ticks - head) * block, hipMemcpyDeviceToHost, lane.stream.get()));
+        HIP_TRY(h, lane.copy(dst, ring + slot0 * block, head * block, n_ticks * block));
+        if (head < n_ticks) HIP_TRY(h, lane.copy(dst + head * block, ring, (n_ticks - head) * block, 0));
     }
-    HIP_TRY(h, hipEventRecord(lane.ev_copied.get(), lane.stream.get()));
-    lane.pending = true;
+    HIP_TRY(h, lane.end());
+    // the one reader whose copies read the RING from the copy stream: sixdof_step holds back a batch that would overwrite these ticks
     lane.stream_lo = first_tick;
-    lane.stream_hi = last;
+    lane.stream_hi = first_tick + n_ticks - 1;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -1373,6 +1388,62 @@ int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_c
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
+// A read whose results are computed on the compute stream, out of the ring into a device staging buffer, and brought from
+// there to the caller's buffers, blocking or over the copy lane: sixdof_watch_read and sixdof_history_envelope.  The lane
+// and the rules of the staging buffer live here and nowhere in the callers: add() the components, claim() the buffers,
+// launch into them, deliver().
+struct StagedRead {
+    // one component: ring base and width as they are NOW, its block in the staging buffer (256-byte aligned), where it goes
+    struct Part { const void* ring; size_t w, bytes, offset; void* host; };
+    sixdof_handle* h;
+    const char* who;        // the entry point, for its messages
+    DeviceBuffer* stage;    // lives with whatever the entry point chose (the handle, the ring)
+    std::vector<Part> parts;
+    size_t stage_bytes = 0;
+
+    // `per_width` elements of `elem` bytes for every element of a row; `unrecorded`: the message when the ring does not hold `id`
+    int add(uint64_t id, void* host, size_t per_width, size_t elem, const char* unrecorded) {
+        Part p{};
+        if (!watch_lookup(h, id, &p.ring, &p.w) || !p.ring) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, std::string(who) + ": " + unrecorded);
+        if (!host) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, std::string(who) + ": null host buffer");
+        p.host = host, p.bytes = per_width * p.w * elem, p.offset = stage_bytes;
+        stage_bytes += (p.bytes + 255) / 256 * 256;
+        parts.push_back(p);
+        return SIXDOF_OK;
+    }
+    // After this the compute stream may write the staging buffer, large enough for every part, and `scratch` (if any) of at
+    // least scratch_bytes.  A buffer that could not be grown is left empty: the next read allocates it again.
+    int claim(DeviceBuffer* scratch = nullptr, size_t scratch_bytes = 0) {
+        CopyLane& lane = h->copy;
+        const bool grow_stage = stage_bytes > stage->bytes(), grow_scratch = scratch && scratch_bytes > scratch->bytes();
+        if (grow_stage || grow_scratch) {
+            // the copy stream may still read the old staging buffer (a previous asynchronous read), the compute stream may still use both
+            if (lane.pending) HIP_TRY(h, hipStreamSynchronize(lane.stream.get()));
+            HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
+            if (grow_stage) HIP_TRY(h, stage->alloc(stage_bytes));   // free first; on failure empty
+            if (grow_scratch) HIP_TRY(h, scratch->alloc(scratch_bytes));
+        }
+        HIP_TRY(h, lane.hold(h->stream.get()));   // one staging buffer: the launches that follow overwrite it
+        return SIXDOF_OK;
+    }
+    // The parts, complete in the staging buffer once the compute stream gets here, to the caller's buffers.
+    int deliver(bool async) {
+        CopyLane& lane = h->copy;
+        const char* staged = stage->get<char>();
+        if (!async) {
+            for (const Part& p : parts)
+                if (p.bytes) HIP_TRY(h, hipMemcpyAsync(p.host, staged + p.offset, p.bytes, hipMemcpyDeviceToHost, h->stream.get()));
+            HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
+            return SIXDOF_OK;
+        }
+        HIP_TRY(h, lane.begin(h->stream.get()));
+        for (const Part& p : parts)
+            if (p.bytes) HIP_TRY(h, lane.copy(p.host, staged + p.offset, p.bytes, p.bytes));
+        HIP_TRY(h, lane.end());
+        return SIXDOF_OK;
+    }
+};
+
 // Ordering of the gather after the batch that recorded the ticks it reads.  With a ring enabled a handle neither replays
 // hipGraphs nor submits AQL chains (graph_eligible needs !hist_ring): every recording launch — the step kernel, the pair
 // and model kernels and their snapshot_tick_to_ring copies — is an eager launch on h->stream.get(), so the gather, launched on
@@ -1394,61 +1465,27 @@ int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples,
     if (!sampled_range_ok(first_tick, n_samples, every, h->hist.first_tick, h->tick, h->hist.ring))
         return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: ticks are not (all) in the ring");
     const size_t n_comp = h->watch_ids.size(), es = h->elem_size(), m = h->watch_m;
-    // per component: ring base and width as they are NOW, and its block in the staging buffer (256-byte aligned)
-    struct Part { const void* ring; size_t w, bytes, offset; };
-    std::vector<Part> parts(n_comp);
-    size_t stage = 0;
+    StagedRead rd{h, "watch_read", &h->d_watch_stage};
     for (size_t k = 0; k < n_comp; k++) {
-        Part& p = parts[k];
-        if (!watch_lookup(h, h->watch_ids[k], &p.ring, &p.w) || !p.ring)
-            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "watch_read: a watched component is no longer recorded (the program was replaced)");
-        if (!host_dst[k]) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "watch_read: null host buffer");
-        p.bytes = m * static_cast<size_t>(n_samples) * p.w * es;
-        p.offset = stage;
-        stage += (p.bytes + 255) / 256 * 256;
+        const int rc = rd.add(h->watch_ids[k], host_dst[k], m * static_cast<size_t>(n_samples), es,
+                              "a watched component is no longer recorded (the program was replaced)");
+        if (rc != SIXDOF_OK) return rc;
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    const bool async = (flags & SIXDOF_WATCH_ASYNC) != 0;
-    CopyLane& lane = h->copy;
-    if (async) HIP_TRY(h, lane.ensure());
-    if (stage > h->d_watch_stage.bytes()) {
-        // the copy stream may still read the old buffer (a previous asynchronous read), the compute stream may still write it
-        if (lane.pending) HIP_TRY(h, hipStreamSynchronize(lane.stream.get()));
-        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
-        HIP_TRY(h, h->d_watch_stage.alloc(stage));   // free first; on failure empty
-    }
-    // one staging buffer: the previous asynchronous read's copies must have drained it before it is overwritten (device-side wait)
-    if (lane.pending) HIP_TRY(h, hipStreamWaitEvent(h->stream.get(), lane.ev_copied.get(), 0));
+    if (int rc = rd.claim(); rc != SIXDOF_OK) return rc;
     for (size_t k0 = 0; k0 < n_comp; k0 += kHistoryGatherMax) {
         const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kHistoryGatherMax, n_comp - k0));
         HistoryGatherArgs a{};
         for (uint32_t k = 0; k < cnt; k++) {
-            a.c[k].ring = parts[k0 + k].ring;
-            a.c[k].out_offset = parts[k0 + k].offset / es;
-            a.c[k].w = static_cast<uint32_t>(parts[k0 + k].w);
+            a.c[k].ring = rd.parts[k0 + k].ring;
+            a.c[k].out_offset = rd.parts[k0 + k].offset / es;
+            a.c[k].w = static_cast<uint32_t>(rd.parts[k0 + k].w);
         }
         hipError_t e = launch_history_gather(a, cnt, h->d_watch_stage.get(), h->d_watch_rows.get<uint32_t>(), m, h->desc.n_entities, first_tick, n_samples,
                                              every, h->hist.ring, es, h->stream.get());
         if (e != hipSuccess) return h->hip_fail(e, "history_gather");
     }
-    const char* staged = h->d_watch_stage.get<char>();
-    if (!async) {
-        for (const Part& p : parts)
-            if (p.bytes) HIP_TRY(h, hipMemcpyAsync(host_dst[&p - parts.data()], staged + p.offset, p.bytes, hipMemcpyDeviceToHost, h->stream.get()));
-        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
-        return SIXDOF_OK;
-    }
-    HIP_TRY(h, hipEventRecord(lane.ev_snap.get(), h->stream.get()));            // the series are in the staging buffer after this
-    HIP_TRY(h, hipStreamWaitEvent(lane.stream.get(), lane.ev_snap.get(), 0));
-    for (size_t k = 0; k < n_comp; k++) {
-        if (!parts[k].bytes) continue;
-        lane.pin(host_dst[k], parts[k].bytes);
-        HIP_TRY(h, hipMemcpyAsync(host_dst[k], staged + parts[k].offset, parts[k].bytes, hipMemcpyDeviceToHost, lane.stream.get()));
-    }
-    // re-recorded behind whatever the copy stream already carried: one sixdof_download_wait covers a history_stream copy too
-    HIP_TRY(h, hipEventRecord(lane.ev_copied.get(), lane.stream.get()));
-    lane.pending = true;
-    return SIXDOF_OK;
+    return rd.deliver((flags & SIXDOF_WATCH_ASYNC) != 0);
 } SIXDOF_ABI_CATCH(err_of(h))
 
 // The envelopes of sampled ticks: ordering, ring reads and the copy lane exactly as for sixdof_watch_read above — the two
@@ -1468,30 +1505,27 @@ int sixdof_history_envelope(sixdof_handle* h, const uint64_t* component_ids, siz
     if (!component_ids || !host_dst) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: null argument");
     if (!sampled_range_ok(first_tick, n_samples, every, h->hist.first_tick, h->tick, h->hist.ring))
         return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: ticks are not (all) in the ring");
-    // per component: ring base and width as they are NOW, its block in the staging buffer and its records in a sample's partials
-    struct Part { const void* ring; size_t w, doubles, offset, partial_offset; };
-    std::vector<Part> parts(n_components);
-    size_t stage = 0, partial_stride = 0, launch_records = 0;
+    History& hs = h->hist;
+    StagedRead rd{h, "history_envelope", &hs.env_stage};
+    std::vector<size_t> partial_offset(n_components);   // per component: its records in a sample's partials
+    size_t partial_stride = 0, launch_records = 0;
     for (size_t k = 0; k < n_components; k++) {
-        Part& p = parts[k];
-        if (!watch_lookup(h, component_ids[k], &p.ring, &p.w) || !p.ring)
-            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "history_envelope: only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
-        if (!host_dst[k]) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: null host buffer");
-        if (!envelope_supported(p.w, period))
-            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: period " + std::to_string(period) + " x width " + std::to_string(p.w) +
+        const int rc = rd.add(component_ids[k], host_dst[k], static_cast<size_t>(n_samples) * period * kEnvelopeStats, sizeof(double),
+                              "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
+        if (rc != SIXDOF_OK) return rc;
+        const size_t w = rd.parts[k].w;
+        if (!envelope_supported(w, period))
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: period " + std::to_string(period) + " x width " + std::to_string(w) +
                                                             " exceeds the " + std::to_string(kEnvelopeMaxBins) + " (group, element) bins one block keeps apart");
-        const EnvelopeGeom g = envelope_geom(n, static_cast<uint32_t>(p.w), period);
-        p.doubles = static_cast<size_t>(n_samples) * period * kEnvelopeStats * p.w;
-        p.offset = stage;
-        stage += (p.doubles + 31) / 32 * 32;              // 256-byte aligned blocks
+        const EnvelopeGeom g = envelope_geom(n, static_cast<uint32_t>(w), period);
         if (k % kEnvelopeMaxComponents == 0) launch_records = 0;   // every launch of at most 32 components reuses the records
-        p.partial_offset = launch_records;
+        partial_offset[k] = launch_records;
         launch_records += static_cast<size_t>(g.blocks) * g.bins;
         partial_stride = std::max(partial_stride, launch_records);
     }
     if (n == 0) {      // nothing to reduce: count 0, statistics NaN
         for (size_t k = 0; k < n_components; k++)
-            for (size_t i = 0; i < parts[k].doubles; i++) host_dst[k][i] = i / parts[k].w % kEnvelopeStats == 0 ? 0.0 : std::nan("");
+            for (size_t i = 0; i < rd.parts[k].bytes / sizeof(double); i++) host_dst[k][i] = i / rd.parts[k].w % kEnvelopeStats == 0 ? 0.0 : std::nan("");
         return SIXDOF_OK;
     }
     // samples per launch: the partial records of one launch stay within a fixed budget, and the grid's y extent below 2^16
@@ -1499,27 +1533,15 @@ int sixdof_history_envelope(sixdof_handle* h, const uint64_t* component_ids, siz
     const size_t per_sample = partial_stride * sizeof(EnvelopePartial);
     const uint64_t chunk = std::min<uint64_t>({n_samples, 65535, std::max<size_t>(1, kPartialBudget / per_sample)});
     HIP_TRY(h, hipSetDevice(h->device));
-    const bool async = (flags & SIXDOF_ENVELOPE_ASYNC) != 0;
-    CopyLane& lane = h->copy;
-    if (async) HIP_TRY(h, lane.ensure());
-    History& hs = h->hist;
-    if (stage * sizeof(double) > hs.env_stage.bytes() || chunk * per_sample > hs.env_partial.bytes()) {
-        // the copy stream may still read the old staging buffer (a previous asynchronous read), the compute stream may still use both
-        if (lane.pending) HIP_TRY(h, hipStreamSynchronize(lane.stream.get()));
-        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
-        if (stage * sizeof(double) > hs.env_stage.bytes()) HIP_TRY(h, hs.env_stage.alloc(stage * sizeof(double)));   // free first; on failure empty
-        if (chunk * per_sample > hs.env_partial.bytes()) HIP_TRY(h, hs.env_partial.alloc(chunk * per_sample));
-    }
-    // one staging buffer: the previous asynchronous read's copies must have drained it before it is overwritten (device-side wait)
-    if (lane.pending) HIP_TRY(h, hipStreamWaitEvent(h->stream.get(), lane.ev_copied.get(), 0));
+    if (int rc = rd.claim(&hs.env_partial, chunk * per_sample); rc != SIXDOF_OK) return rc;
     for (size_t k0 = 0; k0 < n_components; k0 += kEnvelopeMaxComponents) {
         const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kEnvelopeMaxComponents, n_components - k0));
         EnvelopeArgs a{};
         for (uint32_t k = 0; k < cnt; k++) {
-            a.c[k].ring = parts[k0 + k].ring;
-            a.c[k].out_offset = parts[k0 + k].offset;
-            a.c[k].partial_offset = parts[k0 + k].partial_offset;
-            a.c[k].w = static_cast<uint32_t>(parts[k0 + k].w);
+            a.c[k].ring = rd.parts[k0 + k].ring;
+            a.c[k].out_offset = rd.parts[k0 + k].offset / sizeof(double);
+            a.c[k].partial_offset = partial_offset[k0 + k];
+            a.c[k].w = static_cast<uint32_t>(rd.parts[k0 + k].w);
         }
         for (uint64_t s0 = 0; s0 < n_samples; s0 += chunk) {
             hipError_t e = launch_history_envelope(a, cnt, hs.env_stage.get<double>(), hs.env_partial.get(), partial_stride, n, period, first_tick, s0,
@@ -1527,23 +1549,7 @@ int sixdof_history_envelope(sixdof_handle* h, const uint64_t* component_ids, siz
             if (e != hipSuccess) return h->hip_fail(e, "history_envelope");
         }
     }
-    const double* staged = hs.env_stage.get<double>();
-    if (!async) {
-        for (size_t k = 0; k < n_components; k++)
-            HIP_TRY(h, hipMemcpyAsync(host_dst[k], staged + parts[k].offset, parts[k].doubles * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
-        return SIXDOF_OK;
-    }
-    HIP_TRY(h, hipEventRecord(lane.ev_snap.get(), h->stream.get()));            // the envelopes are in the staging buffer after this
-    HIP_TRY(h, hipStreamWaitEvent(lane.stream.get(), lane.ev_snap.get(), 0));
-    for (size_t k = 0; k < n_components; k++) {
-        lane.pin(host_dst[k], parts[k].doubles * sizeof(double));
-        HIP_TRY(h, hipMemcpyAsync(host_dst[k], staged + parts[k].offset, parts[k].doubles * sizeof(double), hipMemcpyDeviceToHost, lane.stream.get()));
-    }
-    // re-recorded behind whatever the copy stream already carried: one sixdof_download_wait covers a history_stream copy too
-    HIP_TRY(h, hipEventRecord(lane.ev_copied.get(), lane.stream.get()));
-    lane.pending = true;
-    return SIXDOF_OK;
+    return rd.deliver((flags & SIXDOF_ENVELOPE_ASYNC) != 0);
 } SIXDOF_ABI_CATCH(err_of(h))
 
 int sixdof_download_column(sixdof_handle* h, uint64_t component_id) try {
@@ -1966,7 +1972,7 @@ int sixdof_step(sixdof_handle* h, uint64_t n_ticks, sixdof_timings* tm) try {
         // ticks tick+1 .. tick+n land in slots (t-1) % ring: hold the compute stream back only if that range reaches a
         // slot the copy stream may still be reading
         const uint64_t ring = h->hist.ring, in_flight = h->copy.stream_hi - h->copy.stream_lo + 1;
-        const uint64_t a = h->tick % ring, b = (h->copy.stream_lo - 1) % ring;       // first slot written / first slot read
+        const uint64_t a = history_slot(h->tick + 1, ring), b = history_slot(h->copy.stream_lo, ring);   // first slot written / first slot read
         const uint64_t gap_ab = (b + ring - a) % ring, gap_ba = (a + ring - b) % ring;
         const bool overlap = n_ticks + in_flight > ring || gap_ab < std::min<uint64_t>(n_ticks, ring) || gap_ba < in_flight;
         if (overlap) HIP_TRY(h, hipStreamWaitEvent(h->stream.get(), h->copy.ev_copied.get(), 0));

@@ -462,12 +462,24 @@ class HipExec:
             _raise(self._h, rc, "sixdof_set_history")
         self._ring_ticks = int(ring_ticks)      # what stream_series compares its batch with (stream_history sizes its own ring)
 
-    def history(self, name: str, first_tick: int, last_tick: int) -> np.ndarray:
-        """exec.history() analogue: [last-first+1, n, w] block of component `name`, row k = state after tick first+k."""
+    def _refuse_window(self, name: str) -> None:
         if name in self._windows:
             raise ValueError(f"{name} is a window component: it is its own history (HipExec.component), the ring does not copy it per tick")
-        w = 7 if name == "world_pos" else (self._aux[name].shape[1] if name in self._aux else 6)   # program columns too
-        out = np.empty((last_tick - first_tick + 1, self.n, w), dtype=self.dtype)
+
+    def _recorded_width(self, name: str) -> int:
+        """Row width of a component the ring records: a Body column, or a plain component column of a generated program."""
+        self._refuse_window(name)
+        return 7 if name == "world_pos" else (self._aux[name].shape[1] if name in self._aux else 6)
+
+    @staticmethod
+    def _sample_count(first_tick: int, last_tick: int, every: int) -> int:
+        """How many of the ticks first_tick, first_tick + every, ... are at most last_tick (0 for an empty or malformed range:
+        the library then says what is wrong with it)."""
+        return (last_tick - first_tick) // every + 1 if every > 0 and last_tick >= first_tick else 0
+
+    def history(self, name: str, first_tick: int, last_tick: int) -> np.ndarray:
+        """exec.history() analogue: [last-first+1, n, w] block of component `name`, row k = state after tick first+k."""
+        out = np.empty((last_tick - first_tick + 1, self.n, self._recorded_width(name)), dtype=self.dtype)
         for k, tick in enumerate(range(first_tick, last_tick + 1)):
             rc = self._lib.sixdof_history_read(self._h, L.component_id(name), tick, out[k].ctypes.data)
             if rc != L.OK:
@@ -481,8 +493,7 @@ class HipExec:
         allowed.  Independent of enable_history (either order).  Empty names and ids clear the watch."""
         names = [names] if isinstance(names, str) else list(names)
         for name in names:
-            if name in self._windows:
-                raise ValueError(f"{name} is a window component: it is its own history (HipExec.component), the ring does not copy it per tick")
+            self._refuse_window(name)
         ids = np.ascontiguousarray(entity_ids, dtype=np.uint64).reshape(-1)
         comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
         u64p = C.POINTER(C.c_uint64)
@@ -493,10 +504,9 @@ class HipExec:
 
     def _series_buffers(self, n_samples: int):
         names, m = getattr(self, "_watch", ((), 0))
-        width = lambda name: 7 if name == "world_pos" else (self._aux[name].shape[1] if name in self._aux else 6)
         out = {}
         for name in names:      # a name watched twice shares one entry: its buffer is filled once per occurrence, identically
-            out[name] = np.empty((m, n_samples, width(name)), dtype=self.dtype)
+            out[name] = np.empty((m, n_samples, self._recorded_width(name)), dtype=self.dtype)
         ptrs = (C.c_void_p * max(1, len(names)))(*[out[name].ctypes.data for name in names])
         return out, ptrs
 
@@ -504,7 +514,7 @@ class HipExec:
         """{name: [m, samples, w]} of the watched pairs: sample j of entity e is the state after tick first_tick + j * every,
         up to last_tick.  The rows are gathered on the device; m rows per sample cross the link, not n."""
         first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
-        n_samples = (last_tick - first_tick) // every + 1 if every > 0 and last_tick >= first_tick else 0
+        n_samples = self._sample_count(first_tick, last_tick, every)
         out, ptrs = self._series_buffers(n_samples)
         rc = self._lib.sixdof_watch_read(self._h, first_tick, n_samples, every, ptrs, 0)
         if rc != L.OK:
@@ -520,7 +530,6 @@ class HipExec:
         SAMPLED tick, the last one is the batch's last tick; the arrays are reused two batches later.  Returns the wall time in
         seconds.  (The ring size is the one enable_history was last called with: after a stream_history, which sizes its own
         ring, call enable_history again.)"""
-        import time
         n_batches, ticks_per_batch, every = int(n_batches), int(ticks_per_batch), int(every)
         if every < 1 or ticks_per_batch < 1 or ticks_per_batch % every != 0:
             raise ValueError(f"stream_series: ticks_per_batch ({ticks_per_batch}) must be a positive multiple of every ({every})")
@@ -530,38 +539,19 @@ class HipExec:
             self.enable_history(ticks_per_batch)
         n_samples = ticks_per_batch // every
         bufs, ptrs = zip(*[self._series_buffers(n_samples) for _ in range(2)])
+
+        def read(first_tick, k):
+            rc = self._lib.sixdof_watch_read(self._h, first_tick, n_samples, every, ptrs[k], L.WATCH_ASYNC)
+            if rc != L.OK:
+                _raise(self._h, rc, "sixdof_watch_read")
         self.sync()              # nothing of an earlier streaming run is in flight
-        self.set_flags(flags | L.FLAG_ASYNC_STEP)
-        t0 = time.perf_counter()
-        try:
-            first = []
-            for i in range(n_batches):
-                first.append(self.tick + every)                          # samples end on the batch's last tick
-                self.invoke_batch(ticks_per_batch)                       # enqueue batch i
-                if i > 0:
-                    self.download_wait()                                 # batch i-1 has landed in bufs[(i-1) % 2]
-                    if consume is not None:
-                        consume(i - 1, first[i - 1], bufs[(i - 1) % 2])
-                rc = self._lib.sixdof_watch_read(self._h, first[i], n_samples, every, ptrs[i % 2], L.WATCH_ASYNC)
-                if rc != L.OK:
-                    _raise(self._h, rc, "sixdof_watch_read")
-            self.download_wait()
-            if consume is not None and n_batches:
-                consume(n_batches - 1, first[-1], bufs[(n_batches - 1) % 2])
-        finally:
-            self.set_flags(flags)
-            self.sync()          # also drops the page locks on `bufs` before they go out of scope
-        return time.perf_counter() - t0
+        return self._stream_batches(n_batches, ticks_per_batch, every, read, lambda k: bufs[k], consume, flags)   # samples end on the batch's last tick
 
     # ---- ring envelopes: count / min / max / mean / spread across the rows of every sampled tick -------------------
     ENVELOPE_STATS = ("count", "min", "max", "mean", "m2")
 
     def _envelope_buffers(self, names, n_samples: int, period: int):
-        for name in names:
-            if name in self._windows:
-                raise ValueError(f"{name} is a window component: it is its own history (HipExec.component), the ring does not copy it per tick")
-        width = lambda name: 7 if name == "world_pos" else (self._aux[name].shape[1] if name in self._aux else 6)
-        raw = [np.empty((n_samples, max(period, 1), 5, width(name)), dtype=np.float64) for name in names]
+        raw = [np.empty((n_samples, max(period, 1), 5, self._recorded_width(name)), dtype=np.float64) for name in names]
         ptrs = (C.c_void_p * max(1, len(names)))(*[a.ctypes.data for a in raw])
         comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
         return raw, ptrs, comp
@@ -586,7 +576,7 @@ class HipExec:
         and std = sqrt(m2 / count).  Stateless: no watch is involved."""
         names = [names] if isinstance(names, str) else list(names)
         first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
-        n_samples = (last_tick - first_tick) // every + 1 if every > 0 and last_tick >= first_tick else 0
+        n_samples = self._sample_count(first_tick, last_tick, every)
         raw, ptrs, comp = self._envelope_buffers(names, n_samples, period)
         rc = self._lib.sixdof_history_envelope(self._h, comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), first_tick, n_samples, every,
                                                max(period, 0), ptrs, 0)
@@ -601,7 +591,6 @@ class HipExec:
         unless enable_history already made one at least that large).  `consume(batch_index, first_tick, {name: {statistic:
         [ticks_per_batch // every, period, w]}})` sees a batch once it has landed — first_tick is the batch's first SAMPLED
         tick; the arrays are views of buffers reused two batches later.  Returns the wall time in seconds."""
-        import time
         names = [names] if isinstance(names, str) else list(names)
         n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
         if every < 1 or ticks_per_batch < 1 or ticks_per_batch % every != 0:
@@ -613,28 +602,13 @@ class HipExec:
         n_samples = ticks_per_batch // every
         raw, ptrs, comps = zip(*[self._envelope_buffers(names, n_samples, period) for _ in range(2)])
         comp_p = comps[0].ctypes.data_as(C.POINTER(C.c_uint64))
+
+        def read(first_tick, k):
+            rc = self._lib.sixdof_history_envelope(self._h, comp_p, len(names), first_tick, n_samples, every, period, ptrs[k], L.ENVELOPE_ASYNC)
+            if rc != L.OK:
+                _raise(self._h, rc, "sixdof_history_envelope")
         self.sync()              # nothing of an earlier streaming run is in flight
-        self.set_flags(flags | L.FLAG_ASYNC_STEP)
-        t0 = time.perf_counter()
-        try:
-            first = []
-            for i in range(n_batches):
-                first.append(self.tick + every)                          # samples end on the batch's last tick
-                self.invoke_batch(ticks_per_batch)                       # enqueue batch i
-                if i > 0:
-                    self.download_wait()                                 # batch i-1 has landed in raw[(i-1) % 2]
-                    if consume is not None:
-                        consume(i - 1, first[i - 1], self._envelope_dict(names, raw[(i - 1) % 2]))
-                rc = self._lib.sixdof_history_envelope(self._h, comp_p, len(names), first[i], n_samples, every, period, ptrs[i % 2], L.ENVELOPE_ASYNC)
-                if rc != L.OK:
-                    _raise(self._h, rc, "sixdof_history_envelope")
-            self.download_wait()
-            if consume is not None and n_batches:
-                consume(n_batches - 1, first[-1], self._envelope_dict(names, raw[(n_batches - 1) % 2]))
-        finally:
-            self.set_flags(flags)
-            self.sync()          # also drops the page locks on `raw` before they go out of scope
-        return time.perf_counter() - t0
+        return self._stream_batches(n_batches, ticks_per_batch, every, read, lambda k: self._envelope_dict(names, raw[k]), consume, flags)
 
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))
@@ -662,7 +636,6 @@ class HipExec:
         page-locked host buffers on the copy stream while batch i+1 computes.  `consume(batch_index, first_tick,
         {column: array [ticks, n, w]})` sees a batch once it has landed (the arrays are reused two batches later).
         Returns the wall time in seconds."""
-        import time
         names = ("world_pos", "world_vel", "world_accel", "force")
         rc = self._lib.sixdof_set_history(self._h, 2 * int(ticks_per_batch))
         if rc != L.OK:
@@ -670,26 +643,38 @@ class HipExec:
         bufs = [{c: np.empty((ticks_per_batch, self.n, 7 if c == "world_pos" else 6), dtype=self.dtype) for c in columns}
                 for _ in range(2)]
         ptrs = [(C.c_void_p * 4)(*[b[c].ctypes.data if c in b else None for c in names]) for b in bufs]
+
+        def read(first_tick, k):       # batch i was recorded into ring half i % 2
+            rc = self._lib.sixdof_history_stream(self._h, first_tick, ticks_per_batch, ptrs[k])
+            if rc != L.OK:
+                _raise(self._h, rc, "sixdof_history_stream")
+        return self._stream_batches(n_batches, ticks_per_batch, 1, read, lambda k: bufs[k], consume, flags)
+
+    def _stream_batches(self, n_batches: int, ticks_per_batch: int, first_offset: int, read, landed, consume, flags: int) -> float:
+        """The double-buffered loop of stream_history / stream_series / stream_envelope: batch i is enqueued, then batch i-1 is
+        waited for and consumed, then batch i's read-back is enqueued into buffer set i % 2, where it overlaps batch i+1.
+        `first_offset`: the batch's first sampled tick, counted from the tick before the batch; `read(first_tick, k)` enqueues
+        the asynchronous read into buffer set k; `landed(k)` is what `consume(batch_index, first_tick, .)` receives of set k.
+        Whatever happens, the caller's flags are restored and the handle is drained.  Returns the wall time in seconds."""
+        import time
         self.set_flags(flags | L.FLAG_ASYNC_STEP)
         t0 = time.perf_counter()
         try:
             first = []
             for i in range(n_batches):
-                first.append(self.tick + 1)
-                self.invoke_batch(ticks_per_batch)                       # enqueue batch i (records into ring half i % 2)
+                first.append(self.tick + first_offset)
+                self.invoke_batch(ticks_per_batch)                       # enqueue batch i
                 if i > 0:
-                    self.download_wait()                                 # batch i-1 has landed in bufs[(i-1) % 2]
+                    self.download_wait()                                 # batch i-1 has landed in buffer set (i-1) % 2
                     if consume is not None:
-                        consume(i - 1, first[i - 1], bufs[(i - 1) % 2])
-                rc = self._lib.sixdof_history_stream(self._h, first[i], ticks_per_batch, ptrs[i % 2])
-                if rc != L.OK:
-                    _raise(self._h, rc, "sixdof_history_stream")
+                        consume(i - 1, first[i - 1], landed((i - 1) % 2))
+                read(first[i], i % 2)
             self.download_wait()
             if consume is not None and n_batches:
-                consume(n_batches - 1, first[-1], bufs[(n_batches - 1) % 2])
+                consume(n_batches - 1, first[-1], landed((n_batches - 1) % 2))
         finally:
             self.set_flags(flags)
-            self.sync()          # also drops the page locks on `bufs` before they go out of scope
+            self.sync()          # also drops the page locks on the buffer sets before they go out of scope
         return time.perf_counter() - t0
 
     def run_streaming(self, n_batches: int, ticks_per_batch: int, consume=None, flags: int = 0) -> float:

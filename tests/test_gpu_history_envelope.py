@@ -397,6 +397,46 @@ def test_async_envelope_alongside_a_history_stream_copy():
     hip.close()
 
 
+def test_two_staged_readers_and_a_stream_copy_pending_on_one_lane():
+    """A sixdof_history_stream copy, an asynchronous watch read, an asynchronous envelope read and a second, larger watch read
+    — whose staging buffer has to grow while the others are pending — all before ONE download_wait: every buffer holds the bits
+    of the blocking read of its range, made beforehand.  (The larger watch read's blocking twin goes through sixdof_history_read,
+    so that the watch staging buffer is still the smaller one when the asynchronous reads start.)"""
+    n, rows = 300, [0, 63, 64, 299]
+    hip, w = _exec(n, 4)
+    hip.enable_history(16)
+    hip.run(16)
+    names = ("world_pos", "world_vel")
+    hip.set_watch(names, np.asarray(w["entity_ids"])[rows])
+    want_blocks = {c: hip.history(c, 5, 12) for c in FIELDS}
+    want_short = hip.history_series(10, 16, 2)
+    want_env = [np.zeros((4, 12, 5, 7 if c == "world_pos" else 6)) for c in FIELDS]
+    assert _raw(hip, FIELDS, 10, 4, 2, 12, want_env) == L.OK
+    want_long = {c: np.ascontiguousarray(hip.history(c, 9, 16)[:, rows].transpose(1, 0, 2)) for c in names}
+
+    blocks = {c: np.zeros((8, n, 7 if c == "world_pos" else 6)) for c in FIELDS}
+    got_short, short_ptrs = hip._series_buffers(4)
+    got_env = [np.zeros_like(a) for a in want_env]
+    got_long, long_ptrs = hip._series_buffers(8)
+    assert hip._lib.sixdof_history_stream(hip._h, 5, 8, (C.c_void_p * 4)(*[blocks[c].ctypes.data for c in FIELDS])) == L.OK
+    assert hip._lib.sixdof_watch_read(hip._h, 10, 4, 2, short_ptrs, L.WATCH_ASYNC) == L.OK
+    assert _raw(hip, FIELDS, 10, 4, 2, 12, got_env, L.ENVELOPE_ASYNC) == L.OK
+    assert hip._lib.sixdof_watch_read(hip._h, 9, 8, 1, long_ptrs, L.WATCH_ASYNC) == L.OK
+    hip.download_wait()
+    for c in FIELDS:
+        assert blocks[c].tobytes() == want_blocks[c].tobytes(), c
+    for c in names:
+        assert got_short[c].tobytes() == want_short[c].tobytes(), c
+        assert got_long[c].shape == want_long[c].shape and got_long[c].tobytes() == want_long[c].tobytes(), c
+    for c, got, want in zip(FIELDS, got_env, want_env):
+        assert got.tobytes() == want.tobytes(), c
+    assert want_env[0][:, :, 0].min() == n // 12 and np.any(want_long["world_vel"] != 0)      # the twins read something
+    hip.run(4)                                               # the stepper goes on; the page locks end at sync
+    hip.sync()
+    assert hip.tick == 20
+    hip.close()
+
+
 # ---- 10. front end ---------------------------------------------------------------------------------------------------------
 def test_front_end_envelope_of_one_entity_is_its_series():
     spec = importlib.util.spec_from_file_location("ball", ROOT / "examples" / "ball.py")

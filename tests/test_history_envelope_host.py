@@ -22,6 +22,6 @@ def test_envelope_entry_point_over_the_fake_runtime():
                          env={"ASAN_OPTIONS": "detect_leaks=1", "UBSAN_OPTIONS": "print_stacktrace=1"})
     assert run.returncode == 0, (run.stdout[-500:], run.stderr[-3000:])
     assert "envelope_host_test: ok" in run.stdout, run.stdout[-500:]
-    faults = re.search(r"envelope_host_test: (\d+) fallible calls", run.stdout)
-    assert faults and int(faults.group(1)) >= 15, run.stdout[-500:]      # two allocations, launches, copies, events, waits
+    faults = re.findall(r"envelope_host_test: (\d+) fallible calls", run.stdout)     # the envelope sweep, then the watch sweep
+    assert len(faults) == 2 and all(int(f) >= 15 for f in faults), run.stdout[-500:]      # allocations, launches, copies, events, waits
     assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-3000:]
