@@ -83,7 +83,10 @@ using CustomLayoutFn = unsigned (*)();                                          
 using CustomLaunchFn = int (*)(const StepParams*, int integrator, int dtype, void* stream);  // returns hipError_t
 
 // ---- pairwise (edge_fold) path -----------------------------------------------------------------------
-// One tick = pack -> accumulate -> integrate (3 launches).  See nbody_kernels.hip.
+// Kernels and launch templates: pair_kernel.hpp (built-in folds: nbody_kernels.hip; user-written folds: generated units).
+// A batch of ticks is one pack launch, then per tick: all-pairs = accumulate + integrate (2 launches); edge lists = ONE
+// fold-and-integrate launch (+ 2 hub launches when there are hub sources); n <= kPairSmallMax = one launch for the whole batch.
+// Every tick writes the next tick's pack rows.
 constexpr int kPackWidth = 10;   // per source: p(c=0) p(c=1/2) p(c=1) mass
 constexpr int kPartialForce = 9;  // all-pairs gravity writes forces only
 constexpr int kPartialWidth = 18; // per target and source split: 3 stage positions x Force [tau(3), f(3)]
@@ -124,7 +127,7 @@ struct PairParams {
 };
 // Picks the number of source splits for n targets so the all-pairs grid fills 256 CUs.
 uint32_t pair_splits_for(uint32_t n);
-// n_ticks ticks: one pack launch (unless p.packed), then fold + integrate per tick (the integrate kernel writes the next pack rows).
+// n_ticks ticks: one pack launch (all-pairs: unless p.packed), then the tick's launches as above.  An edge list needs p.pack_next.
 hipError_t launch_pair_ticks(const PairParams& p, int integrator, uint32_t n_ticks, hipStream_t stream, uint64_t* launches);
 // n <= kPairSmallMax: pack, fold and integrate n_ticks ticks in one single-workgroup launch (bit-identical results).
 constexpr uint32_t kPairSmallMax = 256;

@@ -21,8 +21,12 @@
 //                            stage, RK4 combination, write pos / vel / accel / force — and the NEXT tick's pack row
 //                            from the state it has just formed, so a batch of ticks is pack + 2 launches per tick;
 //   edge lists (CSR):        2 + 3 in ONE launch per tick (pair_tick_fused_kernel, 3b: the lane folds its out-edges while its
-//                            state slabs land; pack rows double-buffered), hub sources folded by whole waves in front of it (2c).
-// instead of four dependent all-pairs sweeps.  Kernels 1 and 3 use the step kernel's memory plan (step_kernel.hpp):
+//                            state slabs land; pack rows double-buffered), hub sources folded by whole waves in front of it (2c);
+//   small graphs (n <= 256): 1 + 2 + 3 for a whole batch of ticks in ONE single-workgroup launch (pair_small_kernel)
+// instead of four dependent all-pairs sweeps.  Kernels 3 and 3b are one body, pair_wave_tick, and differ only in the fold they
+// hand it (sum the splits' partial rows | fold the out-edges) and in the pack buffer the next tick's rows go to; every path
+// reads an entity with read_entity, integrates it with pair_integrate_entity and writes it with write_entity / pack_row, which
+// is what keeps them bit-identical to each other.  Kernels 1, 3 and 3b use the step kernel's memory plan (step_kernel.hpp):
 // single-wave workgroups own 64 consecutive rows, whole slabs move HBM <-> LDS 16 B per lane (LDS-DMA on the way in), a lane
 // reads / writes its own row in LDS — no 56- / 48-byte-strided global access is left on the path.  Bound: f64 vector ALU (about 21 instructions per pair
 // evaluation, of which one v_rsq_f64 + refinement); bytes are negligible.  MFMA is not used: gfx950's
@@ -37,6 +41,7 @@
 #include "kernels.hpp"
 #include "spatial.hpp"
 #include "step_kernel.hpp"      // slab_dma_in / slab_out / the ragged-tail movers
+#include <type_traits>
 
 namespace sixdof {
 
@@ -233,13 +238,6 @@ __device__ __forceinline__ void edge_accumulate_range(const double* pack, uint32
     }
 }
 
-template <int NS, class PAIR>
-__device__ __forceinline__ void edge_accumulate(const double* pack, const uint32_t* __restrict__ row_start,
-                                                const uint32_t* __restrict__ dst, uint32_t i, double p0, double p1,
-                                                double (&acc)[3][6]) {
-    edge_accumulate_range<NS, PAIR>(pack, row_start[i], row_start[i + 1], dst, i, p0, p1, acc);
-}
-
 // ---- 2c. hub sources ----------------------------------------------------------------------------------------
 // One lane per source serialises on a source's out-degree: a hub with 10^5 out-edges would hold its wave for 10^5
 // dependent gathers while every other lane idles.  The reference buckets sources by out-degree for the same reason
@@ -378,11 +376,10 @@ __device__ __forceinline__ void pair_integrate_entity(const PairParams& P, const
     Fw = world_wrench<PIPE>(b.q, F);
 }
 
-__device__ __forceinline__ void load_entity(const PairParams& P, uint32_t i, EntityState& e, StepParams& SP,
-                                            Vec3<double> (&aux)[kMaxOps]) {
-    const double* pos = static_cast<const double*>(P.pos) + (size_t)i * 7;
-    const double* vel = static_cast<const double*>(P.vel) + (size_t)i * 6;
-    const double* in = static_cast<const double*>(P.inertia) + (size_t)i * 7;
+// The one EntityState reader: a row of pos / vel / inertia each, in LDS (the wave tick) or in global memory (the small-graph
+// kernel); read_spatial reads the world_accel row beside it.  1.0 / x stays an IEEE divide — four per entity and launch — because recip() may differ from it in the
+// last bit, and every path has to form the same inverses.
+__device__ __forceinline__ void read_entity(const double* pos, const double* vel, const double* in, EntityState& e) {
     e.q0 = {pos[0], pos[1], pos[2], pos[3]};
     e.p0 = {pos[4], pos[5], pos[6]};
     e.v0 = {{vel[0], vel[1], vel[2]}, {vel[3], vel[4], vel[5]}};
@@ -390,30 +387,15 @@ __device__ __forceinline__ void load_entity(const PairParams& P, uint32_t i, Ent
     e.inv_I = {1.0 / in[0], 1.0 / in[1], 1.0 / in[2]};
     e.mass = in[6];
     e.inv_m = 1.0 / in[6];
-    SP.n_ops = P.n_ops;   // view of the per-entity ops for the shared effector code
-    SP.vel_independent = 0;
-#pragma unroll
-    for (int k = 0; k < kMaxOps; k++) SP.ops[k] = P.ops[k];
-#pragma unroll
-    for (int k = 0; k < kMaxOps; k++) {
-        aux[k] = Vec3<double>{0, 0, 0};
-        if (k < (int)P.n_ops && P.ops[k].aux != nullptr) {
-            const double* a = static_cast<const double*>(P.ops[k].aux) + (size_t)i * 3;
-            aux[k] = Vec3<double>{a[0], a[1], a[2]};
-        }
-    }
 }
+__device__ __forceinline__ Spatial<double> read_spatial(const double* r) { return {{r[0], r[1], r[2]}, {r[3], r[4], r[5]}}; }
 
-__device__ __forceinline__ void store_entity(const PairParams& P, uint32_t i, const EntityState& e,
+// The one row writer: pos 7 / vel 6 / accel 6 / force 6 doubles, to LDS staging rows or to global rows.
+__device__ __forceinline__ void write_entity(double* pos, double* vel, double* ac, double* fo, const EntityState& e,
                                              const Spatial<double>& A, const Spatial<double>& Fw) {
-    double* pos = static_cast<double*>(P.pos) + (size_t)i * 7;
-    double* vel = static_cast<double*>(P.vel) + (size_t)i * 6;
     pos[0] = e.q0.i; pos[1] = e.q0.j; pos[2] = e.q0.k; pos[3] = e.q0.w; pos[4] = e.p0.x; pos[5] = e.p0.y; pos[6] = e.p0.z;
-    vel[0] = e.v0.ang.x; vel[1] = e.v0.ang.y; vel[2] = e.v0.ang.z;
-    vel[3] = e.v0.lin.x; vel[4] = e.v0.lin.y; vel[5] = e.v0.lin.z;
-    double* ac = static_cast<double*>(P.accel) + (size_t)i * 6;
+    vel[0] = e.v0.ang.x; vel[1] = e.v0.ang.y; vel[2] = e.v0.ang.z; vel[3] = e.v0.lin.x; vel[4] = e.v0.lin.y; vel[5] = e.v0.lin.z;
     ac[0] = A.ang.x; ac[1] = A.ang.y; ac[2] = A.ang.z; ac[3] = A.lin.x; ac[4] = A.lin.y; ac[5] = A.lin.z;
-    double* fo = static_cast<double*>(P.force) + (size_t)i * 6;
     fo[0] = Fw.ang.x; fo[1] = Fw.ang.y; fo[2] = Fw.ang.z; fo[3] = Fw.lin.x; fo[4] = Fw.lin.y; fo[5] = Fw.lin.z;
 }
 
@@ -433,15 +415,17 @@ __device__ __forceinline__ void load_ops(const PairParams& P, uint32_t i, bool a
     }
 }
 
-// The integrate half of an ALL-PAIRS tick (edge lists fold and integrate in one launch: 3b).  Single-wave workgroups, 64 rows
-// each (the step kernel's memory plan): pos / vel / inertia / world_accel come in as slabs by LDS-DMA; pos / vel / accel / force
-// and the NEXT tick's pack rows leave as slabs; the `splits` partial force sums (72 B each) are added per lane in fixed order.  The arithmetic is load_entity / pair_integrate_entity / pack_row, i.e. exactly the one-launch small-graph
-// kernel's: the two paths stay bit-identical (tests/test_gpu_parity.py::test_small_graph_single_launch_path_is_bit_identical).
-// (1.0 / x stays an IEEE divide here — four per entity and launch — because recip() may differ from it in the last bit.)
-template <int INTEGRATOR, bool PACK_NEXT>
-__global__ __launch_bounds__(kWave) void pair_integrate_kernel(const PairParams P) {
+// One tick of the 64 rows a single-wave workgroup owns (the step kernel's memory plan) — the body of both per-wave kernels below.
+// pos / vel / inertia / world_accel come in as slabs by LDS-DMA (ragged last wave: the tail movers) and the effector columns per
+// lane; while they are in flight every active lane forms its stage forces: `fold(i, pf)` fills pf and says whether row i is an
+// edge source.  One wait and a barrier, each lane reads its row, a second barrier hands LDS over as the output staging area, the
+// lane integrates (pair_integrate_entity) and stages its rows, a third barrier, and pos / vel / accel / force leave as slabs
+// together with the NEXT tick's pack rows, which go to `pack_out`.  `lds`: kWave * 35 doubles, 16-byte aligned.
+// The arithmetic is read_entity / pair_integrate_entity / write_entity / pack_row, i.e. exactly the one-launch small-graph
+// kernel's: the paths stay bit-identical (tests/test_gpu_parity.py::test_small_graph_single_launch_path_is_bit_identical).
+template <int INTEGRATOR, class FOLD>
+__device__ __forceinline__ void pair_wave_tick(const PairParams& P, double* const lds, double* const pack_out, FOLD&& fold) {
     // in: pos 7 | vel 6 | inertia 7 | accel 6 = 26 doubles per row; out: pos 7 | vel 6 | accel 6 | force 6 | pack 10 = 35
-    __shared__ __attribute__((aligned(16))) double lds[kWave * 35];
     double* const l_pos = lds;
     double* const l_vel = lds + kWave * 7;
     double* const l_in = lds + kWave * 13;
@@ -468,34 +452,16 @@ __global__ __launch_bounds__(kWave) void pair_integrate_kernel(const PairParams 
     StepParams SP;
     Vec3<double> aux[kMaxOps];
     load_ops(P, i, active, SP, aux);
-    constexpr int NS = INTEGRATOR == kRk4 ? 3 : 1;
     double pf[3][6] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
-    const bool is_source = active && P.n > 1;
-    if (active) {      // `splits` partial sums of 72 bytes each, added in fixed order (deterministic)
-        for (uint32_t sp = 0; sp < P.splits; sp++) {
-            const double* part = P.partial + ((size_t)sp * P.n + i) * kPartialForce;
-#pragma unroll
-            for (int st = 0; st < NS; st++)
-                for (int c = 0; c < 3; c++) pf[st][3 + c] += part[3 * st + c];
-        }
-    }
+    bool is_source = false;
+    if (active) is_source = fold(i, pf);      // while the slabs land
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // LDS-DMA data has landed
     __syncthreads();
     EntityState e;
     Spatial<double> A = {{0, 0, 0}, {0, 0, 0}}, Fw = {{0, 0, 0}, {0, 0, 0}};
     if (active) {
-        const double* pos = l_pos + t * 7;
-        const double* vel = l_vel + t * 6;
-        const double* in = l_in + t * 7;
-        e.q0 = {pos[0], pos[1], pos[2], pos[3]};
-        e.p0 = {pos[4], pos[5], pos[6]};
-        e.v0 = {{vel[0], vel[1], vel[2]}, {vel[3], vel[4], vel[5]}};
-        e.I = {in[0], in[1], in[2]};
-        e.inv_I = {1.0 / in[0], 1.0 / in[1], 1.0 / in[2]};
-        e.mass = in[6];
-        e.inv_m = 1.0 / in[6];
-        const double* ac = l_acc + t * 6;
-        A = Spatial<double>{{ac[0], ac[1], ac[2]}, {ac[3], ac[4], ac[5]}};
+        read_entity(l_pos + t * 7, l_vel + t * 6, l_in + t * 7, e);
+        A = read_spatial(l_acc + t * 6);
     }
     __syncthreads();  // every lane has consumed the input slabs; LDS is the output staging area from here on
     if (active) pair_integrate_entity<INTEGRATOR>(P, SP, aux, pf, is_source, e, A, Fw);
@@ -505,34 +471,43 @@ __global__ __launch_bounds__(kWave) void pair_integrate_kernel(const PairParams 
     double* const o_force = lds + kWave * 19;
     double* const o_pack = lds + kWave * 25;
     if (active) {
-        double* r = o_pos + t * 7;
-        r[0] = e.q0.i; r[1] = e.q0.j; r[2] = e.q0.k; r[3] = e.q0.w; r[4] = e.p0.x; r[5] = e.p0.y; r[6] = e.p0.z;
-        double* v = o_vel + t * 6;
-        v[0] = e.v0.ang.x; v[1] = e.v0.ang.y; v[2] = e.v0.ang.z; v[3] = e.v0.lin.x; v[4] = e.v0.lin.y; v[5] = e.v0.lin.z;
-        double* a = o_acc + t * 6;
-        a[0] = A.ang.x; a[1] = A.ang.y; a[2] = A.ang.z; a[3] = A.lin.x; a[4] = A.lin.y; a[5] = A.lin.z;
-        double* f = o_force + t * 6;
-        f[0] = Fw.ang.x; f[1] = Fw.ang.y; f[2] = Fw.ang.z; f[3] = Fw.lin.x; f[4] = Fw.lin.y; f[5] = Fw.lin.z;
-        if constexpr (PACK_NEXT) {
-            const double x[3] = {e.p0.x, e.p0.y, e.p0.z}, vl[3] = {e.v0.lin.x, e.v0.lin.y, e.v0.lin.z};
-            pack_row(o_pack + t * kPackWidth, x, vl, e.mass, P.dt_g * 0.5, P.dt_g);
-        }
+        write_entity(o_pos + t * 7, o_vel + t * 6, o_acc + t * 6, o_force + t * 6, e, A, Fw);
+        const double x[3] = {e.p0.x, e.p0.y, e.p0.z}, vl[3] = {e.v0.lin.x, e.v0.lin.y, e.v0.lin.z};
+        pack_row(o_pack + t * kPackWidth, x, vl, e.mass, P.dt_g * 0.5, P.dt_g);
     }
     __syncthreads();
-    double* const g_pack = P.pack + (size_t)row0 * kPackWidth;
+    double* const g_pack = pack_out + (size_t)row0 * kPackWidth;
     if (full) {
         slab_out<kWave * 7 * 8, kPolPlain>(reinterpret_cast<const char*>(o_pos), reinterpret_cast<char*>(g_pos), t);
         slab_out<kWave * 6 * 8, kPolPlain>(reinterpret_cast<const char*>(o_vel), reinterpret_cast<char*>(g_vel), t);
         slab_out<kWave * 6 * 8, kPolPlain>(reinterpret_cast<const char*>(o_acc), reinterpret_cast<char*>(g_acc), t);
         slab_out<kWave * 6 * 8, kPolNtStores>(reinterpret_cast<const char*>(o_force), reinterpret_cast<char*>(g_force), t);   // written, never read back
-        if constexpr (PACK_NEXT) slab_out<kWave * kPackWidth * 8, kPolPlain>(reinterpret_cast<const char*>(o_pack), reinterpret_cast<char*>(g_pack), t);
+        slab_out<kWave * kPackWidth * 8, kPolPlain>(reinterpret_cast<const char*>(o_pack), reinterpret_cast<char*>(g_pack), t);
     } else {
         slab_out_tail(o_pos, g_pos, rows * 7, t);
         slab_out_tail(o_vel, g_vel, rows * 6, t);
         slab_out_tail(o_acc, g_acc, rows * 6, t);
         slab_out_tail(o_force, g_force, rows * 6, t);
-        if constexpr (PACK_NEXT) slab_out_tail(o_pack, g_pack, rows * kPackWidth, t);
+        slab_out_tail(o_pack, g_pack, rows * kPackWidth, t);
     }
+}
+
+// The integrate half of an ALL-PAIRS tick (edge lists fold and integrate in one launch: 3b): the `splits` partial force sums of
+// allpairs_kernel (72 B each) are added per lane in fixed order (deterministic); the next tick's pack rows overwrite `pack`,
+// which no wave of this launch reads.
+template <int INTEGRATOR>
+__global__ __launch_bounds__(kWave) void pair_integrate_kernel(const PairParams P) {
+    __shared__ __attribute__((aligned(16))) double lds[kWave * 35];
+    constexpr int NS = INTEGRATOR == kRk4 ? 3 : 1;
+    pair_wave_tick<INTEGRATOR>(P, lds, P.pack, [&](uint32_t i, double (&pf)[3][6]) {
+        for (uint32_t sp = 0; sp < P.splits; sp++) {
+            const double* part = P.partial + ((size_t)sp * P.n + i) * kPartialForce;
+#pragma unroll
+            for (int st = 0; st < NS; st++)
+                for (int c = 0; c < 3; c++) pf[st][3 + c] += part[3 * st + c];
+        }
+        return P.n > 1;
+    });
 }
 
 // ---- 3b. edge lists: fold + integrate in ONE launch (hub sources' sums come from the two hub launches in front of it) -------------
@@ -540,42 +515,13 @@ __global__ __launch_bounds__(kWave) void pair_integrate_kernel(const PairParams 
 // With the pack rows double-buffered — this tick reads `pack`, writes the next tick's rows to `pack_next` — nothing a wave reads
 // is written by another wave of the same launch, so the two halves need no launch boundary between them: a tick is one kernel,
 // the [n, 18] partial rows (144 B written and read back per entity and tick) never exist, and the state slabs' LDS-DMA is in
-// flight while the lane folds its edges.  Same device functions as the two-kernel path in the same order: identical bits.
+// flight while the lane folds its edges (pair_wave_tick).
 template <int INTEGRATOR, class PAIR>
 __global__ __launch_bounds__(kWave) void pair_tick_fused_kernel(const PairParams P) {
-    __shared__ __attribute__((aligned(16))) double lds[kWave * 35];      // in: pos 7 | vel 6 | inertia 7 | accel 6; out: + force 6 | pack 10
-    double* const l_pos = lds;
-    double* const l_vel = lds + kWave * 7;
-    double* const l_in = lds + kWave * 13;
-    double* const l_acc = lds + kWave * 20;
-    const uint32_t row0 = blockIdx.x * kWave, t = threadIdx.x, i = row0 + t;
-    const uint32_t rows = min((uint32_t)kWave, P.n - row0);
-    const bool full = rows == kWave, active = t < rows;
-    double* const g_pos = static_cast<double*>(P.pos) + (size_t)row0 * 7;
-    double* const g_vel = static_cast<double*>(P.vel) + (size_t)row0 * 6;
-    double* const g_acc = static_cast<double*>(P.accel) + (size_t)row0 * 6;
-    double* const g_force = static_cast<double*>(P.force) + (size_t)row0 * 6;
-    const double* const g_in = static_cast<const double*>(P.inertia) + (size_t)row0 * 7;
-    if (full) {
-        slab_dma_in<kWave * 7 * 8, kPolPlain>(reinterpret_cast<const char*>(g_pos), reinterpret_cast<char*>(l_pos), t);
-        slab_dma_in<kWave * 6 * 8, kPolPlain>(reinterpret_cast<const char*>(g_vel), reinterpret_cast<char*>(l_vel), t);
-        slab_dma_in<kWave * 7 * 8, kPolPlain>(reinterpret_cast<const char*>(g_in), reinterpret_cast<char*>(l_in), t);
-        slab_dma_in<kWave * 6 * 8, kPolPlain>(reinterpret_cast<const char*>(g_acc), reinterpret_cast<char*>(l_acc), t);
-    } else {
-        slab_in_tail(g_pos, l_pos, rows * 7, t);
-        slab_in_tail(g_vel, l_vel, rows * 6, t);
-        slab_in_tail(g_in, l_in, rows * 7, t);
-        slab_in_tail(g_acc, l_acc, rows * 6, t);
-    }
-    StepParams SP;
-    Vec3<double> aux[kMaxOps];
-    load_ops(P, i, active, SP, aux);
+    __shared__ __attribute__((aligned(16))) double lds[kWave * 35];
     constexpr int NS = INTEGRATOR == kRk4 ? 3 : 1;
-    double pf[3][6] = {{0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
-    bool is_source = false;
-    if (active) {      // the fold, while the slabs land
+    pair_wave_tick<INTEGRATOR>(P, lds, P.pack_next, [&](uint32_t i, double (&pf)[3][6]) {
         const uint32_t e0 = P.row_start[i], e1 = P.row_start[i + 1];
-        is_source = e1 > e0;
         if (PAIR::kAdditive && P.n_hubs && e1 - e0 >= kHubDegree) {
             // a hub source: its edges were folded by whole waves in front of this launch (2c), the sums wait in its partial row
             const double* part = P.partial + (size_t)i * kPartialWidth;
@@ -585,59 +531,8 @@ __global__ __launch_bounds__(kWave) void pair_tick_fused_kernel(const PairParams
         } else {
             edge_accumulate_range<NS, PAIR>(P.pack, e0, e1, P.dst, i, P.p0, P.p1, pf);
         }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    EntityState e;
-    Spatial<double> A = {{0, 0, 0}, {0, 0, 0}}, Fw = {{0, 0, 0}, {0, 0, 0}};
-    if (active) {
-        const double* pos = l_pos + t * 7;
-        const double* vel = l_vel + t * 6;
-        const double* in = l_in + t * 7;
-        e.q0 = {pos[0], pos[1], pos[2], pos[3]};
-        e.p0 = {pos[4], pos[5], pos[6]};
-        e.v0 = {{vel[0], vel[1], vel[2]}, {vel[3], vel[4], vel[5]}};
-        e.I = {in[0], in[1], in[2]};
-        e.inv_I = {1.0 / in[0], 1.0 / in[1], 1.0 / in[2]};
-        e.mass = in[6];
-        e.inv_m = 1.0 / in[6];
-        const double* ac = l_acc + t * 6;
-        A = Spatial<double>{{ac[0], ac[1], ac[2]}, {ac[3], ac[4], ac[5]}};
-    }
-    __syncthreads();
-    if (active) pair_integrate_entity<INTEGRATOR>(P, SP, aux, pf, is_source, e, A, Fw);
-    double* const o_pos = lds;
-    double* const o_vel = lds + kWave * 7;
-    double* const o_acc = lds + kWave * 13;
-    double* const o_force = lds + kWave * 19;
-    double* const o_pack = lds + kWave * 25;
-    if (active) {
-        double* r = o_pos + t * 7;
-        r[0] = e.q0.i; r[1] = e.q0.j; r[2] = e.q0.k; r[3] = e.q0.w; r[4] = e.p0.x; r[5] = e.p0.y; r[6] = e.p0.z;
-        double* v = o_vel + t * 6;
-        v[0] = e.v0.ang.x; v[1] = e.v0.ang.y; v[2] = e.v0.ang.z; v[3] = e.v0.lin.x; v[4] = e.v0.lin.y; v[5] = e.v0.lin.z;
-        double* a = o_acc + t * 6;
-        a[0] = A.ang.x; a[1] = A.ang.y; a[2] = A.ang.z; a[3] = A.lin.x; a[4] = A.lin.y; a[5] = A.lin.z;
-        double* f = o_force + t * 6;
-        f[0] = Fw.ang.x; f[1] = Fw.ang.y; f[2] = Fw.ang.z; f[3] = Fw.lin.x; f[4] = Fw.lin.y; f[5] = Fw.lin.z;
-        const double x[3] = {e.p0.x, e.p0.y, e.p0.z}, vl[3] = {e.v0.lin.x, e.v0.lin.y, e.v0.lin.z};
-        pack_row(o_pack + t * kPackWidth, x, vl, e.mass, P.dt_g * 0.5, P.dt_g);
-    }
-    __syncthreads();
-    double* const g_pack = P.pack_next + (size_t)row0 * kPackWidth;
-    if (full) {
-        slab_out<kWave * 7 * 8, kPolPlain>(reinterpret_cast<const char*>(o_pos), reinterpret_cast<char*>(g_pos), t);
-        slab_out<kWave * 6 * 8, kPolPlain>(reinterpret_cast<const char*>(o_vel), reinterpret_cast<char*>(g_vel), t);
-        slab_out<kWave * 6 * 8, kPolPlain>(reinterpret_cast<const char*>(o_acc), reinterpret_cast<char*>(g_acc), t);
-        slab_out<kWave * 6 * 8, kPolNtStores>(reinterpret_cast<const char*>(o_force), reinterpret_cast<char*>(g_force), t);
-        slab_out<kWave * kPackWidth * 8, kPolPlain>(reinterpret_cast<const char*>(o_pack), reinterpret_cast<char*>(g_pack), t);
-    } else {
-        slab_out_tail(o_pos, g_pos, rows * 7, t);
-        slab_out_tail(o_vel, g_vel, rows * 6, t);
-        slab_out_tail(o_acc, g_acc, rows * 6, t);
-        slab_out_tail(o_force, g_force, rows * 6, t);
-        slab_out_tail(o_pack, g_pack, rows * kPackWidth, t);
-    }
+        return e1 > e0;
+    });
 }
 
 // ---- small graphs: the whole tick (and n_ticks of them) in ONE single-workgroup launch --------------------------
@@ -654,7 +549,11 @@ __global__ __launch_bounds__(kTile) void pair_small_kernel(const PairParams P, u
     EntityState e;
     StepParams SP;
     Vec3<double> aux[kMaxOps];
-    if (active) load_entity(P, i, e, SP, aux);
+    if (active) {
+        read_entity(static_cast<const double*>(P.pos) + (size_t)i * 7, static_cast<const double*>(P.vel) + (size_t)i * 6,
+                    static_cast<const double*>(P.inertia) + (size_t)i * 7, e);
+        load_ops(P, i, true, SP, aux);
+    }
     const bool allpairs = P.pair_kind == SIXDOF_EFF_ALLPAIRS_GRAVITY_SOFTENED;
     // CSR range of this source in registers, targets in LDS: the per-tick fold then touches no global memory
     uint32_t e0 = 0, e1 = 0;
@@ -668,10 +567,8 @@ __global__ __launch_bounds__(kTile) void pair_small_kernel(const PairParams P, u
     const bool is_source = active && (allpairs ? (P.n > 1) : (e1 > e0));
     const double h1 = P.dt_g * 0.5, h3 = P.dt_g;
     Spatial<double> A = {{0, 0, 0}, {0, 0, 0}}, Fw = {{0, 0, 0}, {0, 0, 0}};
-    if (active) {   // a_in of the first tick = the world_accel column; of later ticks = the previous tick's A, in registers
-        const double* ac = static_cast<const double*>(P.accel) + (size_t)i * 6;
-        A = Spatial<double>{{ac[0], ac[1], ac[2]}, {ac[3], ac[4], ac[5]}};
-    }
+    // a_in of the first tick = the world_accel column; of later ticks = the previous tick's A, in registers
+    if (active) A = read_spatial(static_cast<const double*>(P.accel) + (size_t)i * 6);
     for (uint32_t t = 0; t < n_ticks; t++) {
         if (active) {
             const double x[3] = {e.p0.x, e.p0.y, e.p0.z}, v[3] = {e.v0.lin.x, e.v0.lin.y, e.v0.lin.z};
@@ -703,7 +600,9 @@ __global__ __launch_bounds__(kTile) void pair_small_kernel(const PairParams P, u
         __syncthreads();   // every lane has read the packed sources before the next tick overwrites them
         if (active) pair_integrate_entity<INTEGRATOR>(P, SP, aux, pf, is_source, e, A, Fw);
     }
-    if (active && n_ticks) store_entity(P, i, e, A, Fw);
+    if (active && n_ticks)
+        write_entity(static_cast<double*>(P.pos) + (size_t)i * 7, static_cast<double*>(P.vel) + (size_t)i * 6,
+                     static_cast<double*>(P.accel) + (size_t)i * 6, static_cast<double*>(P.force) + (size_t)i * 6, e, A, Fw);
 }
 
 // ---- launch helpers (shared with generated translation units) ------------------------------------------------
@@ -716,88 +615,78 @@ inline uint32_t pair_splits_for_n(uint32_t n) {
     return s ? s : 1;
 }
 
-// n <= kPairSmallMax: one single-workgroup launch for n_ticks ticks.
 // ONLY: -1 instantiates both integrators (the product library); a generated object built for one executor names the integrator
-// it will be launched with and carries that kernel alone — half the device code to compile (codegen.generate_pair_source).
-// Launching such an object with the other integrator is an error, not a silent substitution.
+// it will be launched with and carries those kernels alone — half the device code to compile (codegen.generate_pair_source).
+// Calls f(std::integral_constant<int, kRk4 or kSemiImplicit>) for `integrator`; the other arm is not instantiated when ONLY
+// excludes it.  Launching such an object with the other integrator is an error, not a silent substitution: the callers refuse it.
+template <int ONLY, class F>
+inline void with_integrator(int integrator, F&& f) {
+    if constexpr (ONLY != kSemiImplicit) {
+        if (integrator == kRk4) f(std::integral_constant<int, kRk4>{});
+    }
+    if constexpr (ONLY != kRk4) {
+        if (integrator != kRk4) f(std::integral_constant<int, kSemiImplicit>{});
+    }
+}
+
+// n <= kPairSmallMax: one single-workgroup launch for n_ticks ticks.
 template <class PAIR, int ONLY = -1>
 inline hipError_t launch_pair_small_t(const PairParams& p, int integrator, uint32_t n_ticks, hipStream_t stream,
                                       uint64_t* launches) {
     if (p.n == 0 || n_ticks == 0) return hipSuccess;
     if (ONLY >= 0 && integrator != ONLY) return hipErrorInvalidValue;
     const dim3 block(p.n <= 64 ? 64 : kTile);   // one wave when it suffices: its barriers cost nothing
-    if constexpr (ONLY != kSemiImplicit) {
-        if (integrator == kRk4) hipLaunchKernelGGL((pair_small_kernel<kRk4, PAIR>), dim3(1), block, 0, stream, p, n_ticks);
-    }
-    if constexpr (ONLY != kRk4) {
-        if (integrator != kRk4) hipLaunchKernelGGL((pair_small_kernel<kSemiImplicit, PAIR>), dim3(1), block, 0, stream, p, n_ticks);
-    }
+    with_integrator<ONLY>(integrator, [&](auto ic) {
+        hipLaunchKernelGGL((pair_small_kernel<decltype(ic)::value, PAIR>), dim3(1), block, 0, stream, p, n_ticks);
+    });
     if (launches) *launches += 1;
     return hipGetLastError();
 }
 
-// A batch of ticks: pack once (unless the caller says `pack` already holds the rows of the current state: `packed`), then per
-// tick fold -> integrate, the integrate kernel writing the next tick's pack rows.  ALLPAIRS selects the tiled complete-graph
-// kernel (softened gravity).  `last_packs`: the final tick also leaves its pack rows (so a following batch may skip the pack).
+// A batch of ticks.  All-pairs (ALLPAIRS: the tiled complete-graph kernel, softened gravity): pack once (unless the caller says
+// `pack` already holds the rows of the current state: `packed`), then per tick accumulate -> integrate, the integrate kernel
+// writing the next tick's pack rows.  Edge lists: pack (every batch: the two pack buffers alternate), then ONE launch per tick
+// (+ the two hub launches in front of it when there are hub sources).
 template <class PAIR, bool ALLPAIRS, int ONLY = -1>
 inline hipError_t launch_pair_ticks_t(const PairParams& p, int integrator, uint32_t n_ticks, bool packed, hipStream_t stream, uint64_t* launches) {
     if (p.n == 0 || n_ticks == 0) return hipSuccess;
     if (ONLY >= 0 && integrator != ONLY) return hipErrorInvalidValue;
+    // an edge list without the second pack buffer (PairParams::pack_next): not a launch this library makes
+    if (!ALLPAIRS && p.pack_next == nullptr) return hipErrorInvalidValue;
     const uint32_t waves = (p.n + kWave - 1) / kWave;
-    const double h1 = p.dt_g * 0.5, h3 = p.dt_g;
-    const bool fused_path = !ALLPAIRS && p.pack_next != nullptr;      // (its buffers alternate: every batch packs)
-    if (!packed || fused_path) {
+    if (!packed || !ALLPAIRS) {
         hipLaunchKernelGGL(pair_pack_kernel, dim3(waves), dim3(kWave), 0, stream, static_cast<const double*>(p.pos),
-                           static_cast<const double*>(p.vel), static_cast<const double*>(p.inertia), p.pack, p.n, h1, h3);
+                           static_cast<const double*>(p.vel), static_cast<const double*>(p.inertia), p.pack, p.n, p.dt_g * 0.5, p.dt_g);
         if (launches) *launches += 1;
     }
-    const bool rk4 = integrator == kRk4;
-    if constexpr (!ALLPAIRS) {
-        // with a second pack buffer: ONE launch per tick (+ the two hub launches in front of it when there are hub sources)
-        if (p.pack_next != nullptr) {
+    with_integrator<ONLY>(integrator, [&](auto ic) {
+        constexpr int I = decltype(ic)::value, NS = I == kRk4 ? 3 : 1;
+        if constexpr (ALLPAIRS) {
+            const dim3 grid((p.n + kTile - 1) / kTile, p.splits);
+            for (uint32_t t = 0; t < n_ticks; t++) {
+                hipLaunchKernelGGL(allpairs_kernel<NS>, grid, dim3(kTile), 0, stream, p.pack, p.partial, p.n, p.splits, p.p0, p.p1);
+                // every tick writes the next tick's pack rows (5 KB per wave beside the 12.5 KB of state it writes anyway)
+                hipLaunchKernelGGL(pair_integrate_kernel<I>, dim3(waves), dim3(kWave), 0, stream, p);
+                if (launches) *launches += 2;
+            }
+        } else {
             PairParams q = p;
             const uint32_t hubs = PAIR::kAdditive ? p.n_hubs : 0u;
             for (uint32_t t = 0; t < n_ticks; t++) {
                 if (hubs) {
-                    if constexpr (ONLY != kSemiImplicit) if (rk4) {
-                        hipLaunchKernelGGL((edge_hub_chunk_kernel<3, PAIR>), dim3(q.n_hub_chunks), dim3(64), 0, stream, q.pack, q.row_start, q.dst, q.chunk_e0, q.chunk_row, q.chunk_partial, q.p0, q.p1);
-                        hipLaunchKernelGGL(edge_hub_reduce_kernel<3>, dim3(hubs), dim3(64), 0, stream, q.hub_rows, q.hub_chunk_start, q.chunk_partial, q.partial);
-                    }
-                    if constexpr (ONLY != kRk4) if (!rk4) {
-                        hipLaunchKernelGGL((edge_hub_chunk_kernel<1, PAIR>), dim3(q.n_hub_chunks), dim3(64), 0, stream, q.pack, q.row_start, q.dst, q.chunk_e0, q.chunk_row, q.chunk_partial, q.p0, q.p1);
-                        hipLaunchKernelGGL(edge_hub_reduce_kernel<1>, dim3(hubs), dim3(64), 0, stream, q.hub_rows, q.hub_chunk_start, q.chunk_partial, q.partial);
-                    }
+                    hipLaunchKernelGGL((edge_hub_chunk_kernel<NS, PAIR>), dim3(q.n_hub_chunks), dim3(64), 0, stream, q.pack, q.row_start, q.dst, q.chunk_e0, q.chunk_row, q.chunk_partial, q.p0, q.p1);
+                    hipLaunchKernelGGL(edge_hub_reduce_kernel<NS>, dim3(hubs), dim3(64), 0, stream, q.hub_rows, q.hub_chunk_start, q.chunk_partial, q.partial);
                     if (launches) *launches += 2;
                 }
-                if constexpr (ONLY != kSemiImplicit) { if (rk4) hipLaunchKernelGGL((pair_tick_fused_kernel<kRk4, PAIR>), dim3(waves), dim3(kWave), 0, stream, q); }
-                if constexpr (ONLY != kRk4) { if (!rk4) hipLaunchKernelGGL((pair_tick_fused_kernel<kSemiImplicit, PAIR>), dim3(waves), dim3(kWave), 0, stream, q); }
+                hipLaunchKernelGGL((pair_tick_fused_kernel<I, PAIR>), dim3(waves), dim3(kWave), 0, stream, q);
                 double* const cur = q.pack;      // the rows just written are the next tick's
                 q.pack = q.pack_next;
                 q.pack_next = cur;
                 if (launches) *launches += 1;
             }
-            return hipGetLastError();
         }
-    }
-    if constexpr (ALLPAIRS) {
-        for (uint32_t t = 0; t < n_ticks; t++) {
-            const dim3 grid((p.n + kTile - 1) / kTile, p.splits);
-            if constexpr (ONLY != kSemiImplicit) { if (rk4) hipLaunchKernelGGL(allpairs_kernel<3>, grid, dim3(kTile), 0, stream, p.pack, p.partial, p.n, p.splits, p.p0, p.p1); }
-            if constexpr (ONLY != kRk4) { if (!rk4) hipLaunchKernelGGL(allpairs_kernel<1>, grid, dim3(kTile), 0, stream, p.pack, p.partial, p.n, p.splits, p.p0, p.p1); }
-            // every tick writes the next tick's pack rows (5 KB per wave beside the 12.5 KB of state it writes anyway)
-            if constexpr (ONLY != kSemiImplicit) { if (rk4) hipLaunchKernelGGL((pair_integrate_kernel<kRk4, true>), dim3(waves), dim3(kWave), 0, stream, p); }
-            if constexpr (ONLY != kRk4) { if (!rk4) hipLaunchKernelGGL((pair_integrate_kernel<kSemiImplicit, true>), dim3(waves), dim3(kWave), 0, stream, p); }
-            if (launches) *launches += 2;
-        }
-        return hipGetLastError();
-    }
-    return hipErrorInvalidValue;      // an edge list without the second pack buffer (PairParams::pack_next): not a launch this library makes
-}
-
-// One tick on its own (pack, then fold + integrate).
-template <class PAIR, bool ALLPAIRS, int ONLY = -1>
-inline hipError_t launch_pair_tick_t(const PairParams& p, int integrator, hipStream_t stream, uint64_t* launches) {
-    return launch_pair_ticks_t<PAIR, ALLPAIRS, ONLY>(p, integrator, 1, false, stream, launches);
+    });
+    return hipGetLastError();
 }
 
 }  // namespace sixdof

@@ -536,7 +536,7 @@ def test_streaming_path_at_2m_bodies():
 @pytest.mark.parametrize("kind", ["three_body", "allpairs"])
 def test_small_graph_single_launch_path_is_bit_identical(kind):
     """n <= 256: pack + fold + integrate (and ticks_per_launch ticks) in one single-workgroup launch; must equal the
-    three-kernel path bit for bit."""
+    multi-kernel path bit for bit."""
     import os
     if kind == "three_body":
         g = gu.load("three_body")
@@ -566,6 +566,85 @@ def test_small_graph_single_launch_path_is_bit_identical(kind):
         a = getattr(runs["three_kernels"][0], f)
         assert np.array_equal(a, getattr(runs["small_k1"][0], f)), f
         assert np.array_equal(a, getattr(runs["small_k16"][0], f)), f
+
+
+def _two_waves_and_a_tail(kind, hubs=False):
+    """130 rows = two full waves and a 2-row tail.  Out-degrees from {0, 1, 4, 5, 31} (all below kHubDegree = 32): a target-only
+    row in every wave, sources that fill a batch of four gathers, a batch plus a remainder, and 7 batches + 3; the spawn order
+    interleaves the sources.  `hubs`: row 17 gets an edge to every other row (129: one hub chunk), row 100 gets 33."""
+    n = 130
+    rng = np.random.default_rng(23)
+    pos, vel, inertia = _plummer(n, seed=13)
+    deg = rng.choice([0, 1, 4, 5, 31], n)
+    deg[[0, 65, 128]] = [31, 5, 4]
+    deg[[3, 73, 129]] = 0                                   # one target-only row in each wave, the ragged one included
+    if hubs:
+        deg[[17, 100]] = [n - 1, 33]
+    frm, to = [], []
+    for src in range(n):
+        frm += [src + 1] * int(deg[src])
+        to += list(rng.permutation(np.delete(np.arange(n), src))[:deg[src]] + 1)
+    order = rng.permutation(len(frm))
+    frm, to = np.array(frm, dtype=np.uint64)[order], np.array(to, dtype=np.uint64)[order]
+    g = (0.0, 0.0, -1e-12)
+    if kind == "newton":
+        op, hk, ok = (K_SQ,), L.EFF_EDGE_GRAVITY_NEWTON, orc.EFF_EDGE_GRAVITY_NEWTON
+    else:
+        op, hk, ok = (K_SQ, EPS_AU2), L.EFF_EDGE_GRAVITY_SOFTENED, orc.EFF_EDGE_GRAVITY_SOFTENED
+    eff = [ea.Effector(L.EFF_UNIFORM_GRAVITY, g), ea.Effector(hk, op)]
+    ops = [(orc.EFF_UNIFORM_GRAVITY, g, None), (ok, op, None)]
+    ids = np.arange(1, n + 1, dtype=np.uint64)
+    return (pos, vel, inertia), eff, ops, (frm, to), orc.resolve_edges(ids, frm, to), deg, g
+
+
+@pytest.mark.parametrize("kind", ["newton", "softened"])
+@pytest.mark.parametrize("integrator", [L.RK4, L.SEMI_IMPLICIT])
+def test_whole_waves_of_the_fused_launch_equal_the_small_kernel_bit_for_bit(kind, integrator, monkeypatch):
+    """The fused fold-and-integrate launch on whole waves (state slabs by LDS-DMA) and on a ragged tail in one run, per-entity
+    gravity in front of the edge fold, against the one-launch small-graph kernel: all five Body columns bit for bit; against the
+    oracle's sequential fold within 1e-9; target-only rows keep the per-entity gravity in `force`."""
+    ticks = 7
+    (pos, vel, inertia), eff, ops, edges, edge_rows, deg, g = _two_waves_and_a_tail(kind)
+    runs = {}
+    for label, env, k in (("multi", "0", 1), ("small_k1", None, 1), ("small_k4", None, 4)):
+        if env is None:
+            monkeypatch.delenv("SIXDOF_PAIR_SMALL", raising=False)
+        else:
+            monkeypatch.setenv("SIXDOF_PAIR_SMALL", env)
+        ex = ea.HipExec(pos, vel, inertia, simulation_time_step=3600.0, integrator=integrator, ticks_per_launch=k, effectors=eff, edges=edges)
+        runs[label] = (ex, ex.run(ticks).launches)
+    monkeypatch.delenv("SIXDOF_PAIR_SMALL", raising=False)
+    assert [runs[r][1] for r in ("multi", "small_k1", "small_k4")] == [1 + ticks, ticks, 2]      # no hub launches: every degree < 32
+    multi = runs["multi"][0]
+    for f in parity.FIELDS + ("inertia",):
+        for other in ("small_k1", "small_k4"):
+            assert np.array_equal(getattr(multi, f), getattr(runs[other][0], f)), (f, other)
+    ref = orc.OracleWorld(pos, vel, inertia, simulation_time_step=3600.0, integrator=integrator, ops=ops, edges=edge_rows)
+    ref.step(ticks)
+    errs = parity.state_errors(multi, ref)
+    print(f"130 rows, {len(edges[0])} edges, {kind}, integrator {integrator}: vs oracle {errs}")
+    assert max(errs.values()) < parity.F64_RTOL, errs
+    leaves = np.flatnonzero(deg == 0)
+    assert {3, 73, 129} <= set(leaves.tolist())
+    assert np.allclose(multi.force[leaves, 3:], np.outer(inertia[leaves, 6], g), rtol=1e-12, atol=0.0)
+
+
+def test_hub_and_lane_folded_sources_in_the_same_waves_match_the_oracle(monkeypatch):
+    """The same 130 rows with two hub sources (129 out-edges: one chunk; 33: just over the threshold) among the lane-folded ones, on
+    the multi-kernel path: the fused launch takes the hubs' sums from their partial rows.  A hub's sum is associated differently
+    from the sequential fold, so this is compared with the oracle only."""
+    ticks = 7
+    (pos, vel, inertia), eff, ops, edges, edge_rows, deg, g = _two_waves_and_a_tail("newton", hubs=True)
+    monkeypatch.setenv("SIXDOF_PAIR_SMALL", "0")
+    hip = ea.HipExec(pos, vel, inertia, simulation_time_step=3600.0, integrator=L.RK4, effectors=eff, edges=edges)
+    launches = hip.run(ticks).launches
+    monkeypatch.delenv("SIXDOF_PAIR_SMALL", raising=False)
+    ref = orc.OracleWorld(pos, vel, inertia, simulation_time_step=3600.0, integrator=L.RK4, ops=ops, edges=edge_rows)
+    ref.step(ticks)
+    errs = parity.state_errors(hip, ref)
+    print(f"130 rows, {len(edges[0])} edges, hubs of 129 and 33: vs oracle {errs}")
+    assert max(errs.values()) < parity.F64_RTOL, errs
+    assert launches == 1 + 3 * ticks                       # pack, then per tick: hub chunks, hub reduce, fold-and-integrate
 
 
 @pytest.mark.parametrize("small", [True, False])
