@@ -15,7 +15,7 @@ import os
 import subprocess
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Optional, Dict, List, Sequence, Tuple
+from typing import Callable, Optional, Dict, List, NamedTuple, Sequence, Tuple
 
 from . import dsl
 
@@ -1155,137 +1155,6 @@ def _graph_fold_kinds(outputs, w: int):
     return kinds
 
 
-def _emit_fold_stage(u: _Unit, fs: "dsl.TracedFoldStage") -> str:
-    """A stand-alone fold inside a program (dsl.TracedFoldStage): one lane per SOURCE folds its out-edges in spawn order into
-    the scratch column, a second kernel commits scratch -> out on source rows (every fold reads the values from before it
-    ran).  Components come from the program's columns (P.model_cols) or the Body columns; the CSR is baked in."""
-    j = fs.index
-    f = fs.traced.fold
-    w = fs.out[2]
-    body_ptr = {"world_pos": "P.pos", "world_vel": "P.vel", "inertia": "P.inertia"}
-    ptr = lambda name, slot: f"static_cast<const T*>({body_ptr[name]})" if slot is None else f"static_cast<const T*>(P.model_cols[{slot}])"
-    leaves = {f"acc_{k}": f"acc[{k}]" for k in range(w)}
-    complete = int(getattr(fs, "complete", 0) or 0)
-    # the target row of edge e: from the baked CSR, or — a complete graph — slot s of source i is row s + (s >= i)
-    dst_of = (lambda e_: f"({e_} + (({e_}) >= i ? 1u : 0u))") if complete else (lambda e_: f"fold{j}_dst[{e_}]")
-    e_lo, e_hi = ("0u", f"{complete - 1}u") if complete else (f"fold{j}_start[i]", f"fold{j}_start[i + 1]")
-    loads_a, loads_b = [], []
-    for i, (n, slot, wn) in enumerate(fs.left):
-        for k in range(wn):
-            leaves[f"a{i}_{k}"] = f"a{i}[{k}]"
-        loads_a.append(f"    const T* a{i} = {ptr(n, slot)} + (size_t)row * {wn};")
-    for i, (n, slot, wn) in enumerate(fs.right):
-        for k in range(wn):
-            leaves[f"b{i}_{k}"] = f"b{i}[{k}]"
-        loads_b.append(f"        const T* b{i} = {ptr(n, slot)} + (size_t)(base + {dst_of('e')}) * {wn};")
-    body = "\n".join(emit_block(u, [(f"acc[{k}]", e) for k, e in enumerate(fs.traced.outputs)], leaves, indent="        "))
-    init = ", ".join(f"T({v!r})" for v in f.init)
-    nl = "\n"
-    # One lane per source folds its out-edges in order: a chain of dependent gathers, ~350 ns a trip with nothing to hide it behind
-    # (a 256-body complete graph: 255 trips, 4 folds per tick = 353 us: profiles/r06_fold_world_time_plain_loop.json).  So the targets'
-    # rows are fetched FOLD_BATCH edges at a time — all their loads in flight together — and folded in order afterwards: the same
-    # operations in the same order.  Asked for by the fold (dsl.GraphFold.gather_batch: the scans stablehlo.world_program lifts out of a
-    # whole-world tick set it; folds written by hand keep the plain loop and their generated text), narrow right-hand sides only
-    # (the row buffers are registers).
-    batched = ""
-    B = int(getattr(f, "gather_batch", 1) or 1)
-    if B > 1 and sum(wn for _, _, wn in fs.right) <= 16:
-        decl = "".join(f"        T rb{i}[{B}][{wn}];\n" for i, (_, _, wn) in enumerate(fs.right))
-        fetch = "".join(f"            {{ const T* g = {ptr(n, slot)} + (size_t)(base + {dst_of('e + u')}) * {wn};\n"
-                        f"#pragma unroll\n              for (int k = 0; k < {wn}; k++) rb{i}[u][k] = g[k]; }}\n" for i, (n, slot, wn) in enumerate(fs.right))
-        use = "".join(f"            const T* b{i} = rb{i}[u];\n" for i in range(len(fs.right)))
-        inner = "\n".join("    " + ln for ln in body.split("\n"))
-        batched = (f"    for (; e + {B} <= {e_hi}; e += {B}) {{\n{decl}#pragma unroll\n        for (int u = 0; u < {B}; u++) {{\n{fetch}        }}\n"
-                   f"#pragma unroll\n        for (int u = 0; u < {B}; u++) {{\n{use}{inner}\n        }}\n    }}\n")
-    n_src = len(fs.src_rows)
-    count, stride = fs.replicas if fs.replicas else (1, 0)
-    arr = lambda xs: ", ".join(str(int(x)) for x in xs) if xs else "0"
-    tables = (f"// (the complete graph over the {complete} rows of a world: no tables — slot s of source i is row s + (s >= i))" if complete else
-              f"__device__ const uint32_t fold{j}_src[{max(n_src, 1)}] = {{{arr(fs.src_rows)}}};\n"
-              f"__device__ const uint32_t fold{j}_start[{n_src + 1}] = {{{arr(fs.row_start)}}};\n"
-              f"__device__ const uint32_t fold{j}_dst[{max(len(fs.dst), 1)}] = {{{arr(fs.dst)}}};")
-    src_of = (lambda i_: i_) if complete else (lambda i_: f"fold{j}_src[{i_}]")
-    n_edges = complete * (complete - 1) if complete else len(fs.dst)
-    # a fold whose output column is none of the columns it reads (dsl.GraphFold.direct_out: the scans of stablehlo.world_program) needs
-    # no scratch-then-commit: no lane can read what another has already replaced
-    direct = bool(getattr(f, "direct_out", False)) and fs.out[0] not in [n for n, _, _ in fs.left + fs.right]
-    out_slot = fs.out[1] if direct else fs.scratch_slot
-    kinds = _graph_fold_kinds(fs.traced.outputs, w) if getattr(f, "wave_fold", False) else None
-    if kinds is not None:
-        # A WAVE per source (dsl.GraphFold.wave_fold: the long scans stablehlo.world_program lifts out of a whole-world tick ask for
-        # it).  One lane per source walks its N - 1 out-edges alone — 2,047 dependent trips at 2,048 bodies, 1.4 ms per tick — although the
-        # fold is a plain sum: every component is acc_k +- g_k(source, target), acc_k itself, or the constant 0.  So lane l folds edges
-        # l, l + 64, ... from zero in slot order, the 64 partial sums are added by a fixed shuffle tree and the initial value joins at
-        # the end: the same sum in another association (~1e-16 x sqrt(degree) relative, identical from run to run) — the trade the
-        # hub kernels of csrc/pair_kernel.hpp make.  world_program(..., wave_folds=False) keeps the sequential, bit-for-bit fold.
-        zero = ", ".join("T(0)" for _ in range(w))
-        fin = "\n".join({"sum": f"        if (lane == 0) sc[{k}] = T({f.init[k]!r}) + v{k};", "keep": f"        if (lane == 0) sc[{k}] = T({f.init[k]!r});",
-                         "zero": f"        if (lane == 0) sc[{k}] = ({e_hi} > {e_lo}) ? T(0) : T({f.init[k]!r});"}[kd] for k, kd in enumerate(kinds))
-        red = "\n".join(f"        T v{k} = acc[{k}];\n#pragma unroll\n        for (int off = 32; off >= 1; off >>= 1) v{k} += __shfl_down(v{k}, off, 64);"
-                        for k, kd in enumerate(kinds) if kd == "sum")
-        return f'''// ---- fold stage {j}: {fs.name} ({n_edges} edges, {n_src} sources{f", x {count} replicas of {stride} rows" if fs.replicas else ""}), one WAVE per source ----
-{tables}
-template <class T>
-__global__ __launch_bounds__(64) void fold{j}_kernel(const StepParams P) {{
-    const uint32_t gi = blockIdx.x, lane = threadIdx.x;
-    if (gi >= {n_src * count}u) return;
-    const uint32_t i = gi % {max(n_src, 1)}u, base = (gi / {max(n_src, 1)}u) * {stride}u;   // source within the template, replica's first row
-    const uint32_t row = base + {src_of("i")};
-    if (row >= P.n) return;
-{nl.join(loads_a)}
-    T acc[{w}] = {{{zero}}};
-    for (uint32_t e = {e_lo} + lane; e < {e_hi}; e += 64u) {{
-{nl.join(loads_b)}
-{body}
-    }}
-    T* sc = static_cast<T*>(P.model_cols[{out_slot}]) + (size_t)row * {w};
-    {{
-{red}
-{fin}
-    }}
-}}
-template <class T>
-__global__ __launch_bounds__(64) void fold{j}_commit(const StepParams P) {{
-    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gi >= {n_src * count}u) return;
-    const uint32_t row = (gi / {max(n_src, 1)}u) * {stride}u + {f"(gi % {max(n_src, 1)}u)" if complete else f"fold{j}_src[gi % {max(n_src, 1)}u]"};
-    if (row >= P.n) return;
-    const T* sc = static_cast<const T*>(P.model_cols[{fs.scratch_slot}]) + (size_t)row * {w};
-    T* o = static_cast<T*>(P.model_cols[{fs.out[1]}]) + (size_t)row * {w};
-    for (int k = 0; k < {w}; k++) o[k] = sc[k];
-}}
-'''
-    return f'''// ---- fold stage {j}: {fs.name} ({n_edges} edges, {n_src} sources{f", x {count} replicas of {stride} rows" if fs.replicas else ""}) ----
-{tables}
-template <class T>
-__global__ __launch_bounds__(64) void fold{j}_kernel(const StepParams P) {{
-    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gi >= {n_src * count}u) return;
-    const uint32_t i = gi % {max(n_src, 1)}u, base = (gi / {max(n_src, 1)}u) * {stride}u;   // source within the template, replica's first row
-    const uint32_t row = base + {src_of("i")};
-    if (row >= P.n) return;
-{nl.join(loads_a)}
-    T acc[{w}] = {{{init}}};
-{("    uint32_t e = " + e_lo + ";" + nl + batched + "    for (; e < " + e_hi + "; e++) {") if batched else ("    for (uint32_t e = " + e_lo + "; e < " + e_hi + "; e++) {")}
-{nl.join(loads_b)}
-{body}
-    }}
-    T* sc = static_cast<T*>(P.model_cols[{out_slot}]) + (size_t)row * {w};
-    for (int k = 0; k < {w}; k++) sc[k] = acc[k];
-}}
-template <class T>
-__global__ __launch_bounds__(64) void fold{j}_commit(const StepParams P) {{
-    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gi >= {n_src * count}u) return;
-    const uint32_t row = (gi / {max(n_src, 1)}u) * {stride}u + {f"(gi % {max(n_src, 1)}u)" if complete else f"fold{j}_src[gi % {max(n_src, 1)}u]"};
-    if (row >= P.n) return;
-    const T* sc = static_cast<const T*>(P.model_cols[{fs.scratch_slot}]) + (size_t)row * {w};
-    T* o = static_cast<T*>(P.model_cols[{fs.out[1]}]) + (size_t)row * {w};
-    for (int k = 0; k < {w}; k++) o[k] = sc[k];
-}}
-'''
-
-
 # What a device-table fold kernel gets next to StepParams (csrc/sixdof_capi.cpp holds the same struct and checks its size through
 # sixdof_custom_fold_info).  The sources are PARTITIONED: [0, n_lane) are folded by one lane each, [n_lane, n_src) by one wave
 # each (out-degree >= 64 of a fold that may be regrouped) — the two lists of a fold are two ranges of one CSR.
@@ -1301,71 +1170,169 @@ struct FoldTable {
 """
 
 
-def _fold_wave_ok(fs: "dsl.TracedFoldStage") -> bool:
-    """The fold asked for waves (dsl.GraphFold.wave_fold) and is a plain sum, so partial folds may be regrouped."""
-    return bool(getattr(fs.traced.fold, "wave_fold", False)) and _graph_fold_kinds(fs.traced.outputs, fs.out[2]) is not None
+def _fold_front(u: _Unit, outputs, w: int, left, right, T: str = "T"):
+    """The per-edge front half every fold kernel shares — the fold stages of a program, whatever their edge source, and the
+    stand-alone fold.  left / right: [(pointer expression, width)] of the source-side and the target-side operands, T the element
+    type as the pointers spell it.  -> (leaf table, the source-side operand lines, target-row expression -> the target-side
+    operand lines, the per-edge body): the body is ONE text, so every kernel that holds it performs the same operations in the
+    same order."""
+    leaves = {f"acc_{k}": f"acc[{k}]" for k in range(w)}
+    for side, operands in (("a", left), ("b", right)):
+        for i, (_, wn) in enumerate(operands):
+            leaves.update({f"{side}{i}_{k}": f"{side}{i}[{k}]" for k in range(wn)})
+    loads_a = [f"    const {T}* a{i} = {p} + (size_t)row * {wn};" for i, (p, wn) in enumerate(left)]
+    loads_b = lambda row: [f"        const {T}* b{i} = {p} + (size_t){row} * {wn};" for i, (p, wn) in enumerate(right)]
+    body = "\n".join(emit_block(u, [(f"acc[{k}]", e) for k, e in enumerate(outputs)], leaves, indent="        "))
+    return leaves, loads_a, loads_b, body
 
 
-def _emit_fold_stage_device(u: _Unit, fs: "dsl.TracedFoldStage") -> str:
-    """_emit_fold_stage with the CSR read from device memory (FoldTable): the same arithmetic in the same order — one lane per
-    source walks row_start[i] .. row_start[i + 1] in spawn order, gather_batch and direct_out as in the baked flavour.  Nothing
-    about the graph is in the text.  A fold that may be regrouped (_fold_wave_ok) gets a second kernel, one WAVE per source, for
-    the sources the host put behind n_lane (out-degree >= 64): the baked wave kernel's partition and shuffle tree.  Every index
-    is a plain load; the host has checked every target row (sixdof_set_fold_edges), the kernels guard i and the source row."""
-    j = fs.index
+class _FoldPlan(NamedTuple):
+    """What is decided about a fold stage, once (_fold_plan): the emitter, the launch lines and the table exports all read this."""
+    kinds: Optional[List[str]]      # per component "sum" / "keep" / "zero" when a wave may regroup the fold (_graph_fold_kinds), else None
+    direct: bool                    # the kernels write the output column themselves: no commit launch
+    batch: int                      # target rows fetched per round trip of the lane kernel (1: the plain loop)
+    count: int                      # replicas of the edge template ...
+    stride: int                     # ... and the rows between two of them (1, 0: none)
+
+
+def _fold_plan(fs: "dsl.TracedFoldStage") -> _FoldPlan:
     f = fs.traced.fold
-    w = fs.out[2]
+    # waves: the fold asked for them (dsl.GraphFold.wave_fold) and is a plain sum, so partial folds may be regrouped
+    kinds = _graph_fold_kinds(fs.traced.outputs, fs.out[2]) if f.wave_fold else None
+    # gather_batch: narrow right-hand sides only (the row buffers are registers)
+    batch = int(f.gather_batch or 1) if sum(wn for _, _, wn in fs.right) <= 16 else 1
+    count, stride = fs.replicas if fs.replicas else (1, 0)
+    # a fold whose output column is none of the columns it reads (dsl.GraphFold.direct_out: the scans of stablehlo.world_program) needs
+    # no scratch-then-commit: no lane can read what another has already replaced (dsl.TracedFoldStage.direct)
+    return _FoldPlan(kinds, fs.direct, max(batch, 1), count, stride)
+
+
+class _EdgeSource(NamedTuple):
+    """Where the kernels of a fold stage find their edges — only what differs between a baked CSR, the arithmetic complete graph
+    and a FoldTable in device memory (dsl.TracedFoldStage.edge_source)."""
+    header: str                 # the stage's header comment, after the fold's name
+    tables: str                 # the table declarations, or the comment that stands in for them
+    param: str                  # the kernels' parameter next to StepParams
+    partitioned: bool           # the sources come as a lane range and a wave range (grids read from the table at launch), not one list
+    sources: Callable           # "lane" | "wave" | "all" -> (guard lines, source index of gi, replica of gi) over that range of sources
+    src_row: Callable           # source index expression -> its row in replica 0
+    bounds: str                 # the line that names e_lo / e_hi, if one does
+    e_lo: str
+    e_hi: str
+    dst: Callable               # edge index expression -> its target row in replica 0
+    batch_cond: Callable        # B -> "B more edges are left" as the batch loop asks it
+
+
+def _edge_source(fs: "dsl.TracedFoldStage", plan: _FoldPlan) -> _EdgeSource:
+    j, n_src, count = fs.index, len(fs.src_rows), plan.count
+    if fs.edge_source == "device":
+        # Nothing about the graph is in the text.  Every index is a plain load; the host has checked every target row
+        # (sixdof_set_fold_edges), the kernels guard i and the source row.  Edge counts go up to 2^32 - 1, so the batch loop asks
+        # for the edges left rather than forming e + B, which could wrap (the two spellings compile to different lane kernels:
+        # profiles/fold_emitters_refactor.md — so each source keeps its own).
+        def sources(which):
+            n = {"lane": "F.n_lane", "wave": "n_wave", "all": "F.n_src"}[which]
+            return (("    const uint32_t n_wave = F.n_src - F.n_lane;\n" if which == "wave" else "") + f"    if ({n} == 0u || gi / {n} >= {count}u) return;",
+                    ("F.n_lane + " if which == "wave" else "") + f"gi % {n}", f"(gi / {n})")
+        return _EdgeSource(header=f", edges in device memory{f' (x {count} replicas of {plan.stride} rows)' if fs.replicas else ''}",
+                           tables="", param=", const FoldTable F", partitioned=True, sources=sources, src_row=lambda i_: f"F.src_rows[{i_}]",
+                           bounds="    const uint32_t e_lo = F.row_start[i], e_hi = F.row_start[i + 1];\n", e_lo="e_lo", e_hi="e_hi",
+                           dst=lambda e_: f"F.dst[{e_}]", batch_cond=lambda B: f"e_hi - e >= {B}u")
+    complete = fs.complete
+    n_edges = complete * (complete - 1) if complete else len(fs.dst)
+    header = f" ({n_edges} edges, {n_src} sources{f', x {count} replicas of {plan.stride} rows' if fs.replicas else ''})"
+    one_list = lambda which: (f"    if (gi >= {n_src * count}u) return;", f"gi % {max(n_src, 1)}u", f"(gi / {max(n_src, 1)}u)")
+    # (e + B cannot wrap here: a baked CSR holds at most 65,536 edges, a complete graph's slots end at its row count)
+    if complete:
+        # a complete graph never reads a table, even under fold_tables="device": slot s of source i is row s + (s >= i)
+        return _EdgeSource(header=header, tables=f"// (the complete graph over the {complete} rows of a world: no tables — slot s of source i is row s + (s >= i))\n",
+                           param="", partitioned=False, sources=one_list, src_row=lambda i_: i_ if i_ == "i" else f"({i_})", bounds="",
+                           e_lo="0u", e_hi=f"{complete - 1}u", dst=lambda e_: f"({e_} + (({e_}) >= i ? 1u : 0u))",
+                           batch_cond=lambda B: f"e + {B} <= {complete - 1}u")
+    arr = lambda xs: ", ".join(str(int(x)) for x in xs) if xs else "0"
+    return _EdgeSource(header=header, tables=(f"__device__ const uint32_t fold{j}_src[{max(n_src, 1)}] = {{{arr(fs.src_rows)}}};\n"
+                                              f"__device__ const uint32_t fold{j}_start[{n_src + 1}] = {{{arr(fs.row_start)}}};\n"
+                                              f"__device__ const uint32_t fold{j}_dst[{max(len(fs.dst), 1)}] = {{{arr(fs.dst)}}};\n"),
+                       param="", partitioned=False, sources=one_list, src_row=lambda i_: f"fold{j}_src[{i_}]", bounds="",
+                       e_lo=f"fold{j}_start[i]", e_hi=f"fold{j}_start[i + 1]", dst=lambda e_: f"fold{j}_dst[{e_}]",
+                       batch_cond=lambda B: f"e + {B} <= fold{j}_start[i + 1]")
+
+
+def _emit_fold_stage(u: _Unit, fs: "dsl.TracedFoldStage", plan: _FoldPlan) -> str:
+    """A stand-alone fold inside a program (dsl.TracedFoldStage): one lane per SOURCE folds its out-edges in spawn order into
+    the scratch column, a second kernel commits scratch -> out on source rows (every fold reads the values from before it
+    ran).  Components come from the program's columns (P.model_cols) or the Body columns.  One lane kernel, one wave kernel and
+    one commit kernel serve the three edge sources (_edge_source): the same arithmetic in the same order wherever the edges sit.
+    A fold that may be regrouped (plan.kinds) is folded by one WAVE per source — every source of a baked fold (the wave kernel is
+    its only fold kernel), the sources the host put behind n_lane (out-degree >= 64) of a fold with device tables, which keeps
+    the lane kernel for the rest: the same partition and shuffle tree either way."""
+    j, f, w = fs.index, fs.traced.fold, fs.out[2]
+    es = _edge_source(fs, plan)
     body_ptr = {"world_pos": "P.pos", "world_vel": "P.vel", "inertia": "P.inertia"}
     ptr = lambda name, slot: f"static_cast<const T*>({body_ptr[name]})" if slot is None else f"static_cast<const T*>(P.model_cols[{slot}])"
-    leaves = {f"acc_{k}": f"acc[{k}]" for k in range(w)}
-    dst_of = lambda e_: f"F.dst[{e_}]"
-    loads_a, loads_b = [], []
-    for i, (n, slot, wn) in enumerate(fs.left):
-        for k in range(wn):
-            leaves[f"a{i}_{k}"] = f"a{i}[{k}]"
-        loads_a.append(f"    const T* a{i} = {ptr(n, slot)} + (size_t)row * {wn};")
-    for i, (n, slot, wn) in enumerate(fs.right):
-        for k in range(wn):
-            leaves[f"b{i}_{k}"] = f"b{i}[{k}]"
-        loads_b.append(f"        const T* b{i} = {ptr(n, slot)} + (size_t)(base + {dst_of('e')}) * {wn};")
-    body = "\n".join(emit_block(u, [(f"acc[{k}]", e) for k, e in enumerate(fs.traced.outputs)], leaves, indent="        "))
-    init = ", ".join(f"T({v!r})" for v in f.init)
+    right = [(ptr(n, slot), wn) for n, slot, wn in fs.right]
+    _, loads_a, loads_b, body = _fold_front(u, fs.traced.outputs, w, [(ptr(n, slot), wn) for n, slot, wn in fs.left], right)
     nl = "\n"
-    batched = ""
-    B = int(getattr(f, "gather_batch", 1) or 1)
-    if B > 1 and sum(wn for _, _, wn in fs.right) <= 16:
-        decl = "".join(f"        T rb{i}[{B}][{wn}];\n" for i, (_, _, wn) in enumerate(fs.right))
-        fetch = "".join(f"            {{ const T* g = {ptr(n, slot)} + (size_t)(base + {dst_of('e + u')}) * {wn};\n"
-                        f"#pragma unroll\n              for (int k = 0; k < {wn}; k++) rb{i}[u][k] = g[k]; }}\n" for i, (n, slot, wn) in enumerate(fs.right))
-        use = "".join(f"            const T* b{i} = rb{i}[u];\n" for i in range(len(fs.right)))
-        inner = "\n".join("    " + ln for ln in body.split("\n"))
-        batched = (f"    for (; e_hi - e >= {B}u; e += {B}) {{\n{decl}#pragma unroll\n        for (int u = 0; u < {B}; u++) {{\n{fetch}        }}\n"
-                   f"#pragma unroll\n        for (int u = 0; u < {B}; u++) {{\n{use}{inner}\n        }}\n    }}\n")
-    count, stride = fs.replicas if fs.replicas else (1, 0)
-    direct = bool(getattr(f, "direct_out", False)) and fs.out[0] not in [n for n, _, _ in fs.left + fs.right]
-    out_slot = fs.out[1] if direct else fs.scratch_slot
-    wave = ""
-    if _fold_wave_ok(fs):
-        kinds = _graph_fold_kinds(fs.traced.outputs, w)
+    target = lambda e_: f"(base + {es.dst(e_)})"
+    out_slot = fs.out[1] if plan.direct else fs.scratch_slot
+
+    def head(which):      # from the guard to the source-side operands, for the lane or wave that serves source gi of that range
+        guard, i_, replica = es.sources(which)
+        return (f"{guard}\n    const uint32_t i = {i_}, base = {replica} * {plan.stride}u;   // source within the template, replica's first row\n"
+                f"    const uint32_t row = base + {es.src_row('i')};\n    if (row >= P.n) return;\n{es.bounds}{nl.join(loads_a)}")
+
+    def lane_kernel():
+        # One lane per source folds its out-edges in order: a chain of dependent gathers, ~350 ns a trip with nothing to hide it behind
+        # (a 256-body complete graph: 255 trips, 4 folds per tick = 353 us: profiles/r06_fold_world_time_plain_loop.json).  So the targets'
+        # rows are fetched plan.batch edges at a time — all their loads in flight together — and folded in order afterwards: the same
+        # operations in the same order.  Asked for by the fold (dsl.GraphFold.gather_batch: the scans stablehlo.world_program lifts out of a
+        # whole-world tick set it; folds written by hand keep the plain loop and their generated text).
+        B = plan.batch
+        loop = f"    for (uint32_t e = {es.e_lo}; e < {es.e_hi}; e++) {{"
+        if B > 1:
+            decl = "".join(f"        T rb{i}[{B}][{wn}];\n" for i, (_, wn) in enumerate(right))
+            fetch = "".join(f"            {{ const T* g = {p} + (size_t){target('e + u')} * {wn};\n"
+                            f"#pragma unroll\n              for (int k = 0; k < {wn}; k++) rb{i}[u][k] = g[k]; }}\n" for i, (p, wn) in enumerate(right))
+            use = "".join(f"            const T* b{i} = rb{i}[u];\n" for i in range(len(right)))
+            inner = "\n".join("    " + ln for ln in body.split("\n"))
+            loop = (f"    uint32_t e = {es.e_lo};\n"
+                    f"    for (; {es.batch_cond(B)}; e += {B}) {{\n{decl}#pragma unroll\n        for (int u = 0; u < {B}; u++) {{\n{fetch}        }}\n"
+                    f"#pragma unroll\n        for (int u = 0; u < {B}; u++) {{\n{use}{inner}\n        }}\n    }}\n"
+                    f"    for (; e < {es.e_hi}; e++) {{")
+        init = ", ".join(f"T({v!r})" for v in f.init)
+        return f'''template <class T>
+__global__ __launch_bounds__(64) void fold{j}_kernel(const StepParams P{es.param}) {{
+    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
+{head("lane")}
+    T acc[{w}] = {{{init}}};
+{loop}
+{nl.join(loads_b(target("e")))}
+{body}
+    }}
+    T* sc = static_cast<T*>(P.model_cols[{out_slot}]) + (size_t)row * {w};
+    for (int k = 0; k < {w}; k++) sc[k] = acc[k];
+}}
+'''
+
+    def wave_kernel(name, which):
+        # A WAVE per source (dsl.GraphFold.wave_fold: the long scans stablehlo.world_program lifts out of a whole-world tick ask for
+        # it).  One lane per source walks its N - 1 out-edges alone — 2,047 dependent trips at 2,048 bodies, 1.4 ms per tick — although the
+        # fold is a plain sum: every component is acc_k +- g_k(source, target), acc_k itself, or the constant 0.  So lane l folds edges
+        # l, l + 64, ... from zero in slot order, the 64 partial sums are added by a fixed shuffle tree and the initial value joins at
+        # the end: the same sum in another association (~1e-16 x sqrt(degree) relative, identical from run to run) — the trade the
+        # hub kernels of csrc/pair_kernel.hpp make.  world_program(..., wave_folds=False) keeps the sequential, bit-for-bit fold.
         zero = ", ".join("T(0)" for _ in range(w))
         fin = "\n".join({"sum": f"        if (lane == 0) sc[{k}] = T({f.init[k]!r}) + v{k};", "keep": f"        if (lane == 0) sc[{k}] = T({f.init[k]!r});",
-                         "zero": f"        if (lane == 0) sc[{k}] = (e_hi > e_lo) ? T(0) : T({f.init[k]!r});"}[kd] for k, kd in enumerate(kinds))
+                         "zero": f"        if (lane == 0) sc[{k}] = ({es.e_hi} > {es.e_lo}) ? T(0) : T({f.init[k]!r});"}[kd] for k, kd in enumerate(plan.kinds))
         red = "\n".join(f"        T v{k} = acc[{k}];\n#pragma unroll\n        for (int off = 32; off >= 1; off >>= 1) v{k} += __shfl_down(v{k}, off, 64);"
-                        for k, kd in enumerate(kinds) if kd == "sum")
-        wave = f'''// one WAVE per source of the wave range: lane l folds edges l, l + 64, ... from zero, a fixed shuffle tree adds the partials, init joins last
-template <class T>
-__global__ __launch_bounds__(64) void fold{j}_wave(const StepParams P, const FoldTable F) {{
+                        for k, kd in enumerate(plan.kinds) if kd == "sum")
+        return f'''template <class T>
+__global__ __launch_bounds__(64) void {name}(const StepParams P{es.param}) {{
     const uint32_t gi = blockIdx.x, lane = threadIdx.x;
-    const uint32_t n_wave = F.n_src - F.n_lane;
-    if (n_wave == 0u || gi / n_wave >= {count}u) return;
-    const uint32_t i = F.n_lane + gi % n_wave, base = (gi / n_wave) * {stride}u;   // source within the template, replica's first row
-    const uint32_t row = base + F.src_rows[i];
-    if (row >= P.n) return;
-    const uint32_t e_lo = F.row_start[i], e_hi = F.row_start[i + 1];
-{nl.join(loads_a)}
+{head(which)}
     T acc[{w}] = {{{zero}}};
-    for (uint32_t e = e_lo + lane; e < e_hi; e += 64u) {{
-{nl.join(loads_b)}
+    for (uint32_t e = {es.e_lo} + lane; e < {es.e_hi}; e += 64u) {{
+{nl.join(loads_b(target("e")))}
 {body}
     }}
     T* sc = static_cast<T*>(P.model_cols[{out_slot}]) + (size_t)row * {w};
@@ -1375,35 +1342,47 @@ __global__ __launch_bounds__(64) void fold{j}_wave(const StepParams P, const Fol
     }}
 }}
 '''
-    return f'''// ---- fold stage {j}: {fs.name}, edges in device memory{f" (x {count} replicas of {stride} rows)" if fs.replicas else ""} ----
-template <class T>
-__global__ __launch_bounds__(64) void fold{j}_kernel(const StepParams P, const FoldTable F) {{
+
+    guard, i_, replica = es.sources("all")
+    commit = f'''template <class T>
+__global__ __launch_bounds__(64) void fold{j}_commit(const StepParams P{es.param}) {{
     const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (F.n_lane == 0u || gi / F.n_lane >= {count}u) return;
-    const uint32_t i = gi % F.n_lane, base = (gi / F.n_lane) * {stride}u;   // source within the template, replica's first row
-    const uint32_t row = base + F.src_rows[i];
-    if (row >= P.n) return;
-    const uint32_t e_lo = F.row_start[i], e_hi = F.row_start[i + 1];
-{nl.join(loads_a)}
-    T acc[{w}] = {{{init}}};
-{("    uint32_t e = e_lo;" + nl + batched + "    for (; e < e_hi; e++) {") if batched else "    for (uint32_t e = e_lo; e < e_hi; e++) {"}
-{nl.join(loads_b)}
-{body}
-    }}
-    T* sc = static_cast<T*>(P.model_cols[{out_slot}]) + (size_t)row * {w};
-    for (int k = 0; k < {w}; k++) sc[k] = acc[k];
-}}
-{wave}template <class T>
-__global__ __launch_bounds__(64) void fold{j}_commit(const StepParams P, const FoldTable F) {{
-    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (F.n_src == 0u || gi / F.n_src >= {count}u) return;
-    const uint32_t row = (gi / F.n_src) * {stride}u + F.src_rows[gi % F.n_src];
+{guard}
+    const uint32_t row = {replica} * {plan.stride}u + {es.src_row(i_)};
     if (row >= P.n) return;
     const T* sc = static_cast<const T*>(P.model_cols[{fs.scratch_slot}]) + (size_t)row * {w};
     T* o = static_cast<T*>(P.model_cols[{fs.out[1]}]) + (size_t)row * {w};
     for (int k = 0; k < {w}; k++) o[k] = sc[k];
 }}
 '''
+    if es.partitioned:
+        fold = lane_kernel() + ("" if plan.kinds is None else
+                                "// one WAVE per source of the wave range: lane l folds edges l, l + 64, ... from zero, a fixed shuffle tree adds the partials, init joins last\n"
+                                + wave_kernel(f"fold{j}_wave", "wave"))
+    else:
+        fold = lane_kernel() if plan.kinds is None else wave_kernel(f"fold{j}_kernel", "all")
+    wave_note = ", one WAVE per source" if plan.kinds is not None and not es.partitioned else ""
+    return f"// ---- fold stage {j}: {fs.name}{es.header}{wave_note} ----\n{es.tables}{fold}{commit}"      # (a direct fold still carries its commit: it is never launched)
+
+
+def _fold_launch(fs: "dsl.TracedFoldStage", plan: _FoldPlan, T: str) -> Optional[str]:
+    """The launch entry's lines for one fold stage: lane / wave / commit as _emit_fold_stage emitted them, no commit for a direct fold."""
+    j, cnt = fs.index, plan.count
+    if fs.edge_source == "device":
+        # grid sizes are data: the launch entry reads them from the table the library handed over
+        call = (f"        {{ const FoldTable& F = g_fold_table[{j}];\n"
+                f"          if (F.n_lane) hipLaunchKernelGGL(fold{j}_kernel<{T}>, dim3((F.n_lane * {cnt}u + 63u) / 64u), dim3(64), 0, s, q, F);\n")
+        if plan.kinds is not None:
+            call += f"          if (F.n_src > F.n_lane) hipLaunchKernelGGL(fold{j}_wave<{T}>, dim3((F.n_src - F.n_lane) * {cnt}u), dim3(64), 0, s, q, F);\n"
+        if not plan.direct:
+            call += f"          if (F.n_src) hipLaunchKernelGGL(fold{j}_commit<{T}>, dim3((F.n_src * {cnt}u + 63u) / 64u), dim3(64), 0, s, q, F);\n"
+        return call + "        }"
+    n = len(fs.src_rows) * cnt
+    nb = (n + 63) // 64
+    if not nb:
+        return None
+    return (f"        hipLaunchKernelGGL(fold{j}_kernel<{T}>, dim3({n if plan.kinds is not None else nb}), dim3(64), 0, s, q);" +      # one wave per source, or one lane
+            ("" if plan.direct else f"\n        hipLaunchKernelGGL(fold{j}_commit<{T}>, dim3({nb}), dim3(64), 0, s, q);"))
 
 
 # Integer components (el.PrimitiveType.I64: flags, counters, examples/stablehlo/sim.py:243-251) live in the executor's float
@@ -1452,13 +1431,13 @@ __device__ __forceinline__ double m_erfinv_fast(double u) {
 '''
 
 
-def _fold_table_exports(tp) -> Tuple[str, str]:
+def _fold_table_exports(tp, plans: Dict[int, _FoldPlan]) -> Tuple[str, str]:
     """The host side of a device-table object: where the library's tables land (sixdof_custom_set_fold_table), what it must know
     per fold to build and check one (sixdof_custom_fold_info), and the launch entry's refusal to run a fold without its table."""
     nf = len(tp.fold_stages)
-    dev = lambda fs_: bool(getattr(fs_, "device_tables", False))
-    info = ", ".join(f"{{{(1 if dev(fs_) else 0) | (2 if dev(fs_) and _fold_wave_ok(fs_) else 0)}u, "
-                     f"{fs_.replicas[0] if fs_.replicas else 1}u, {fs_.replicas[1] if fs_.replicas else 0}u}}" for fs_ in tp.fold_stages)
+    dev = lambda fs_: fs_.edge_source == "device"
+    info = ", ".join(f"{{{(1 if dev(fs_) else 0) | (2 if dev(fs_) and plans[fs_.index].kinds is not None else 0)}u, "
+                     f"{plans[fs_.index].count}u, {plans[fs_.index].stride}u}}" for fs_ in tp.fold_stages)
     text = f"""// ---- the fold stages' tables: handed over by the library (sixdof_set_fold_edges) before a launch, passed to the kernels by value ----
 static thread_local sixdof::FoldTable g_fold_table[{nf}];
 static thread_local bool g_fold_set[{nf}];
@@ -1601,33 +1580,16 @@ def _source(tp, dtype: str, integrator: int, fast_math: bool, u: _Unit) -> str:
                 cur.append(s_)
         if cur:
             chain.append(("seg", cur, [], False))
-        parts, calls = [], []
+        parts, calls, plans = [], [], {}      # plans: the one decision per fold stage (_fold_plan)
         last_seg = max(i for i, c in enumerate(chain) if c[0] == "seg")
         for i, c in enumerate(chain):
             if c[0] == "fold":
                 fs = c[1]
-                if getattr(fs, "device_tables", False):
-                    # grid sizes are data: the launch entry reads them from the table the library handed over
-                    parts.append(_emit_fold_stage_device(u, fs))
-                    cnt = fs.replicas[0] if fs.replicas else 1
-                    direct = bool(getattr(fs.traced.fold, "direct_out", False)) and fs.out[0] not in [n_ for n_, _, _ in fs.left + fs.right]
-                    jf = fs.index
-                    call = (f"        {{ const FoldTable& F = g_fold_table[{jf}];\n"
-                            f"          if (F.n_lane) hipLaunchKernelGGL(fold{jf}_kernel<{T}>, dim3((F.n_lane * {cnt}u + 63u) / 64u), dim3(64), 0, s, q, F);\n")
-                    if _fold_wave_ok(fs):
-                        call += f"          if (F.n_src > F.n_lane) hipLaunchKernelGGL(fold{jf}_wave<{T}>, dim3((F.n_src - F.n_lane) * {cnt}u), dim3(64), 0, s, q, F);\n"
-                    if not direct:
-                        call += f"          if (F.n_src) hipLaunchKernelGGL(fold{jf}_commit<{T}>, dim3((F.n_src * {cnt}u + 63u) / 64u), dim3(64), 0, s, q, F);\n"
-                    calls.append(call + "        }")
-                    continue
-                parts.append(_emit_fold_stage(u, fs))
-                nb = (len(fs.src_rows) * (fs.replicas[0] if fs.replicas else 1) + 63) // 64
-                waves = (getattr(fs.traced.fold, "wave_fold", False) and _graph_fold_kinds(fs.traced.outputs, fs.out[2]) is not None)
-                nk = len(fs.src_rows) * (fs.replicas[0] if fs.replicas else 1) if waves else nb      # one wave per source, or one lane
-                direct = bool(getattr(fs.traced.fold, "direct_out", False)) and fs.out[0] not in [n_ for n_, _, _ in fs.left + fs.right]
-                if nb:
-                    calls.append(f"        hipLaunchKernelGGL(fold{fs.index}_kernel<{T}>, dim3({nk}), dim3(64), 0, s, q);" +
-                                 ("" if direct else f"\n        hipLaunchKernelGGL(fold{fs.index}_commit<{T}>, dim3({nb}), dim3(64), 0, s, q);"))
+                plans[fs.index] = _fold_plan(fs)
+                parts.append(_emit_fold_stage(u, fs, plans[fs.index]))
+                call = _fold_launch(fs, plans[fs.index], T)
+                if call:
+                    calls.append(call)
                 continue
             _, pre, post, six = c
             used = _slots_of(pre + post, pipe_tp.outputs if six else ())
@@ -1642,7 +1604,7 @@ def _source(tp, dtype: str, integrator: int, fast_math: bool, u: _Unit) -> str:
         structs = "\n".join(parts)
         if getattr(tp, "fold_tables", "baked") == "device":
             structs = _FOLD_TABLE + structs
-            fold_exports, fold_guard = _fold_table_exports(tp)
+            fold_exports, fold_guard = _fold_table_exports(tp, plans)
         stage_comment = "// tick = " + " | ".join(("fold:" + c[1].name) if c[0] == "fold" else ("[" + " | ".join([s_.name for s_ in c[1]] + (["six_dof"] if c[3] and integrator != 2 else []) + [s_.name for s_ in c[2]]) + "]") for c in chain) + "\n"
         launch = ("    for (uint32_t t = 0; t < p->n_ticks; t++) {   // a fold needs every row of the link in front of it: one chain per tick\n"
                   "        StepParams q = *p;\n        q.n_ticks = 1;\n        q.tick0 = p->tick0 + t;\n        q.hist_slot0 = p->hist_slot0 + t;\n"
@@ -1787,18 +1749,9 @@ def generate_graph_fold_source(tf: "dsl.TracedGraphFold") -> str:
     fold sees the component values from before the system ran."""
     u = _Unit()      # every switch off: exact arithmetic in program order
     f = tf.fold
-    leaves = {f"acc_{k}": f"acc[{k}]" for k in range(tf.widths[f.out])}
-    loads_a, loads_b = [], []
-    for i, n in enumerate(f.left):
-        for k in range(tf.widths[n]):
-            leaves[f"a{i}_{k}"] = f"a{i}[{k}]"
-        loads_a.append(f"    const double* a{i} = P.left[{i}] + (size_t)row * {tf.widths[n]};")
-    for i, n in enumerate(f.right):
-        for k in range(tf.widths[n]):
-            leaves[f"b{i}_{k}"] = f"b{i}[{k}]"
-        loads_b.append(f"        const double* b{i} = P.right[{i}] + (size_t)P.dst[e] * {tf.widths[n]};")
     w = tf.widths[f.out]
-    body = "\n".join(emit_block(u, [(f"acc[{k}]", e) for k, e in enumerate(tf.outputs)], leaves, indent="        "))
+    _, loads_a, loads_b, body = _fold_front(u, tf.outputs, w, [(f"P.left[{i}]", tf.widths[n]) for i, n in enumerate(f.left)],
+                                            [(f"P.right[{i}]", tf.widths[n]) for i, n in enumerate(f.right)], T="double")
     init = ", ".join(repr(v) for v in f.init)
     nl = "\n"
     return f'''// generated by elodin_amd/codegen.py — do not edit.  stand-alone edge_fold system: {f.__name__}
@@ -1829,7 +1782,7 @@ __global__ __launch_bounds__(256) void graph_fold_kernel(const GraphFoldParams P
 {nl.join(loads_a)}
     double acc[{w}] = {{{init}}};
     for (uint32_t e = P.row_start[i]; e < P.row_start[i + 1]; e++) {{
-{nl.join(loads_b)}
+{nl.join(loads_b("P.dst[e]"))}
 {body}
     }}
     for (int k = 0; k < {w}; k++) P.scratch[(size_t)i * {w} + k] = acc[k];

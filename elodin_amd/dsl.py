@@ -1937,6 +1937,10 @@ class GraphFold:
         self.__name__ = getattr(fn, "__name__", "graph_fold")
         if len(inspect.signature(fn).parameters) != 1 + len(self.left) + len(self.right):
             raise TypeError("fold function must take (acc, *left components, *right components)")
+        # what a fold may ask of the program it is a stage of (set after construction; stablehlo.world_program does, for its scans):
+        self.gather_batch = 1       # target rows the lane kernel fetches per round trip (narrow right-hand sides only)
+        self.wave_fold = False      # a plain sum may be folded by a wave per source (see above)
+        self.direct_out = False     # write the output column without scratch-then-commit, when it is none of the columns read
 
     def trace(self, widths: Dict[str, int]) -> "TracedGraphFold":
         Expr.fresh()
@@ -2213,6 +2217,7 @@ class TracedFoldStage:
     def __init__(self, fold: GraphFold, table: ColumnTable, index: int, edges, partial: Sequence[str] = (),
                  replicas: Optional[Tuple[int, int]] = None, device_tables: bool = False):
         self.name, self.index = fold.__name__, index
+        self.complete = 0               # rows of the complete graph this fold runs over, when it does
         self.device_tables = False      # True: the kernels read this fold's CSR from device memory (a complete graph never has one)
         self.replicas = (int(replicas[0]), int(replicas[1])) if replicas else None
         names = list(dict.fromkeys(fold.left + fold.right + (fold.out,)))
@@ -2235,7 +2240,6 @@ class TracedFoldStage:
         self.scratch_slot = slot_of(self.scratch_name)
         if edges is None:
             raise ValueError(f"fold {self.name}: no edges given for edge component {fold.edge_component!r} (fold_edges)")
-        self.complete = 0
         if len(edges) == 2 and isinstance(edges[0], str) and edges[0] == "complete":
             # the COMPLETE graph over rows 0..n-1 of a world (every source folds every other row in ascending order — the spawn order
             # of examples/n-body/sim.py:330-338): nothing is baked, the kernel forms the target of slot s as s + (s >= source), so
@@ -2245,32 +2249,39 @@ class TracedFoldStage:
                 raise ValueError(f"fold {self.name}: a complete graph of {n_} rows does not fit a replica of {self.replicas[1]} rows")
             self.complete = n_
             self.src_rows = list(range(n_))
-            self._n_edges = n_ * (n_ - 1)
-            self.written = [f"c{self.out[1]}_{k}" for k in range(self.out[2])] + [f"c{self.scratch_slot}_{k}" for k in range(self.out[2])]
-            self.every, self.phase, self.also_at, self.reads_accel, self.writes_inertia = 1, 0, None, False, False
-            return
-        src = [int(x) for x in edges[0]]
-        dst = [int(x) for x in edges[1]]
-        if len(src) != len(dst):
-            raise ValueError("fold edges: from / to lengths differ")
-        if self.replicas and any(not 0 <= r < self.replicas[1] for r in src + dst):
-            raise ValueError(f"fold {self.name}: with fold_replicas the edges describe replica 0 (rows 0..{self.replicas[1] - 1})")
-        if device_tables:
-            # the CSR is data: sources ascending, each source's targets in the order given (a stable sort by source), kept as
-            # uint32 arrays for the executor and the walker — none of it enters the generated text
-            import numpy as _np
-            a_, b_ = _np.asarray(src, dtype=_np.int64), _np.asarray(dst, dtype=_np.int64)
-            if len(a_) > 0xFFFFFFFF or (len(a_) and (min(a_.min(), b_.min()) < 0 or max(a_.max(), b_.max()) > 0xFFFFFFFF)):
-                raise ValueError(f"fold {self.name}: edge rows and counts must fit 32 bits")
-            order = _np.argsort(a_, kind="stable")
-            rows_, counts_ = _np.unique(a_, return_counts=True)
-            self.device_tables = True
-            self.src_rows = rows_.astype(_np.uint32)
-            self.row_start = _np.concatenate([[0], _np.cumsum(counts_)]).astype(_np.uint32)
-            self.dst = b_[order].astype(_np.uint32)
-            self.written = [f"c{self.out[1]}_{k}" for k in range(self.out[2])] + [f"c{self.scratch_slot}_{k}" for k in range(self.out[2])]
-            self.every, self.phase, self.also_at, self.reads_accel, self.writes_inertia = 1, 0, None, False, False
-            return
+        else:
+            src = [int(x) for x in edges[0]]
+            dst = [int(x) for x in edges[1]]
+            if len(src) != len(dst):
+                raise ValueError("fold edges: from / to lengths differ")
+            if self.replicas and any(not 0 <= r < self.replicas[1] for r in src + dst):
+                raise ValueError(f"fold {self.name}: with fold_replicas the edges describe replica 0 (rows 0..{self.replicas[1] - 1})")
+            if device_tables:
+                self._device_csr(src, dst)
+            else:
+                self._baked_csr(src, dst)
+        # the two questions the generator asks, answered here once.  Where do my edges come from?
+        self.edge_source = "complete" if self.complete else "device" if self.device_tables else "baked"
+        # ... and may the kernels write the output column themselves?  The fold asked for it and reads none of what it writes
+        self.direct = bool(fold.direct_out) and fold.out not in fold.left + fold.right
+        self.written = [f"c{self.out[1]}_{k}" for k in range(self.out[2])] + [f"c{self.scratch_slot}_{k}" for k in range(self.out[2])]
+        self.every, self.phase, self.also_at, self.reads_accel, self.writes_inertia = 1, 0, None, False, False
+
+    def _device_csr(self, src, dst):
+        # the CSR is data: sources ascending, each source's targets in the order given (a stable sort by source), kept as
+        # uint32 arrays for the executor and the walker — none of it enters the generated text
+        import numpy as _np
+        a_, b_ = _np.asarray(src, dtype=_np.int64), _np.asarray(dst, dtype=_np.int64)
+        if len(a_) > 0xFFFFFFFF or (len(a_) and (min(a_.min(), b_.min()) < 0 or max(a_.max(), b_.max()) > 0xFFFFFFFF)):
+            raise ValueError(f"fold {self.name}: edge rows and counts must fit 32 bits")
+        order = _np.argsort(a_, kind="stable")
+        rows_, counts_ = _np.unique(a_, return_counts=True)
+        self.device_tables = True
+        self.src_rows = rows_.astype(_np.uint32)
+        self.row_start = _np.concatenate([[0], _np.cumsum(counts_)]).astype(_np.uint32)
+        self.dst = b_[order].astype(_np.uint32)
+
+    def _baked_csr(self, src, dst):
         if len(src) > 65536:
             raise ValueError(f"fold {self.name}: {len(src)} edges — folds inside a program bake their edges into the generated "
                              "code (<= 65,536); trace with fold_tables=\"device\" (HipExec / World.build: graph_tables) to keep the edges "
@@ -2283,9 +2294,6 @@ class TracedFoldStage:
         for r in self.src_rows:
             self.dst += by_src[r]
             self.row_start.append(len(self.dst))
-        self.written = [f"c{self.out[1]}_{k}" for k in range(self.out[2])] + [f"c{self.scratch_slot}_{k}" for k in range(self.out[2])]
-        self.every, self.phase, self.also_at, self.reads_accel, self.writes_inertia = 1, 0, None, False, False
-
 
     # a complete graph's CSR, made on demand (the numpy walker of the tests reads it; the generated kernel does not)
     def __getattr__(self, name):

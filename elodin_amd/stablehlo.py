@@ -2737,7 +2737,7 @@ def world_program(text: str, slots: Sequence, out_slots: Optional[Sequence] = No
             return fold_fn
         edge_c = f"hlo_fold{r.index}_edges"
         folds.append(_dsl.GraphFold(make_fn(), edge_c, (own_c,), (nbr_c,), out_c, list(r.init)))
-        folds[-1].gather_batch = 4 if len(r.table[0]) >= 4 else 1      # a long scan is a chain of dependent gathers: fetch four targets per round trip (codegen._emit_fold_stage)
+        folds[-1].gather_batch = 4 if len(r.table[0]) >= 4 else 1      # a long scan is a chain of dependent gathers: fetch four targets per round trip (codegen._emit_fold_stage: the lane kernel)
         # ... and a scan of a wavefront's worth of edges or more, when it is a plain sum, is folded by a whole WAVE per source (partial
         # sums per lane, a fixed shuffle tree: another association of the same sum, ~1e-16 x sqrt(degree)); wave_folds=False keeps
         # the one-lane sequential fold, bit for bit the reference's order

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from elodin_amd import codegen, dsl
-from tests import dsl_numpy
+from tests import dsl_numpy, fold_tables_common as ft
 
 
 @dsl.system
@@ -127,3 +127,34 @@ def test_only_plain_sums_are_folded_by_a_wave_per_source():
     assert codegen._graph_fold_kinds(tp.fold_stages[0].traced.outputs, 2) is None and "one WAVE per source" not in src
     tp, src = program(lambda acc, a, b: np_.array([acc[0] + acc[1] * b[0], acc[1] + 1.0]), [0.0, 0.0])      # g depends on the accumulator
     assert codegen._graph_fold_kinds(tp.fold_stages[0].traced.outputs, 2) is None and "one WAVE per source" not in src
+
+
+def test_every_fold_kernel_holds_the_one_per_edge_body():
+    """a fold whose edges sit in device memory performs the baked kernel's operations in its order.  True by
+    construction: the per-edge body is one text (codegen._fold_front), and it stands verbatim in the baked kernel, in the
+    device flavour's lane AND wave kernel, and in the stand-alone fold's kernel.  An emitter that forks the body fails here."""
+    def body_of(fs):
+        operands = lambda side: [(f"p{i}", wn) for i, (_, _, wn) in enumerate(side)]
+        return codegen._fold_front(codegen._Unit(), fs.traced.outputs, fs.out[2], operands(fs.left), operands(fs.right))[3]
+
+    def kernel(src, name):
+        assert src.count(f" void {name}(") == 1
+        a = src.index(f" void {name}(")
+        return src[a:src.index("\n}\n", a)]
+
+    texts = {}
+    for name, prog, widths in (("sum", lambda: ft.sum_program(True), {"x": 1, "y": 1, "z": 1}),
+                               ("chain", lambda: dsl.Program([double, fold_test, add_one], dsl.pipe(), []), {"x": 1, "n": 1})):
+        for tables in ("baked", "device"):
+            tp = prog().trace(widths, fold_edges=EDGES, fold_tables=tables)
+            texts[name, tables] = (body_of(tp.fold_stages[0]), codegen.generate_source(tp, "float64", 2))
+        (body, baked), (body_d, device) = texts[name, "baked"], texts[name, "device"]
+        assert body == body_d and "acc[0] =" in body
+        assert baked.count(body) == 1 and body in kernel(baked, "fold0_kernel")
+        assert body in kernel(device, "fold0_kernel")
+    body, device = texts["sum", "device"]
+    assert "one WAVE per source" in texts["sum", "baked"][1]                  # the baked sum's only fold kernel is the wave kernel
+    assert body in kernel(device, "fold0_wave") and device.count(body) == 2      # lane and wave: nowhere else
+    assert texts["chain", "device"][1].count(texts["chain", "device"][0]) == 1 and "fold0_wave" not in texts["chain", "device"][1]
+    alone = codegen.generate_graph_fold_source(fold_test.trace({"x": 1}))
+    assert texts["chain", "baked"][0] in kernel(alone, "graph_fold_kernel")
