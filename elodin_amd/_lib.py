@@ -27,6 +27,8 @@ FLAG_ASYNC_STEP = 4
 WATCH_ASYNC = 1      # sixdof_watch_read flags
 ENVELOPE_ASYNC = 1   # sixdof_history_envelope flags
 ENVELOPE_MAX_BINS = 512   # period * width one call reduces (csrc/envelope_plan.hpp: kEnvelopeMaxBins)
+QUANTILE_ASYNC = 1   # sixdof_history_quantiles flags
+QUANTILE_MAX_RANKS = 16   # ranks one call selects (SIXDOF_QUANTILE_MAX_RANKS)
 
 EFF_CONST_WRENCH = 1
 EFF_UNIFORM_GRAVITY = 2
@@ -143,6 +145,8 @@ SYMBOLS = {
     "sixdof_watch_read": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_history_envelope": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                           C.POINTER(C.c_void_p), C.c_uint32]),
+    "sixdof_history_quantiles": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                           C.POINTER(C.c_uint32), C.c_uint32, C.c_size_t, C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_set_model_apollo": (C.c_int, [_H, C.c_void_p]),
     "sixdof_download_column": (C.c_int, [_H, C.c_uint64]),
     "sixdof_upload_column": (C.c_int, [_H, C.c_uint64]),

@@ -842,6 +842,25 @@ class Exec:
         out["time"] = np.arange(first_tick, last_sample + 1, every, dtype=np.float64) * self._dt
         return out
 
+    def history_quantiles(self, components, first_tick: int, last_tick: int, q, every: int = 1, period: int = 1) -> Dict[str, Any]:
+        """The percentile band of ALL entities over time: {"time": seconds, component: {"count": [samples, period, w], "lower",
+        "upper", "linear": [samples, period, Q, w]}} for world ticks first_tick, first_tick + every, ... <= last_tick, selected
+        exactly on the device out of the ring (enable_history).  q: the ranks, as HipExec.quantile_ranks reads them (Fractions,
+        (num, den) pairs, or floats through their decimal repr).  Entry [j, g, i, c] covers element c of the executor rows r
+        with r % period == g; lower and upper are the order statistics on either side of rank q[i] among the finite elements
+        (count of them), linear the interpolation between the two."""
+        comps = [components] if isinstance(components, str) else list(components)
+        for comp in comps:
+            self._refuse_unrecorded("history_quantiles", comp, comp)
+        s = getattr(self, "_substeps", 1)
+        first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
+        if every < 1:
+            raise ValueError("history_quantiles: every must be at least 1")
+        last_sample = first_tick + (last_tick - first_tick) // every * every if last_tick >= first_tick else first_tick - 1
+        out: Dict[str, Any] = dict(self._hip.history_quantiles(comps, first_tick * s, last_sample * s, q, every * s, period))
+        out["time"] = np.arange(first_tick, last_sample + 1, every, dtype=np.float64) * self._dt
+        return out
+
     def column_ids(self, name: str) -> np.ndarray:
         """Entity id of each row of column_array(name)."""
         n = len(self._main_column_array(name))

@@ -22,6 +22,7 @@
 #include "envelope_plan.hpp"
 #include "history_plan.hpp"
 #include "kernels.hpp"
+#include "quantile_plan.hpp"
 
 namespace hip_fake {
 
@@ -277,6 +278,72 @@ hipError_t launch_history_envelope(const EnvelopeArgs& a, uint32_t n_components,
                 for (uint32_t b = 1; b < g.blocks; b++) r = envelope_merge(r, mine[uint64_t(b) * g.bins + bin]);
                 envelope_emit(r, to + uint64_t(bin / d.w) * kEnvelopeStats * d.w + bin % d.w, d.w);
             }
+        }
+    }
+    return launch(true);
+}
+// the selection itself (quantile_kernels.hip), serially: quantile_plan.hpp's keys, scan step and lo -> hi rule, pass by pass in the
+// launch's own scratch (one sample's slots at a time: the histograms and states of a bin are where the kernels keep them)
+template <class E>
+static void quantiles_of_tick(const char* src, uint64_t n, uint32_t w, uint32_t period, const QuantileRanks& rk, uint32_t* hist, QuantileSlot* state,
+                              double* to) {
+    using B = QuantileBits<E>;
+    const QuantileGeom g = quantile_geom(n, w, period, rk.count);
+    const uint32_t R = rk.count;
+    std::vector<uint64_t> keys;
+    for (uint32_t bin = 0; bin < g.bins; bin++) {
+        keys.clear();
+        for (uint64_t row = 0; row < g.rows; row++) {
+            E x;
+            std::memcpy(&x, src + (row * g.bins + bin) * sizeof(E), sizeof(E));
+            if (B::finite(B::raw(x))) keys.push_back(B::key(B::raw(x)));
+        }
+        uint32_t* h = hist + uint64_t(bin) * R * kQuantileDigits;
+        QuantileSlot* st = state + uint64_t(bin) * R;
+        uint64_t prefix[kQuantileMaxRanks] = {};
+        for (uint32_t pass = 0; pass < quantile_passes(B::bits); pass++) {
+            std::memset(h, 0, size_t(R) * kQuantileDigits * sizeof(uint32_t));
+            for (uint32_t r = 0; r < R; r++) prefix[r] = pass == 0 ? 0 : st[r].prefix;
+            const uint64_t mask = quantile_prefix_mask(B::bits, pass);
+            for (uint32_t r = 0; r < R; r++)
+                if (quantile_alias(prefix, r) == r && (pass == 0 || !(st[r].flags & kQuantileEmpty)))
+                    for (uint64_t key : keys)
+                        if ((key & mask) == prefix[r]) h[r * kQuantileDigits + quantile_digit(key, quantile_shift(B::bits, pass))]++;
+            for (uint32_t r = 0; r < R; r++) quantile_advance(st[r], h + quantile_alias(prefix, r) * kQuantileDigits, B::bits, pass, rk.num[r], rk.den);
+        }
+        for (uint32_t r = 0; r < R; r++) {
+            uint64_t next = ~uint64_t(0);
+            if (st[r].flags & kQuantileNeedNext)
+                for (uint64_t key : keys)
+                    if (key > st[r].prefix && key < next) next = key;
+            quantile_emit<E>(st[r], next, r, to + uint64_t(bin / w) * (1 + 2 * R) * w + bin % w, w);
+        }
+    }
+}
+hipError_t launch_history_quantiles(const QuantileArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, void* hist, void* state,
+                                    uint64_t slot_stride, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples,
+                                    uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
+    if (n_components == 0 || n_components > kQuantileMaxComponents || n_samples > 65535 || period == 0 || n % period != 0 || ranks.count == 0 ||
+        ranks.count > kQuantileMaxRanks || ranks.den == 0)
+        return launch(false);
+    if (n_samples == 0 || n == 0) return launch(true);
+    // the clears the real launcher enqueues between the passes: the first of them stands for all, fallible like them
+    if (hipError_t e = hipMemsetAsync(hist, 0, n_samples * slot_stride * kQuantileDigits * sizeof(uint32_t), s); e != hipSuccess) return e;
+    if (!need(live(state, n_samples * slot_stride * sizeof(QuantileSlot)), "quantile slot states")) return launch(false);
+    const uint64_t planes = 1 + 2 * uint64_t(ranks.count);
+    for (uint32_t k = 0; k < n_components; k++) {
+        const QuantileDesc& d = a.c[k];
+        if (!envelope_supported(d.w, period)) return launch(false);
+        const uint64_t total = n * d.w, bins = uint64_t(period) * d.w;
+        if (!need(d.slot_offset + bins * ranks.count <= slot_stride, "quantile slots of one sample")) return launch(false);
+        for (uint64_t j = 0; j < n_samples; j++) {
+            const char* src = static_cast<const char*>(d.ring) + sample_slot(first_tick, sample0 + j, every, ring) * total * elem;
+            double* to = out + d.out_offset + (sample0 + j) * period * planes * d.w;
+            if (!need(live(src, total * elem) && live(to, size_t(period) * planes * d.w * sizeof(double)), "ring or quantile staging")) return launch(false);
+            uint32_t* h = static_cast<uint32_t*>(hist) + (j * slot_stride + d.slot_offset) * kQuantileDigits;
+            QuantileSlot* st = static_cast<QuantileSlot*>(state) + j * slot_stride + d.slot_offset;
+            if (elem == 8) quantiles_of_tick<double>(src, n, d.w, period, ranks, h, st, to);
+            else quantiles_of_tick<float>(src, n, d.w, period, ranks, h, st, to);
         }
     }
     return launch(true);

@@ -1,8 +1,8 @@
 // history_plan.hpp — where a recorded tick sits in the telemetry ring, and which sampled ranges can be read from it.  Pure
 // arithmetic, no HIP.  Every reader of the ring validates with it — sixdof_history_read, sixdof_history_stream,
-// sixdof_watch_read, sixdof_history_envelope (sixdof_capi.cpp) — and everything that touches a slot addresses with it: those
+// sixdof_watch_read, sixdof_history_envelope, sixdof_history_quantiles (sixdof_capi.cpp) — and everything that touches a slot addresses with it: those
 // readers, snapshot_tick_to_ring and sixdof_step's overwrite check on the host, history_gather_kernel (join_kernels.hip) and
-// the envelope kernels (envelope_kernels.hip) on the device, the fake runtime's launchers (hip_fake.cpp).
+// the envelope and quantile kernels (envelope_kernels.hip, quantile_kernels.hip) on the device, the fake runtime's launchers (hip_fake.cpp).
 // history_plan_test.cpp checks it on the host.
 #pragma once
 

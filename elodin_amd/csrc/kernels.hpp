@@ -178,6 +178,25 @@ hipError_t launch_history_envelope(const EnvelopeArgs& a, uint32_t n_components,
                                    uint64_t n, uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples,
                                    uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
 
+// ---- ring quantiles: exact order statistics across the rows of every sampled tick (quantile_kernels.hip) ------------------
+constexpr uint32_t kQuantileMaxComponents = 32;   // components one launch covers (blockIdx.z)
+struct QuantileDesc {
+    const void* ring;        // [ring][n, w] blocks of this component
+    uint64_t out_offset;     // where its [n_samples][period][1 + 2 * ranks][w] block starts in `out`, in doubles
+    uint64_t slot_offset;    // where its period * w * ranks (bin, rank) slots of one sample start in a sample's scratch
+    uint32_t w;
+    uint32_t reserved;
+};
+struct QuantileArgs { QuantileDesc c[kQuantileMaxComponents]; };
+struct QuantileRanks;   // quantile_plan.hpp
+// Samples sample0 .. sample0 + n_samples - 1 (n_samples < 65,536) of the range first_tick, first_tick + every, ...  Per sample
+// `slot_stride` (bin, rank) slots: `hist` holds 256 uint32 counters per slot, `state` one QuantileSlot (quantile_plan.hpp); both
+// are scratch the launches clear themselves.  The caller has validated the range (sampled_range_ok), the ranks, n % period == 0
+// and envelope_supported(w, period).
+hipError_t launch_history_quantiles(const QuantileArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, void* hist,
+                                    void* state, uint64_t slot_stride, uint64_t n, uint32_t period, uint64_t first_tick,
+                                    uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
+
 hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags,
                             unsigned long long* count, hipStream_t s);
 

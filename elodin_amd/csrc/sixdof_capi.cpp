@@ -31,6 +31,7 @@
 #include "device_mem.hpp"
 #include "aql_chain.hpp"
 #include "envelope_plan.hpp"
+#include "quantile_plan.hpp"
 #include "history_plan.hpp"
 #include "step_plan.hpp"
 
@@ -155,6 +156,8 @@ struct History {
     std::vector<DeviceBuffer> model;  // one ring per component column of a generated program (same order as custom_model; empty: not recorded)
     // sixdof_history_envelope: device staging of one read's output and the stage-1 partial records, grown lazily, freed with the ring
     DeviceBuffer env_stage, env_partial;
+    // sixdof_history_quantiles: its staging, and the histograms and slot states of one launch; the same rules
+    DeviceBuffer quant_stage, quant_scratch;
     void reset() { *this = History{}; }
 };
 
@@ -1550,6 +1553,85 @@ int sixdof_history_envelope(sixdof_handle* h, const uint64_t* component_ids, siz
         }
     }
     return rd.deliver((flags & SIXDOF_ENVELOPE_ASYNC) != 0);
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// Exact order statistics of sampled ticks: the third staged reader, with the envelope's ordering, ring reads, copy lane and
+// limits — the passes of the radix select go on the compute stream behind the batch that recorded the ticks, only the staging
+// buffer is read from the copy stream.  Stateless.
+int sixdof_history_quantiles(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
+                             uint64_t n_samples, uint64_t every, uint32_t period, const uint32_t* rank_num, uint32_t rank_den,
+                             size_t n_ranks, double* const host_dst[], uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    if (flags & ~SIXDOF_QUANTILE_ASYNC) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: unknown flags");
+    if (!h->hist.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: no history ring (sixdof_set_history)");
+    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: every must be at least 1");
+    if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: period must be at least 1");
+    if (n_ranks == 0 || n_ranks > SIXDOF_QUANTILE_MAX_RANKS)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: " + std::to_string(n_ranks) + " ranks, 1 to " + std::to_string(SIXDOF_QUANTILE_MAX_RANKS) + " can be asked for");
+    if (!rank_num) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: null ranks");
+    if (rank_den == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: the ranks' denominator must be at least 1");
+    QuantileRanks ranks{};
+    ranks.den = rank_den, ranks.count = static_cast<uint32_t>(n_ranks);
+    for (size_t i = 0; i < n_ranks; i++) {
+        if (rank_num[i] > rank_den)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: rank " + std::to_string(rank_num[i]) + " / " + std::to_string(rank_den) + " is above 1");
+        ranks.num[i] = rank_num[i];
+    }
+    const uint64_t n = h->desc.n_entities;
+    if (n % period != 0)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+    if ((n / period) >> 32) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: more than 2^32 rows in a group");
+    if (n_samples == 0 || n_components == 0) return SIXDOF_OK;
+    if (!component_ids || !host_dst) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: null argument");
+    if (!sampled_range_ok(first_tick, n_samples, every, h->hist.first_tick, h->tick, h->hist.ring))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: ticks are not (all) in the ring");
+    History& hs = h->hist;
+    StagedRead rd{h, "history_quantiles", &hs.quant_stage};
+    const size_t planes = 1 + 2 * n_ranks;
+    std::vector<size_t> slot_offset(n_components);   // per component: its (bin, rank) slots in a sample's scratch
+    size_t slot_stride = 0, launch_slots = 0;
+    for (size_t k = 0; k < n_components; k++) {
+        const int rc = rd.add(component_ids[k], host_dst[k], static_cast<size_t>(n_samples) * period * planes, sizeof(double),
+                              "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
+        if (rc != SIXDOF_OK) return rc;
+        const size_t w = rd.parts[k].w;
+        if (!envelope_supported(w, period))
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: period " + std::to_string(period) + " x width " + std::to_string(w) +
+                                                            " exceeds the " + std::to_string(kEnvelopeMaxBins) + " (group, element) bins of one read");
+        if (k % kQuantileMaxComponents == 0) launch_slots = 0;   // every launch of at most 32 components reuses the scratch
+        slot_offset[k] = launch_slots;
+        launch_slots += static_cast<size_t>(period) * w * n_ranks;
+        slot_stride = std::max(slot_stride, launch_slots);
+    }
+    if (n == 0) {      // nothing to select from: count 0, order statistics NaN
+        for (size_t k = 0; k < n_components; k++)
+            for (size_t i = 0; i < rd.parts[k].bytes / sizeof(double); i++) host_dst[k][i] = i / rd.parts[k].w % planes == 0 ? 0.0 : std::nan("");
+        return SIXDOF_OK;
+    }
+    // samples per launch: the histograms and states of one launch stay within a fixed budget, and the grid's y extent below 2^16
+    constexpr size_t kScratchBudget = size_t(64) << 20;
+    const size_t hist_per_sample = slot_stride * kQuantileDigits * sizeof(uint32_t), per_sample = hist_per_sample + slot_stride * sizeof(QuantileSlot);
+    const uint64_t chunk = std::min<uint64_t>({n_samples, 65535, std::max<size_t>(1, kScratchBudget / per_sample)});
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = rd.claim(&hs.quant_scratch, chunk * per_sample); rc != SIXDOF_OK) return rc;
+    char* scratch = hs.quant_scratch.get<char>();
+    for (size_t k0 = 0; k0 < n_components; k0 += kQuantileMaxComponents) {
+        const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kQuantileMaxComponents, n_components - k0));
+        QuantileArgs a{};
+        for (uint32_t k = 0; k < cnt; k++) {
+            a.c[k].ring = rd.parts[k0 + k].ring;
+            a.c[k].out_offset = rd.parts[k0 + k].offset / sizeof(double);
+            a.c[k].slot_offset = slot_offset[k0 + k];
+            a.c[k].w = static_cast<uint32_t>(rd.parts[k0 + k].w);
+        }
+        for (uint64_t s0 = 0; s0 < n_samples; s0 += chunk) {   // histograms first, the states behind those of a whole chunk
+            hipError_t e = launch_history_quantiles(a, cnt, ranks, hs.quant_stage.get<double>(), scratch, scratch + chunk * hist_per_sample, slot_stride, n,
+                                                    period, first_tick, s0, std::min<uint64_t>(chunk, n_samples - s0), every, hs.ring, h->elem_size(),
+                                                    h->stream.get());
+            if (e != hipSuccess) return h->hip_fail(e, "history_quantiles");
+        }
+    }
+    return rd.deliver((flags & SIXDOF_QUANTILE_ASYNC) != 0);
 } SIXDOF_ABI_CATCH(err_of(h))
 
 int sixdof_download_column(sixdof_handle* h, uint64_t component_id) try {

@@ -610,6 +610,113 @@ class HipExec:
         self.sync()              # nothing of an earlier streaming run is in flight
         return self._stream_batches(n_batches, ticks_per_batch, every, read, lambda k: self._envelope_dict(names, raw[k]), consume, flags)
 
+    # ---- ring quantiles: exact order statistics across the rows of every sampled tick ---------------------------------
+    @staticmethod
+    def quantile_ranks(q):
+        """(numerators, denominator) of the ranks `q` over one common denominator.  An entry is a fractions.Fraction, a
+        (num, den) pair or a float; a float is read through its shortest decimal repr, Fraction(repr(x)), so 0.99 means 99/100
+        and not the binary fraction next to it.  ValueError: no rank or more than 16, a rank outside [0, 1], a common
+        denominator beyond 32 bits."""
+        import math
+        from fractions import Fraction
+        fr = []
+        for x in ([q] if isinstance(q, (int, float, Fraction)) else list(q)):
+            if isinstance(x, Fraction):
+                f = x
+            elif isinstance(x, (tuple, list)):
+                num, den = x
+                if int(den) < 1:
+                    raise ValueError(f"quantiles: rank {x!r} has no positive denominator")
+                f = Fraction(int(num), int(den))
+            else:
+                x = float(x)
+                if not math.isfinite(x):
+                    raise ValueError(f"quantiles: rank {x!r} is not a number in [0, 1]")
+                f = Fraction(repr(x))
+            if not 0 <= f <= 1:
+                raise ValueError(f"quantiles: rank {x!r} is outside [0, 1]")
+            fr.append(f)
+        if not 1 <= len(fr) <= L.QUANTILE_MAX_RANKS:
+            raise ValueError(f"quantiles: {len(fr)} ranks, 1 to {L.QUANTILE_MAX_RANKS} can be asked for")
+        den = 1
+        for f in fr:
+            den = den * f.denominator // math.gcd(den, f.denominator)
+        if den > 0xFFFFFFFF:
+            raise ValueError(f"quantiles: the ranks' common denominator {den} does not fit 32 bits")
+        return [int(f * den) for f in fr], den
+
+    def _quantile_buffers(self, names, n_samples: int, period: int, n_ranks: int):
+        raw = [np.empty((n_samples, max(period, 1), 1 + 2 * n_ranks, self._recorded_width(name)), dtype=np.float64) for name in names]
+        ptrs = (C.c_void_p * max(1, len(names)))(*[a.ctypes.data for a in raw])
+        comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
+        return raw, ptrs, comp
+
+    @staticmethod
+    def _quantile_dict(names, raw, num, den) -> dict:
+        """[s, period, 1 + 2Q, w] blocks -> {name: {"count": int64 [s, period, w], "lower", "upper", "linear": [s, period, Q, w]}}.
+        linear = lower + (upper - lower) * frac with frac = (num * (count - 1) mod den) / den, evaluated here in f64: what
+        numpy's default ("linear") interpolation evaluates, up to rounding."""
+        out = {}
+        for name, a in zip(names, raw):
+            count = a[:, :, 0, :].astype(np.int64)
+            lower, upper = a[:, :, 1::2, :], a[:, :, 2::2, :]
+            m1 = np.maximum(count - 1, 0).astype(object)[:, :, None, :]      # Python integers: num * (m - 1) is exact
+            rem = (m1 * np.array(num, dtype=object)[None, None, :, None]) % den
+            frac = rem.astype(np.float64) / float(den)
+            with np.errstate(invalid="ignore"):
+                linear = lower + (upper - lower) * frac
+            out[name] = {"count": count, "lower": lower, "upper": upper, "linear": linear}
+        return out
+
+    def history_quantiles(self, names: Sequence[str], first_tick: int, last_tick: int, q, every: int = 1, period: int = 1) -> dict:
+        """{name: {"count": int64 [s, period, w], "lower", "upper", "linear": f64 [s, period, Q, w]}}: exact order statistics over
+        the rows of ticks first_tick, first_tick + every, ... <= last_tick, selected on the device out of the ring.  Entry
+        [j, g, i, c] covers element c of the rows r with r % period == g and rank q[i] (quantile_ranks: Fractions, (num, den)
+        pairs or floats read as their decimal repr).  With m = count finite elements x(0) <= ... <= x(m-1) (non-finite ones
+        are skipped), lower = x(floor(q (m-1))) and upper = x(ceil(q (m-1))), rank arithmetic in integers: both are elements
+        of the ring, bit for bit (-0.0 below +0.0).  linear = lower + (upper - lower) * frac, frac = (num (m-1) mod den) / den in
+        f64 on the host.  count == 0 leaves the three NaN.  Stateless: no watch is involved."""
+        names = [names] if isinstance(names, str) else list(names)
+        num, den = self.quantile_ranks(q)
+        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
+        n_samples = self._sample_count(first_tick, last_tick, every)
+        raw, ptrs, comp = self._quantile_buffers(names, n_samples, period, len(num))
+        nums = (C.c_uint32 * len(num))(*num)
+        rc = self._lib.sixdof_history_quantiles(self._h, comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), first_tick, n_samples, every,
+                                                max(period, 0), nums, den, len(num), ptrs, 0)
+        if rc != L.OK:
+            _raise(self._h, rc, "sixdof_history_quantiles")
+        return self._quantile_dict(names, raw, num, den)
+
+    def stream_quantiles(self, names: Sequence[str], n_batches: int, ticks_per_batch: int, q, every: int = 1, period: int = 1, consume=None,
+                         flags: int = 0) -> float:
+        """stream_envelope for quantiles: every `every`-th tick of every batch selected on the compute stream and copied on the
+        copy stream into one of two host buffer sets while the next batch computes; a ring one batch deep is enough (enabled
+        here unless enable_history already made one at least that large).  `consume(batch_index, first_tick, {name: {"count",
+        "lower", "upper", "linear"}})` sees a batch once it has landed — first_tick is the batch's first SAMPLED tick; lower and
+        upper are views of buffers reused two batches later.  Returns the wall time in seconds."""
+        names = [names] if isinstance(names, str) else list(names)
+        num, den = self.quantile_ranks(q)
+        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
+        if every < 1 or ticks_per_batch < 1 or ticks_per_batch % every != 0:
+            raise ValueError(f"stream_quantiles: ticks_per_batch ({ticks_per_batch}) must be a positive multiple of every ({every})")
+        if period < 1:
+            raise ValueError("stream_quantiles: period must be at least 1")
+        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
+            self.enable_history(ticks_per_batch)
+        n_samples = ticks_per_batch // every
+        raw, ptrs, comps = zip(*[self._quantile_buffers(names, n_samples, period, len(num)) for _ in range(2)])
+        comp_p = comps[0].ctypes.data_as(C.POINTER(C.c_uint64))
+        nums = (C.c_uint32 * len(num))(*num)
+
+        def read(first_tick, k):
+            rc = self._lib.sixdof_history_quantiles(self._h, comp_p, len(names), first_tick, n_samples, every, period, nums, den, len(num), ptrs[k],
+                                                    L.QUANTILE_ASYNC)
+            if rc != L.OK:
+                _raise(self._h, rc, "sixdof_history_quantiles")
+        self.sync()              # nothing of an earlier streaming run is in flight
+        return self._stream_batches(n_batches, ticks_per_batch, every, read, lambda k: self._quantile_dict(names, raw[k], num, den), consume, flags)
+
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))
 
@@ -651,7 +758,7 @@ class HipExec:
         return self._stream_batches(n_batches, ticks_per_batch, 1, read, lambda k: bufs[k], consume, flags)
 
     def _stream_batches(self, n_batches: int, ticks_per_batch: int, first_offset: int, read, landed, consume, flags: int) -> float:
-        """The double-buffered loop of stream_history / stream_series / stream_envelope: batch i is enqueued, then batch i-1 is
+        """The double-buffered loop of stream_history / stream_series / stream_envelope / stream_quantiles: batch i is enqueued, then batch i-1 is
         waited for and consumed, then batch i's read-back is enqueued into buffer set i % 2, where it overlaps batch i+1.
         `first_offset`: the batch's first sampled tick, counted from the tick before the batch; `read(first_tick, k)` enqueues
         the asynchronous read into buffer set k; `landed(k)` is what `consume(batch_index, first_tick, .)` receives of set k.

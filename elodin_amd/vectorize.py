@@ -317,6 +317,14 @@ class Campaign:
         a diverged run's non-finite elements are skipped and show as count below n_runs."""
         return self.exec.history_envelope(components, first_tick, last_tick, every, period=self.entities_per_run)
 
+    def quantiles(self, components, first_tick: int, last_tick: int, q, every: int = 1) -> Dict[str, Any]:
+        """The percentile band of the runs over time, out of the device ring (self.exec.enable_history): {"time": seconds,
+        component: {"count": [sample, entity-of-run, w], "lower", "upper", "linear": [sample, entity-of-run, rank, w]}} over world
+        ticks first_tick, first_tick + every, ... <= last_tick, for the ranks q (e.g. (0.01, 0.5, 0.99)).  Entry [j, e, i, c] is
+        taken over entity e of every run: exact order statistics, a diverged run's non-finite elements skipped and showing as
+        count below n_runs."""
+        return self.exec.history_quantiles(components, first_tick, last_tick, q, every, period=self.entities_per_run)
+
     def result_table(self, names: Sequence[str]) -> np.ndarray:
         """The runs' `el.monte_carlo.result(...)` records as [n_runs, len(names)] (NaN where a run reported nothing)."""
         out = np.full((self.n_runs, len(names)), np.nan)

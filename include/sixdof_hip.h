@@ -458,6 +458,38 @@ int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples,
 int sixdof_history_envelope(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
                             uint64_t n_samples, uint64_t every, uint32_t period, double* const host_dst[], uint32_t flags);
 
+/* ---- ring quantiles: the percentile band of ALL rows over time -----------------------------------------------------
+ * Mean and spread summarise a skewed dispersion, or one with a few diverging runs, poorly; what a campaign's reader wants of
+ * touchdown velocity or propellant margin is p1 / p50 / p99 per tick — order statistics, selected on the device, exactly.
+ *
+ * Samples, components and groups are sixdof_history_envelope's: sample j is the state after tick first_tick + j * every, group
+ * g < period the rows r with r % period == g, reduced per element c < w_k.  The ranks are the exact rationals
+ * rank_num[i] / rank_den (1 <= rank_den, rank_num[i] <= rank_den, 1 <= n_ranks <= SIXDOF_QUANTILE_MAX_RANKS; duplicates and
+ * any order are allowed).  With m the number of finite elements of a group (non-finite elements are skipped) and
+ * x(0) <= ... <= x(m-1) those elements in ascending order,
+ *   lo_i = floor(num_i * (m - 1) / den),  hi_i = ceil(num_i * (m - 1) / den)     in unsigned 64-bit integer arithmetic;
+ * no floating-point rank arithmetic is used.  host_dst[k] receives [n_samples][period][1 + 2 * n_ranks][w_k] doubles:
+ *   plane 0          m
+ *   plane 1 + 2 * i  x(lo_i)
+ *   plane 2 + 2 * i  x(hi_i)         m = 0: plane 0 is 0 and the rank planes are NaN.
+ * Every value is an element of the ring converted to double (exact for an f32 handle): nothing is interpolated or rounded on
+ * the device, so a value is bit-identical whichever range, `every`, component list, rank list or flags read it.  The order is
+ * the total order of the sign-magnitude bit pattern: -0.0 sorts below +0.0.  A radix select, most significant byte first, over
+ * integer keys: integer atomics only, 9 reads of a tick's block for f64 and 5 for f32, never a sort.
+ * flags = 0: returns when the data is in host_dst.  SIXDOF_QUANTILE_ASYNC: the rules of SIXDOF_WATCH_ASYNC — the copies go on the
+ * copy stream, sixdof_download_wait blocks until they have landed, host_dst stays allocated (and page-locked) until
+ * sixdof_sync.  Either way the ring is read on the compute stream: a later sixdof_step may overwrite the slots at once.
+ * n_samples = 0 is a no-op.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied: no ring, every = 0, period = 0, a row count that
+ * is no multiple of period, period * w_k above 512 (the envelope's limit), n_ranks of 0 or above 16, rank_den = 0, a numerator
+ * above the denominator, a null rank pointer, a sampled tick that is not (or no longer) in the ring, unknown flags, a null
+ * buffer.  A call that fails in the runtime leaves the ring as it was; a staging or scratch buffer that could not be grown is
+ * absent (size 0) and the next call allocates it again. */
+#define SIXDOF_QUANTILE_ASYNC 1u
+#define SIXDOF_QUANTILE_MAX_RANKS 16
+int sixdof_history_quantiles(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
+                             uint64_t n_samples, uint64_t every, uint32_t period, const uint32_t* rank_num, uint32_t rank_den,
+                             size_t n_ranks, double* const host_dst[], uint32_t flags);
+
 /* ---- rollout models: systems piped AROUND six_dof, fused with it (the pipes of examples/<name>/sim.py) ------------- */
 struct sixdof_apollo_tables; /* include/sixdof_apollo.h */
 /* Select the Apollo-lander rollout model (examples/apollo-lander/sim.py:517-526 + the guidance sidecar
