@@ -791,6 +791,16 @@ class Exec:
         if comp in getattr(self._hip, "_windows", {}):
             raise NotImplementedError(f"{who}: {what}: {comp} is a window component, the ring does not copy it per tick")
 
+    def _sampled_ticks(self, who: str, first_tick: int, last_tick: int, every: int):
+        """World ticks first_tick, first_tick + every, ... <= last_tick as the executor counts them — (first, last, every) in its
+        sub-stepped ticks, the last one a sample — and their "time" axis in seconds."""
+        s = getattr(self, "_substeps", 1)
+        first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
+        if every < 1:
+            raise ValueError(f"{who}: every must be at least 1")
+        last_sample = first_tick + (last_tick - first_tick) // every * every if last_tick >= first_tick else first_tick - 1
+        return (first_tick * s, last_sample * s, every * s), np.arange(first_tick, last_sample + 1, every, dtype=np.float64) * self._dt
+
     def history_series(self, keys, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, np.ndarray]:
         """The dict shape of history() — "time" plus one series per "entity.component" key — for world ticks first_tick,
         first_tick + every, ... <= last_tick, read out of the device ring (enable_history) through a watch list: only the
@@ -812,14 +822,9 @@ class Exec:
         if cached is None or cached[:2] != (comps, ents) or cached[2] is not getattr(self._hip, "_watch", None):
             self._hip.set_watch(comps, np.asarray(ents, dtype=np.uint64))
             self._series_watch = (comps, ents, self._hip._watch)
-        s = getattr(self, "_substeps", 1)
-        first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
-        if every < 1:
-            raise ValueError("history_series: every must be at least 1")
-        last_sample = first_tick + (last_tick - first_tick) // every * every if last_tick >= first_tick else first_tick - 1
-        blocks = self._hip.history_series(first_tick * s, last_sample * s, every * s)
-        ticks = np.arange(first_tick, last_sample + 1, every, dtype=np.float64)
-        out = {"time": ticks * self._dt}
+        ticks, time = self._sampled_ticks("history_series", first_tick, last_tick, every)
+        blocks = self._hip.history_series(*ticks)
+        out = {"time": time}
         for key, (e, comp) in zip(keys, pairs):
             series = np.array(blocks[comp][ents.index(e)], dtype=np.float64)
             out[key] = series[:, 0] if series.shape[1] == 1 else series
@@ -833,13 +838,9 @@ class Exec:
         comps = [components] if isinstance(components, str) else list(components)
         for comp in comps:
             self._refuse_unrecorded("history_envelope", comp, comp)
-        s = getattr(self, "_substeps", 1)
-        first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
-        if every < 1:
-            raise ValueError("history_envelope: every must be at least 1")
-        last_sample = first_tick + (last_tick - first_tick) // every * every if last_tick >= first_tick else first_tick - 1
-        out: Dict[str, Any] = dict(self._hip.history_envelope(comps, first_tick * s, last_sample * s, every * s, period))
-        out["time"] = np.arange(first_tick, last_sample + 1, every, dtype=np.float64) * self._dt
+        (first, last, step), time = self._sampled_ticks("history_envelope", first_tick, last_tick, every)
+        out: Dict[str, Any] = dict(self._hip.history_envelope(comps, first, last, step, period))
+        out["time"] = time
         return out
 
     def history_quantiles(self, components, first_tick: int, last_tick: int, q, every: int = 1, period: int = 1) -> Dict[str, Any]:
@@ -852,13 +853,9 @@ class Exec:
         comps = [components] if isinstance(components, str) else list(components)
         for comp in comps:
             self._refuse_unrecorded("history_quantiles", comp, comp)
-        s = getattr(self, "_substeps", 1)
-        first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
-        if every < 1:
-            raise ValueError("history_quantiles: every must be at least 1")
-        last_sample = first_tick + (last_tick - first_tick) // every * every if last_tick >= first_tick else first_tick - 1
-        out: Dict[str, Any] = dict(self._hip.history_quantiles(comps, first_tick * s, last_sample * s, q, every * s, period))
-        out["time"] = np.arange(first_tick, last_sample + 1, every, dtype=np.float64) * self._dt
+        (first, last, step), time = self._sampled_ticks("history_quantiles", first_tick, last_tick, every)
+        out: Dict[str, Any] = dict(self._hip.history_quantiles(comps, first, last, q, step, period))
+        out["time"] = time
         return out
 
     def column_ids(self, name: str) -> np.ndarray:

@@ -21,12 +21,12 @@
 namespace sixdof {
 
 template <class E>
-__global__ __launch_bounds__(kEnvelopeThreads) void envelope_partial_kernel(EnvelopeArgs a, EnvelopePartial* __restrict__ partial,
+__global__ __launch_bounds__(kEnvelopeThreads) void envelope_partial_kernel(RingBinArgs a, EnvelopePartial* __restrict__ partial,
                                                                             uint64_t partial_stride, uint64_t n, uint32_t period,
                                                                             uint64_t first_tick, uint64_t sample0, uint64_t every,
                                                                             uint64_t ring) {
     __shared__ EnvelopePartial rec[kEnvelopeThreads];
-    const EnvelopeDesc d = a.c[blockIdx.z];
+    const RingBinDesc d = a.c[blockIdx.z];
     const EnvelopeGeom g = envelope_geom(n, d.w, period);
     const uint32_t b = blockIdx.x, t = threadIdx.x;
     if (b >= g.blocks) return;   // a narrower component than the one that sized the grid: the whole block leaves
@@ -53,27 +53,27 @@ __global__ __launch_bounds__(kEnvelopeThreads) void envelope_partial_kernel(Enve
         if (j < s && j + s < g.per_bin) rec[t] = envelope_merge(rec[t], rec[t + s * g.bins]);
         __syncthreads();
     }
-    if (t < g.bins) partial[(uint64_t)blockIdx.y * partial_stride + d.partial_offset + (uint64_t)b * g.bins + t] = rec[t];
+    if (t < g.bins) partial[(uint64_t)blockIdx.y * partial_stride + d.scratch_offset + (uint64_t)b * g.bins + t] = rec[t];
 }
 
-__global__ __launch_bounds__(128) void envelope_merge_kernel(EnvelopeArgs a, const EnvelopePartial* __restrict__ partial,
+__global__ __launch_bounds__(128) void envelope_merge_kernel(RingBinArgs a, const EnvelopePartial* __restrict__ partial,
                                                              uint64_t partial_stride, double* __restrict__ out, uint64_t n,
                                                              uint32_t period, uint64_t sample0) {
-    const EnvelopeDesc d = a.c[blockIdx.z];
+    const RingBinDesc d = a.c[blockIdx.z];
     const EnvelopeGeom g = envelope_geom(n, d.w, period);
     const uint32_t bin = blockIdx.x * blockDim.x + threadIdx.x;
     if (bin >= g.bins) return;
-    const EnvelopePartial* __restrict__ p = partial + (uint64_t)blockIdx.y * partial_stride + d.partial_offset + bin;
+    const EnvelopePartial* __restrict__ p = partial + (uint64_t)blockIdx.y * partial_stride + d.scratch_offset + bin;
     EnvelopePartial r = p[0];
     for (uint32_t b = 1; b < g.blocks; b++) r = envelope_merge(r, p[(uint64_t)b * g.bins]);
     const uint64_t group = bin / d.w, c = bin % d.w, sample = sample0 + blockIdx.y;
     envelope_emit(r, out + d.out_offset + ((sample * period + group) * kEnvelopeStats) * d.w + c, d.w);
 }
 
-hipError_t launch_history_envelope(const EnvelopeArgs& a, uint32_t n_components, double* out, void* partial, uint64_t partial_stride,
+hipError_t launch_history_envelope(const RingBinArgs& a, uint32_t n_components, double* out, void* partial, uint64_t partial_stride,
                                    uint64_t n, uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples,
                                    uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
-    if (n_components == 0 || n_components > kEnvelopeMaxComponents || n_samples > 65535 || period == 0) return hipErrorInvalidValue;
+    if (!envelope_launch_ok(n_components, kRingBinMaxComponents, n_samples, period)) return hipErrorInvalidValue;
     if (n_samples == 0 || n == 0) return hipSuccess;
     uint32_t blocks = 0, bins = 0;
     for (uint32_t k = 0; k < n_components; k++) {

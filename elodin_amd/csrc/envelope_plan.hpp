@@ -32,6 +32,11 @@ struct EnvelopeGeom {
 SIXDOF_HOST_DEVICE inline bool envelope_supported(uint64_t w, uint64_t period) {
     return w >= 1 && period >= 1 && period <= kEnvelopeMaxBins && w <= kEnvelopeMaxBins && period * w <= kEnvelopeMaxBins;
 }
+// What launch_history_envelope accepts, for the launcher (envelope_kernels.hip) and its host twin (hip_fake.cpp) alike: at most
+// `max_components` (kernels.hpp: kRingBinMaxComponents) components, a grid y extent of n_samples below 2^16.
+inline bool envelope_launch_ok(uint32_t n_components, uint32_t max_components, uint64_t n_samples, uint32_t period) {
+    return n_components != 0 && n_components <= max_components && n_samples <= 65535 && period != 0;
+}
 SIXDOF_HOST_DEVICE inline EnvelopeGeom envelope_geom(uint64_t n, uint32_t w, uint32_t period) {
     EnvelopeGeom g{};
     g.bins = period * w;

@@ -238,49 +238,68 @@ hipError_t launch_history_gather(const HistoryGatherArgs& a, uint32_t n_componen
     }
     return launch(true);
 }
-// the reduction itself (envelope_kernels.hip), serially: envelope_plan.hpp's arithmetic in the kernels' geometry and merge order
-hipError_t launch_history_envelope(const EnvelopeArgs& a, uint32_t n_components, double* out, void* partial, uint64_t partial_stride, uint64_t n,
-                                   uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring,
-                                   size_t elem, hipStream_t) {
-    if (n_components == 0 || n_components > kEnvelopeMaxComponents || n_samples > 65535 || period == 0) return launch(false);
-    EnvelopePartial* part = static_cast<EnvelopePartial*>(partial);
-    if (!need(live(part, n_samples * partial_stride * sizeof(EnvelopePartial)), "envelope partial records")) return launch(false);
-    std::vector<EnvelopePartial> rec(kEnvelopeThreads);
-    for (uint32_t k = 0; k < n_components && n; k++) {
-        const EnvelopeDesc& d = a.c[k];
-        if (!envelope_supported(d.w, period)) return launch(false);
-        const EnvelopeGeom g = envelope_geom(n, d.w, period);
+// The walk both reduction twins make over a launch: every component, every sample of the chunk.  The component's `units` scratch
+// units of one sample fit the stride; the sample's block in the ring and its [period][planes][w] block in the staging buffer are
+// live, and go to tick(d, j, src, to) — the arithmetic of one tick, all that differs between the twins.
+template <class Units, class Tick>
+static bool ring_bin_walk(const char* who, const RingBinArgs& a, uint32_t n_components, double* out, uint64_t planes, uint64_t stride, uint64_t n,
+                          uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem,
+                          Units units, Tick tick) {
+    const std::string scratch = std::string(who) + " scratch of one sample", blocks = std::string("ring or ") + who + " staging";
+    for (uint32_t k = 0; k < n_components; k++) {
+        const RingBinDesc& d = a.c[k];
+        if (!envelope_supported(d.w, period)) return false;
+        if (!need(d.scratch_offset + units(d) <= stride, scratch.c_str())) return false;
         const uint64_t total = n * d.w;
-        if (!need(d.partial_offset + uint64_t(g.blocks) * g.bins <= partial_stride, "envelope partial records of one sample")) return launch(false);
         for (uint64_t j = 0; j < n_samples; j++) {
             const char* src = static_cast<const char*>(d.ring) + sample_slot(first_tick, sample0 + j, every, ring) * total * elem;
-            double* to = out + d.out_offset + (sample0 + j) * period * kEnvelopeStats * d.w;
-            if (!need(live(src, total * elem) && live(to, size_t(period) * kEnvelopeStats * d.w * sizeof(double)), "ring or envelope staging")) return launch(false);
-            EnvelopePartial* mine = part + j * partial_stride + d.partial_offset;
-            for (uint32_t b = 0; b < g.blocks; b++) {                       // stage 1
-                for (uint32_t t = 0; t < g.tile; t++) {
-                    EnvelopePartial acc = envelope_empty();
-                    for (uint64_t i = uint64_t(b) * g.tile + t; i < total; i += uint64_t(g.blocks) * g.tile) {
-                        double x;
-                        if (elem == 8) std::memcpy(&x, src + i * 8, 8);
-                        else { float f; std::memcpy(&f, src + i * 4, 4); x = f; }
-                        envelope_accumulate(acc, x);
-                    }
-                    rec[t] = acc;
-                }
-                for (uint32_t bin = 0; bin < g.bins; bin++) {
-                    envelope_tree_fold(&rec[bin], g.per_bin, g.bins);
-                    mine[uint64_t(b) * g.bins + bin] = rec[bin];
-                }
-            }
-            for (uint32_t bin = 0; bin < g.bins; bin++) {                   // stage 2
-                EnvelopePartial r = mine[bin];
-                for (uint32_t b = 1; b < g.blocks; b++) r = envelope_merge(r, mine[uint64_t(b) * g.bins + bin]);
-                envelope_emit(r, to + uint64_t(bin / d.w) * kEnvelopeStats * d.w + bin % d.w, d.w);
-            }
+            double* to = out + d.out_offset + (sample0 + j) * period * planes * d.w;
+            if (!need(live(src, total * elem) && live(to, size_t(period) * planes * d.w * sizeof(double)), blocks.c_str())) return false;
+            tick(d, j, src, to);
         }
     }
-    return launch(true);
+    return true;
+}
+// the reduction itself (envelope_kernels.hip), serially: envelope_plan.hpp's arithmetic in the kernels' geometry and merge order
+hipError_t launch_history_envelope(const RingBinArgs& a, uint32_t n_components, double* out, void* partial, uint64_t partial_stride, uint64_t n,
+                                   uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring,
+                                   size_t elem, hipStream_t) {
+    if (!envelope_launch_ok(n_components, kRingBinMaxComponents, n_samples, period)) return launch(false);
+    EnvelopePartial* part = static_cast<EnvelopePartial*>(partial);
+    if (!need(live(part, n_samples * partial_stride * sizeof(EnvelopePartial)), "envelope partial records")) return launch(false);
+    if (n == 0) return launch(true);
+    std::vector<EnvelopePartial> rec(kEnvelopeThreads);
+    auto records = [&](const RingBinDesc& d) {
+        const EnvelopeGeom g = envelope_geom(n, d.w, period);
+        return uint64_t(g.blocks) * g.bins;
+    };
+    return launch(ring_bin_walk("envelope", a, n_components, out, kEnvelopeStats, partial_stride, n, period, first_tick, sample0, n_samples, every, ring, elem, records,
+                                [&](const RingBinDesc& d, uint64_t j, const char* src, double* to) {
+        const EnvelopeGeom g = envelope_geom(n, d.w, period);
+        const uint64_t total = n * d.w;
+        EnvelopePartial* mine = part + j * partial_stride + d.scratch_offset;
+        for (uint32_t b = 0; b < g.blocks; b++) {                       // stage 1
+            for (uint32_t t = 0; t < g.tile; t++) {
+                EnvelopePartial acc = envelope_empty();
+                for (uint64_t i = uint64_t(b) * g.tile + t; i < total; i += uint64_t(g.blocks) * g.tile) {
+                    double x;
+                    if (elem == 8) std::memcpy(&x, src + i * 8, 8);
+                    else { float f; std::memcpy(&f, src + i * 4, 4); x = f; }
+                    envelope_accumulate(acc, x);
+                }
+                rec[t] = acc;
+            }
+            for (uint32_t bin = 0; bin < g.bins; bin++) {
+                envelope_tree_fold(&rec[bin], g.per_bin, g.bins);
+                mine[uint64_t(b) * g.bins + bin] = rec[bin];
+            }
+        }
+        for (uint32_t bin = 0; bin < g.bins; bin++) {                   // stage 2
+            EnvelopePartial r = mine[bin];
+            for (uint32_t b = 1; b < g.blocks; b++) r = envelope_merge(r, mine[uint64_t(b) * g.bins + bin]);
+            envelope_emit(r, to + uint64_t(bin / d.w) * kEnvelopeStats * d.w + bin % d.w, d.w);
+        }
+    }));
 }
 // the selection itself (quantile_kernels.hip), serially: quantile_plan.hpp's keys, scan step and lo -> hi rule, pass by pass in the
 // launch's own scratch (one sample's slots at a time: the histograms and states of a bin are where the kernels keep them)
@@ -320,33 +339,22 @@ static void quantiles_of_tick(const char* src, uint64_t n, uint32_t w, uint32_t 
         }
     }
 }
-hipError_t launch_history_quantiles(const QuantileArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, void* hist, void* state,
+hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, void* hist, void* state,
                                     uint64_t slot_stride, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples,
                                     uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
-    if (n_components == 0 || n_components > kQuantileMaxComponents || n_samples > 65535 || period == 0 || n % period != 0 || ranks.count == 0 ||
-        ranks.count > kQuantileMaxRanks || ranks.den == 0)
-        return launch(false);
+    if (!quantile_launch_ok(n_components, kRingBinMaxComponents, ranks, n, n_samples, period)) return launch(false);
     if (n_samples == 0 || n == 0) return launch(true);
     // the clears the real launcher enqueues between the passes: the first of them stands for all, fallible like them
     if (hipError_t e = hipMemsetAsync(hist, 0, n_samples * slot_stride * kQuantileDigits * sizeof(uint32_t), s); e != hipSuccess) return e;
     if (!need(live(state, n_samples * slot_stride * sizeof(QuantileSlot)), "quantile slot states")) return launch(false);
-    const uint64_t planes = 1 + 2 * uint64_t(ranks.count);
-    for (uint32_t k = 0; k < n_components; k++) {
-        const QuantileDesc& d = a.c[k];
-        if (!envelope_supported(d.w, period)) return launch(false);
-        const uint64_t total = n * d.w, bins = uint64_t(period) * d.w;
-        if (!need(d.slot_offset + bins * ranks.count <= slot_stride, "quantile slots of one sample")) return launch(false);
-        for (uint64_t j = 0; j < n_samples; j++) {
-            const char* src = static_cast<const char*>(d.ring) + sample_slot(first_tick, sample0 + j, every, ring) * total * elem;
-            double* to = out + d.out_offset + (sample0 + j) * period * planes * d.w;
-            if (!need(live(src, total * elem) && live(to, size_t(period) * planes * d.w * sizeof(double)), "ring or quantile staging")) return launch(false);
-            uint32_t* h = static_cast<uint32_t*>(hist) + (j * slot_stride + d.slot_offset) * kQuantileDigits;
-            QuantileSlot* st = static_cast<QuantileSlot*>(state) + j * slot_stride + d.slot_offset;
-            if (elem == 8) quantiles_of_tick<double>(src, n, d.w, period, ranks, h, st, to);
-            else quantiles_of_tick<float>(src, n, d.w, period, ranks, h, st, to);
-        }
-    }
-    return launch(true);
+    return launch(ring_bin_walk("quantile", a, n_components, out, 1 + 2 * uint64_t(ranks.count), slot_stride, n, period, first_tick, sample0, n_samples, every, ring, elem,
+                                [&](const RingBinDesc& d) { return uint64_t(period) * d.w * ranks.count; },
+                                [&](const RingBinDesc& d, uint64_t j, const char* src, double* to) {
+        uint32_t* h = static_cast<uint32_t*>(hist) + (j * slot_stride + d.scratch_offset) * kQuantileDigits;
+        QuantileSlot* st = static_cast<QuantileSlot*>(state) + j * slot_stride + d.scratch_offset;
+        if (elem == 8) quantiles_of_tick<double>(src, n, d.w, period, ranks, h, st, to);
+        else quantiles_of_tick<float>(src, n, d.w, period, ranks, h, st, to);
+    }));
 }
 hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags, unsigned long long* count, hipStream_t) {
     return launch(need(live(pos, n * 7 * elem) && live(vel, n * 6 * elem) && live(count, 8) && (!flags || live(flags, n)), "count_nonfinite buffers"));

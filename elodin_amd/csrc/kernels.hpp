@@ -161,39 +161,36 @@ hipError_t launch_history_gather(const HistoryGatherArgs& a, uint32_t n_componen
                                  uint64_t m, uint64_t n, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                                  uint64_t ring, size_t elem, hipStream_t s);
 
-// ---- ring envelopes: count / min / max / mean / m2 across the rows of every sampled tick (envelope_kernels.hip) -----
-constexpr uint32_t kEnvelopeMaxComponents = 32;   // components one launch covers (blockIdx.z)
-struct EnvelopeDesc {
+// ---- ring reductions: one sampled tick of one component reduced into period * w (group, element) bins ---------------------
+// One component of a launch, for every kernel that reduces into bins (envelope_kernels.hip, quantile_kernels.hip): blockIdx.z
+// picks it.  sixdof_capi.cpp's ring_bin_read fills these.
+constexpr uint32_t kRingBinMaxComponents = 32;   // components one launch covers
+struct RingBinDesc {
     const void* ring;         // [ring][n, w] blocks of this component
-    uint64_t out_offset;      // where its [n_samples][period][5][w] block starts in `out`, in doubles
-    uint64_t partial_offset;  // where its [blocks][period * w] records of one sample start in a sample's partial records
+    uint64_t out_offset;      // where its [n_samples][period][planes][w] block starts in `out`, in doubles
+    uint64_t scratch_offset;  // where its units of one sample start in a sample's scratch, in the reduction's own units
     uint32_t w;
     uint32_t reserved;
 };
-struct EnvelopeArgs { EnvelopeDesc c[kEnvelopeMaxComponents]; };   // by value: 1 KiB of kernel arguments
+struct RingBinArgs { RingBinDesc c[kRingBinMaxComponents]; };   // by value: 1 KiB of kernel arguments
+
+// ---- ring envelopes: count / min / max / mean / m2 across the rows of every sampled tick (envelope_kernels.hip) -----
+// 5 planes; a scratch unit is one EnvelopePartial record, [blocks][period * w] of them per component and sample.
 // Samples sample0 .. sample0 + n_samples - 1 (n_samples < 65,536) of the range first_tick, first_tick + every, ...: stage 1 writes
 // `partial_stride` records (envelope_plan.hpp: EnvelopePartial) per sample into `partial`, stage 2 merges them in index order into
 // `out`.  The caller has validated the range (sampled_range_ok), n % period == 0 and envelope_supported(w, period).
-hipError_t launch_history_envelope(const EnvelopeArgs& a, uint32_t n_components, double* out, void* partial, uint64_t partial_stride,
+hipError_t launch_history_envelope(const RingBinArgs& a, uint32_t n_components, double* out, void* partial, uint64_t partial_stride,
                                    uint64_t n, uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples,
                                    uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
 
 // ---- ring quantiles: exact order statistics across the rows of every sampled tick (quantile_kernels.hip) ------------------
-constexpr uint32_t kQuantileMaxComponents = 32;   // components one launch covers (blockIdx.z)
-struct QuantileDesc {
-    const void* ring;        // [ring][n, w] blocks of this component
-    uint64_t out_offset;     // where its [n_samples][period][1 + 2 * ranks][w] block starts in `out`, in doubles
-    uint64_t slot_offset;    // where its period * w * ranks (bin, rank) slots of one sample start in a sample's scratch
-    uint32_t w;
-    uint32_t reserved;
-};
-struct QuantileArgs { QuantileDesc c[kQuantileMaxComponents]; };
+// 1 + 2 * ranks planes; a scratch unit is one (bin, rank) slot, period * w * ranks of them per component and sample.
 struct QuantileRanks;   // quantile_plan.hpp
 // Samples sample0 .. sample0 + n_samples - 1 (n_samples < 65,536) of the range first_tick, first_tick + every, ...  Per sample
 // `slot_stride` (bin, rank) slots: `hist` holds 256 uint32 counters per slot, `state` one QuantileSlot (quantile_plan.hpp); both
 // are scratch the launches clear themselves.  The caller has validated the range (sampled_range_ok), the ranks, n % period == 0
 // and envelope_supported(w, period).
-hipError_t launch_history_quantiles(const QuantileArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, void* hist,
+hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, void* hist,
                                     void* state, uint64_t slot_stride, uint64_t n, uint32_t period, uint64_t first_tick,
                                     uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
 

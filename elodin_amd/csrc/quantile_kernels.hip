@@ -75,18 +75,18 @@ struct QuantileBlock {
     uint32_t col0, cols, rb;
     uint64_t slot0;   // the block's first (bin, rank) slot in the launch's scratch
 };
-__device__ __forceinline__ bool quantile_block(const QuantileDesc& d, const QuantileGeom& g, uint32_t ranks, uint64_t slot_stride, QuantileBlock* b) {
+__device__ __forceinline__ bool quantile_block(const RingBinDesc& d, const QuantileGeom& g, uint32_t ranks, uint64_t slot_stride, QuantileBlock* b) {
     if (blockIdx.x >= g.splits * g.row_blocks) return false;   // a component with fewer blocks than the one that sized the grid
     const uint32_t split = blockIdx.x / g.row_blocks;
     b->rb = blockIdx.x % g.row_blocks;
     b->col0 = split * g.cols;
     b->cols = g.bins - b->col0 < g.cols ? g.bins - b->col0 : g.cols;
-    b->slot0 = static_cast<uint64_t>(blockIdx.y) * slot_stride + d.slot_offset + static_cast<uint64_t>(b->col0) * ranks;
+    b->slot0 = static_cast<uint64_t>(blockIdx.y) * slot_stride + d.scratch_offset + static_cast<uint64_t>(b->col0) * ranks;
     return true;
 }
 
 template <class E, int ROUNDS>
-__global__ __launch_bounds__(kQuantileThreads) void quantile_hist_kernel(QuantileArgs a, uint32_t ranks, uint32_t* __restrict__ hist,
+__global__ __launch_bounds__(kQuantileThreads) void quantile_hist_kernel(RingBinArgs a, uint32_t ranks, uint32_t* __restrict__ hist,
                                                                          const QuantileSlot* __restrict__ state, uint64_t slot_stride, uint64_t n,
                                                                          uint32_t period, uint32_t pass, uint64_t first_tick, uint64_t sample0,
                                                                          uint64_t every, uint64_t ring) {
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kQuantileThreads) void quantile_hist_kernel(Quantil
     __shared__ uint32_t s_slot[kQuantileBlockSlots];     //             and the slot that counts each
     __shared__ uint32_t s_distinct[kQuantileBlockSlots];
     __shared__ uint32_t s_most;
-    const QuantileDesc d = a.c[blockIdx.z];
+    const RingBinDesc d = a.c[blockIdx.z];
     const QuantileGeom g = quantile_geom(n, d.w, period, ranks);
     QuantileBlock b;
     if (!quantile_block(d, g, ranks, slot_stride, &b)) return;
@@ -141,15 +141,15 @@ __global__ __launch_bounds__(kQuantileThreads) void quantile_hist_kernel(Quantil
 
 // 16 bins x 16 ranks per block: the ranks of a bin see each other's prefixes as they were before this pass.
 template <class E>
-__global__ __launch_bounds__(256) void quantile_scan_kernel(QuantileArgs a, QuantileRanks ranks, const uint32_t* __restrict__ hist,
+__global__ __launch_bounds__(256) void quantile_scan_kernel(RingBinArgs a, QuantileRanks ranks, const uint32_t* __restrict__ hist,
                                                             QuantileSlot* __restrict__ state, uint64_t slot_stride, uint64_t n, uint32_t period,
                                                             uint32_t pass) {
     __shared__ uint64_t s_old[16][kQuantileMaxRanks];
-    const QuantileDesc d = a.c[blockIdx.z];
+    const RingBinDesc d = a.c[blockIdx.z];
     const uint32_t bins = envelope_geom(n, d.w, period).bins;
     const uint32_t r = threadIdx.x % kQuantileMaxRanks, local = threadIdx.x / kQuantileMaxRanks, bin = blockIdx.x * 16 + local;
     const bool mine = bin < bins && r < ranks.count;
-    const uint64_t slot0 = static_cast<uint64_t>(blockIdx.y) * slot_stride + d.slot_offset + static_cast<uint64_t>(bin) * ranks.count;
+    const uint64_t slot0 = static_cast<uint64_t>(blockIdx.y) * slot_stride + d.scratch_offset + static_cast<uint64_t>(bin) * ranks.count;
     QuantileSlot s{};
     if (mine && pass > 0) s = state[slot0 + r];
     s_old[local][r] = s.prefix;
@@ -166,14 +166,14 @@ __global__ __launch_bounds__(256) void quantile_scan_kernel(QuantileArgs a, Quan
 constexpr uint64_t kQuantileNoKey = ~uint64_t(0);   // above every finite key: what the cleared (all ones) scratch reads as
 
 template <class E>
-__global__ __launch_bounds__(kQuantileThreads) void quantile_next_kernel(QuantileArgs a, uint32_t ranks, uint64_t* __restrict__ next,
+__global__ __launch_bounds__(kQuantileThreads) void quantile_next_kernel(RingBinArgs a, uint32_t ranks, uint64_t* __restrict__ next,
                                                                          const QuantileSlot* __restrict__ state, uint64_t slot_stride, uint64_t n,
                                                                          uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t every,
                                                                          uint64_t ring) {
     using B = QuantileBits<E>;
     __shared__ uint64_t s_above[kQuantileBlockSlots];   // the key of x(lo), or no key where x(hi) needs no search
     __shared__ uint64_t s_min[kQuantileBlockSlots];
-    const QuantileDesc d = a.c[blockIdx.z];
+    const RingBinDesc d = a.c[blockIdx.z];
     const QuantileGeom g = quantile_geom(n, d.w, period, ranks);
     QuantileBlock b;
     if (!quantile_block(d, g, ranks, slot_stride, &b)) return;
@@ -200,14 +200,14 @@ __global__ __launch_bounds__(kQuantileThreads) void quantile_next_kernel(Quantil
 }
 
 template <class E>
-__global__ __launch_bounds__(256) void quantile_emit_kernel(QuantileArgs a, uint32_t ranks, const uint64_t* __restrict__ next,
+__global__ __launch_bounds__(256) void quantile_emit_kernel(RingBinArgs a, uint32_t ranks, const uint64_t* __restrict__ next,
                                                             const QuantileSlot* __restrict__ state, uint64_t slot_stride, double* __restrict__ out,
                                                             uint64_t n, uint32_t period, uint64_t sample0) {
-    const QuantileDesc d = a.c[blockIdx.z];
+    const RingBinDesc d = a.c[blockIdx.z];
     const uint32_t bins = envelope_geom(n, d.w, period).bins;
     const uint32_t r = threadIdx.x % kQuantileMaxRanks, bin = blockIdx.x * 16 + threadIdx.x / kQuantileMaxRanks;
     if (bin >= bins || r >= ranks) return;
-    const uint64_t slot = static_cast<uint64_t>(blockIdx.y) * slot_stride + d.slot_offset + static_cast<uint64_t>(bin) * ranks + r;
+    const uint64_t slot = static_cast<uint64_t>(blockIdx.y) * slot_stride + d.scratch_offset + static_cast<uint64_t>(bin) * ranks + r;
     const uint64_t group = bin / d.w, c = bin % d.w, sample = sample0 + blockIdx.y, planes = 1 + 2 * static_cast<uint64_t>(ranks);
     quantile_emit<E>(state[slot], next[slot * (kQuantileDigits / 2)], r, out + d.out_offset + ((sample * period + group) * planes) * d.w + c, d.w);
 }
@@ -223,7 +223,7 @@ static int quantile_rounds() {
 }
 
 template <class E>
-static hipError_t quantile_launches(const QuantileArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, uint32_t* hist,
+static hipError_t quantile_launches(const RingBinArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, uint32_t* hist,
                                     QuantileSlot* state, uint64_t slot_stride, uint64_t n, uint32_t period, uint64_t first_tick,
                                     uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, uint32_t blocks, uint32_t bins,
                                     hipStream_t s) {
@@ -246,12 +246,10 @@ static hipError_t quantile_launches(const QuantileArgs& a, uint32_t n_components
     return hipGetLastError();
 }
 
-hipError_t launch_history_quantiles(const QuantileArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, void* hist,
+hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, void* hist,
                                     void* state, uint64_t slot_stride, uint64_t n, uint32_t period, uint64_t first_tick,
                                     uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
-    if (n_components == 0 || n_components > kQuantileMaxComponents || n_samples > 65535 || period == 0 || n % period != 0 || (n / period) >> 32 ||
-        ranks.count == 0 || ranks.count > kQuantileMaxRanks || ranks.den == 0)
-        return hipErrorInvalidValue;
+    if (!quantile_launch_ok(n_components, kRingBinMaxComponents, ranks, n, n_samples, period)) return hipErrorInvalidValue;
     if (n_samples == 0 || n == 0) return hipSuccess;
     uint32_t blocks = 0, bins = 0;
     for (uint32_t k = 0; k < n_components; k++) {

@@ -62,6 +62,12 @@ struct QuantileRanks {   // by value into the kernels
     uint32_t num[kQuantileMaxRanks];
     uint32_t den, count;
 };
+// What launch_history_quantiles accepts, for the launcher (quantile_kernels.hip) and its host twin (hip_fake.cpp) alike: the
+// envelope's limits, whole groups whose rows a 32-bit counter holds, 1 to 16 ranks over a denominator.
+inline bool quantile_launch_ok(uint32_t n_components, uint32_t max_components, const QuantileRanks& ranks, uint64_t n, uint64_t n_samples, uint32_t period) {
+    return envelope_launch_ok(n_components, max_components, n_samples, period) && n % period == 0 && !((n / period) >> 32) && ranks.count != 0 &&
+           ranks.count <= kQuantileMaxRanks && ranks.den != 0;
+}
 struct QuantileIndex { uint64_t lo, hi; };
 // floor and ceiling of num * (m - 1) / den, m >= 1: num <= den < 2^32 and m <= 2^32, so the product stays below 2^64
 SIXDOF_HOST_DEVICE inline QuantileIndex quantile_index(uint32_t num, uint32_t den, uint64_t m) {

@@ -1392,9 +1392,9 @@ int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_c
 } SIXDOF_ABI_CATCH(err_of(h))
 
 // A read whose results are computed on the compute stream, out of the ring into a device staging buffer, and brought from
-// there to the caller's buffers, blocking or over the copy lane: sixdof_watch_read and sixdof_history_envelope.  The lane
-// and the rules of the staging buffer live here and nowhere in the callers: add() the components, claim() the buffers,
-// launch into them, deliver().
+// there to the caller's buffers, blocking or over the copy lane: sixdof_watch_read and, through ring_bin_read below,
+// sixdof_history_envelope and sixdof_history_quantiles.  The lane and the rules of the staging buffer live here and nowhere
+// in the callers: add() the components, claim() the buffers, launch into them, deliver().
 struct StagedRead {
     // one component: ring base and width as they are NOW, its block in the staging buffer (256-byte aligned), where it goes
     struct Part { const void* ring; size_t w, bytes, offset; void* host; };
@@ -1491,147 +1491,140 @@ int sixdof_watch_read(sixdof_handle* h, uint64_t first_tick, uint64_t n_samples,
     return rd.deliver((flags & SIXDOF_WATCH_ASYNC) != 0);
 } SIXDOF_ABI_CATCH(err_of(h))
 
-// The envelopes of sampled ticks: ordering, ring reads and the copy lane exactly as for sixdof_watch_read above — the two
-// reduction launches go on the compute stream behind the batch that recorded the ticks, only the staging buffer is read from
-// the copy stream.  Stateless: components and widths are looked up per call.
-int sixdof_history_envelope(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
-                            uint64_t n_samples, uint64_t every, uint32_t period, double* const host_dst[], uint32_t flags) try {
-    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
-    if (flags & ~SIXDOF_ENVELOPE_ASYNC) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: unknown flags");
-    if (!h->hist.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: no history ring (sixdof_set_history)");
-    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: every must be at least 1");
-    if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: period must be at least 1");
+}  // extern "C"
+
+// A per-tick reduction of ring components into (group, element) bins: sixdof_history_envelope and sixdof_history_quantiles.
+// Ordering, ring reads and the copy lane exactly as for sixdof_watch_read above — the reduction's launches go on the compute
+// stream behind the batch that recorded the ticks, only the staging buffer is read from the copy stream.  Stateless: components
+// and widths are looked up per call.  What a reduction is:
+struct RingBinSpec {
+    const char* who;          // the entry point, for its messages
+    uint32_t async_flag;      // the one flag it knows
+    size_t planes;            // doubles per bin in the output
+    size_t unit_bytes;        // scratch bytes per unit and sample
+    const char* bins_limit;   // how its message ends when period x width exceeds kEnvelopeMaxBins
+    bool rows_in_32_bits;     // its kernels count the rows of a group in 32 bits
+    DeviceBuffer *stage, *scratch;
+};
+// Refuses, plans, launches and delivers.  own_checks() -> status: the entry point's own argument checks, in their place after
+// the common four.  units(n, w, period): scratch units of one component and sample.  launch(args, count, stride, chunk, sample0,
+// n_samples) -> hipError_t: one batch of at most kRingBinMaxComponents components x one chunk of samples; `stride` units of
+// scratch per sample, `chunk` samples per launch (the last may be shorter) as the scratch buffer was sized.
+template <class Checks, class Units, class Launch>
+static int ring_bin_read(sixdof_handle* h, const RingBinSpec& spec, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
+                         uint64_t n_samples, uint64_t every, uint32_t period, double* const host_dst[], uint32_t flags, Checks own_checks,
+                         Units units, Launch launch) {
+    const std::string who = spec.who;
+    if (flags & ~spec.async_flag) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": unknown flags");
+    if (!h->hist.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": no history ring (sixdof_set_history)");
+    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": every must be at least 1");
+    if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
+    if (int rc = own_checks(); rc != SIXDOF_OK) return rc;
     const uint64_t n = h->desc.n_entities;
     if (n % period != 0)
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+    if (spec.rows_in_32_bits && (n / period) >> 32) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": more than 2^32 rows in a group");
     if (n_samples == 0 || n_components == 0) return SIXDOF_OK;
-    if (!component_ids || !host_dst) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: null argument");
+    if (!component_ids || !host_dst) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
     if (!sampled_range_ok(first_tick, n_samples, every, h->hist.first_tick, h->tick, h->hist.ring))
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: ticks are not (all) in the ring");
-    History& hs = h->hist;
-    StagedRead rd{h, "history_envelope", &hs.env_stage};
-    std::vector<size_t> partial_offset(n_components);   // per component: its records in a sample's partials
-    size_t partial_stride = 0, launch_records = 0;
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": ticks are not (all) in the ring");
+    StagedRead rd{h, spec.who, spec.stage};
+    std::vector<size_t> scratch_offset(n_components);   // per component: its units in a sample's scratch
+    size_t stride = 0, launch_units = 0;
     for (size_t k = 0; k < n_components; k++) {
-        const int rc = rd.add(component_ids[k], host_dst[k], static_cast<size_t>(n_samples) * period * kEnvelopeStats, sizeof(double),
+        const int rc = rd.add(component_ids[k], host_dst[k], static_cast<size_t>(n_samples) * period * spec.planes, sizeof(double),
                               "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
         if (rc != SIXDOF_OK) return rc;
         const size_t w = rd.parts[k].w;
         if (!envelope_supported(w, period))
-            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_envelope: period " + std::to_string(period) + " x width " + std::to_string(w) +
-                                                            " exceeds the " + std::to_string(kEnvelopeMaxBins) + " (group, element) bins one block keeps apart");
-        const EnvelopeGeom g = envelope_geom(n, static_cast<uint32_t>(w), period);
-        if (k % kEnvelopeMaxComponents == 0) launch_records = 0;   // every launch of at most 32 components reuses the records
-        partial_offset[k] = launch_records;
-        launch_records += static_cast<size_t>(g.blocks) * g.bins;
-        partial_stride = std::max(partial_stride, launch_records);
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period " + std::to_string(period) + " x width " + std::to_string(w) + " exceeds the " +
+                                                            std::to_string(kEnvelopeMaxBins) + " (group, element) bins " + spec.bins_limit);
+        if (k % kRingBinMaxComponents == 0) launch_units = 0;   // every launch of at most 32 components reuses the scratch
+        scratch_offset[k] = launch_units;
+        launch_units += units(n, static_cast<uint32_t>(w), period);
+        stride = std::max(stride, launch_units);
     }
-    if (n == 0) {      // nothing to reduce: count 0, statistics NaN
+    if (n == 0) {      // nothing to reduce: count 0, the other planes NaN
         for (size_t k = 0; k < n_components; k++)
-            for (size_t i = 0; i < rd.parts[k].bytes / sizeof(double); i++) host_dst[k][i] = i / rd.parts[k].w % kEnvelopeStats == 0 ? 0.0 : std::nan("");
+            for (size_t i = 0; i < rd.parts[k].bytes / sizeof(double); i++) host_dst[k][i] = i / rd.parts[k].w % spec.planes == 0 ? 0.0 : std::nan("");
         return SIXDOF_OK;
     }
-    // samples per launch: the partial records of one launch stay within a fixed budget, and the grid's y extent below 2^16
-    constexpr size_t kPartialBudget = size_t(64) << 20;
-    const size_t per_sample = partial_stride * sizeof(EnvelopePartial);
-    const uint64_t chunk = std::min<uint64_t>({n_samples, 65535, std::max<size_t>(1, kPartialBudget / per_sample)});
+    // samples per launch: the scratch of one launch stays within a fixed budget, and the grid's y extent below 2^16
+    constexpr size_t kScratchBudget = size_t(64) << 20;
+    const size_t per_sample = stride * spec.unit_bytes;
+    const uint64_t chunk = std::min<uint64_t>({n_samples, 65535, std::max<size_t>(1, kScratchBudget / per_sample)});
     HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = rd.claim(&hs.env_partial, chunk * per_sample); rc != SIXDOF_OK) return rc;
-    for (size_t k0 = 0; k0 < n_components; k0 += kEnvelopeMaxComponents) {
-        const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kEnvelopeMaxComponents, n_components - k0));
-        EnvelopeArgs a{};
+    if (int rc = rd.claim(spec.scratch, chunk * per_sample); rc != SIXDOF_OK) return rc;
+    for (size_t k0 = 0; k0 < n_components; k0 += kRingBinMaxComponents) {
+        const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_components - k0));
+        RingBinArgs a{};
         for (uint32_t k = 0; k < cnt; k++) {
             a.c[k].ring = rd.parts[k0 + k].ring;
             a.c[k].out_offset = rd.parts[k0 + k].offset / sizeof(double);
-            a.c[k].partial_offset = partial_offset[k0 + k];
+            a.c[k].scratch_offset = scratch_offset[k0 + k];
             a.c[k].w = static_cast<uint32_t>(rd.parts[k0 + k].w);
         }
         for (uint64_t s0 = 0; s0 < n_samples; s0 += chunk) {
-            hipError_t e = launch_history_envelope(a, cnt, hs.env_stage.get<double>(), hs.env_partial.get(), partial_stride, n, period, first_tick, s0,
-                                                   std::min<uint64_t>(chunk, n_samples - s0), every, hs.ring, h->elem_size(), h->stream.get());
-            if (e != hipSuccess) return h->hip_fail(e, "history_envelope");
+            hipError_t e = launch(a, cnt, stride, chunk, s0, std::min<uint64_t>(chunk, n_samples - s0));
+            if (e != hipSuccess) return h->hip_fail(e, spec.who);
         }
     }
-    return rd.deliver((flags & SIXDOF_ENVELOPE_ASYNC) != 0);
+    return rd.deliver((flags & spec.async_flag) != 0);
+}
+
+extern "C" {
+
+// The envelopes of sampled ticks: two reduction launches per batch and chunk, a scratch unit is one partial record.
+int sixdof_history_envelope(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
+                            uint64_t n_samples, uint64_t every, uint32_t period, double* const host_dst[], uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    History& hs = h->hist;
+    const RingBinSpec spec{"history_envelope", SIXDOF_ENVELOPE_ASYNC, kEnvelopeStats, sizeof(EnvelopePartial), "one block keeps apart", false,
+                           &hs.env_stage, &hs.env_partial};
+    return ring_bin_read(
+        h, spec, component_ids, n_components, first_tick, n_samples, every, period, host_dst, flags, [] { return int(SIXDOF_OK); },
+        [](uint64_t n, uint32_t w, uint32_t p) {
+            const EnvelopeGeom g = envelope_geom(n, w, p);
+            return static_cast<size_t>(g.blocks) * g.bins;
+        },
+        [&](const RingBinArgs& a, uint32_t cnt, size_t stride, uint64_t, uint64_t s0, uint64_t ns) {
+            return launch_history_envelope(a, cnt, hs.env_stage.get<double>(), hs.env_partial.get(), stride, h->desc.n_entities, period, first_tick, s0, ns,
+                                           every, hs.ring, h->elem_size(), h->stream.get());
+        });
 } SIXDOF_ABI_CATCH(err_of(h))
 
-// Exact order statistics of sampled ticks: the third staged reader, with the envelope's ordering, ring reads, copy lane and
-// limits — the passes of the radix select go on the compute stream behind the batch that recorded the ticks, only the staging
-// buffer is read from the copy stream.  Stateless.
+// Exact order statistics of sampled ticks: the passes of a radix select per batch and chunk, a scratch unit is one (bin, rank)
+// slot — its histogram and, behind the histograms of a whole chunk, its state.
 int sixdof_history_quantiles(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
                              uint64_t n_samples, uint64_t every, uint32_t period, const uint32_t* rank_num, uint32_t rank_den,
                              size_t n_ranks, double* const host_dst[], uint32_t flags) try {
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
-    if (flags & ~SIXDOF_QUANTILE_ASYNC) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: unknown flags");
-    if (!h->hist.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: no history ring (sixdof_set_history)");
-    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: every must be at least 1");
-    if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: period must be at least 1");
-    if (n_ranks == 0 || n_ranks > SIXDOF_QUANTILE_MAX_RANKS)
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: " + std::to_string(n_ranks) + " ranks, 1 to " + std::to_string(SIXDOF_QUANTILE_MAX_RANKS) + " can be asked for");
-    if (!rank_num) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: null ranks");
-    if (rank_den == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: the ranks' denominator must be at least 1");
-    QuantileRanks ranks{};
-    ranks.den = rank_den, ranks.count = static_cast<uint32_t>(n_ranks);
-    for (size_t i = 0; i < n_ranks; i++) {
-        if (rank_num[i] > rank_den)
-            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: rank " + std::to_string(rank_num[i]) + " / " + std::to_string(rank_den) + " is above 1");
-        ranks.num[i] = rank_num[i];
-    }
-    const uint64_t n = h->desc.n_entities;
-    if (n % period != 0)
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
-    if ((n / period) >> 32) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: more than 2^32 rows in a group");
-    if (n_samples == 0 || n_components == 0) return SIXDOF_OK;
-    if (!component_ids || !host_dst) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: null argument");
-    if (!sampled_range_ok(first_tick, n_samples, every, h->hist.first_tick, h->tick, h->hist.ring))
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: ticks are not (all) in the ring");
     History& hs = h->hist;
-    StagedRead rd{h, "history_quantiles", &hs.quant_stage};
-    const size_t planes = 1 + 2 * n_ranks;
-    std::vector<size_t> slot_offset(n_components);   // per component: its (bin, rank) slots in a sample's scratch
-    size_t slot_stride = 0, launch_slots = 0;
-    for (size_t k = 0; k < n_components; k++) {
-        const int rc = rd.add(component_ids[k], host_dst[k], static_cast<size_t>(n_samples) * period * planes, sizeof(double),
-                              "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
-        if (rc != SIXDOF_OK) return rc;
-        const size_t w = rd.parts[k].w;
-        if (!envelope_supported(w, period))
-            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: period " + std::to_string(period) + " x width " + std::to_string(w) +
-                                                            " exceeds the " + std::to_string(kEnvelopeMaxBins) + " (group, element) bins of one read");
-        if (k % kQuantileMaxComponents == 0) launch_slots = 0;   // every launch of at most 32 components reuses the scratch
-        slot_offset[k] = launch_slots;
-        launch_slots += static_cast<size_t>(period) * w * n_ranks;
-        slot_stride = std::max(slot_stride, launch_slots);
-    }
-    if (n == 0) {      // nothing to select from: count 0, order statistics NaN
-        for (size_t k = 0; k < n_components; k++)
-            for (size_t i = 0; i < rd.parts[k].bytes / sizeof(double); i++) host_dst[k][i] = i / rd.parts[k].w % planes == 0 ? 0.0 : std::nan("");
-        return SIXDOF_OK;
-    }
-    // samples per launch: the histograms and states of one launch stay within a fixed budget, and the grid's y extent below 2^16
-    constexpr size_t kScratchBudget = size_t(64) << 20;
-    const size_t hist_per_sample = slot_stride * kQuantileDigits * sizeof(uint32_t), per_sample = hist_per_sample + slot_stride * sizeof(QuantileSlot);
-    const uint64_t chunk = std::min<uint64_t>({n_samples, 65535, std::max<size_t>(1, kScratchBudget / per_sample)});
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (int rc = rd.claim(&hs.quant_scratch, chunk * per_sample); rc != SIXDOF_OK) return rc;
-    char* scratch = hs.quant_scratch.get<char>();
-    for (size_t k0 = 0; k0 < n_components; k0 += kQuantileMaxComponents) {
-        const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kQuantileMaxComponents, n_components - k0));
-        QuantileArgs a{};
-        for (uint32_t k = 0; k < cnt; k++) {
-            a.c[k].ring = rd.parts[k0 + k].ring;
-            a.c[k].out_offset = rd.parts[k0 + k].offset / sizeof(double);
-            a.c[k].slot_offset = slot_offset[k0 + k];
-            a.c[k].w = static_cast<uint32_t>(rd.parts[k0 + k].w);
+    QuantileRanks ranks{};
+    auto rank_checks = [&] {
+        if (n_ranks == 0 || n_ranks > SIXDOF_QUANTILE_MAX_RANKS)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: " + std::to_string(n_ranks) + " ranks, 1 to " + std::to_string(SIXDOF_QUANTILE_MAX_RANKS) + " can be asked for");
+        if (!rank_num) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: null ranks");
+        if (rank_den == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: the ranks' denominator must be at least 1");
+        ranks.den = rank_den, ranks.count = static_cast<uint32_t>(n_ranks);
+        for (size_t i = 0; i < n_ranks; i++) {
+            if (rank_num[i] > rank_den)
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_quantiles: rank " + std::to_string(rank_num[i]) + " / " + std::to_string(rank_den) + " is above 1");
+            ranks.num[i] = rank_num[i];
         }
-        for (uint64_t s0 = 0; s0 < n_samples; s0 += chunk) {   // histograms first, the states behind those of a whole chunk
-            hipError_t e = launch_history_quantiles(a, cnt, ranks, hs.quant_stage.get<double>(), scratch, scratch + chunk * hist_per_sample, slot_stride, n,
-                                                    period, first_tick, s0, std::min<uint64_t>(chunk, n_samples - s0), every, hs.ring, h->elem_size(),
-                                                    h->stream.get());
-            if (e != hipSuccess) return h->hip_fail(e, "history_quantiles");
-        }
-    }
-    return rd.deliver((flags & SIXDOF_QUANTILE_ASYNC) != 0);
+        return int(SIXDOF_OK);
+    };
+    constexpr size_t kHistBytes = kQuantileDigits * sizeof(uint32_t);
+    const RingBinSpec spec{"history_quantiles", SIXDOF_QUANTILE_ASYNC, 1 + 2 * n_ranks, kHistBytes + sizeof(QuantileSlot), "of one read", true,
+                           &hs.quant_stage, &hs.quant_scratch};
+    return ring_bin_read(
+        h, spec, component_ids, n_components, first_tick, n_samples, every, period, host_dst, flags, rank_checks,
+        [&](uint64_t, uint32_t w, uint32_t p) { return static_cast<size_t>(p) * w * n_ranks; },
+        [&](const RingBinArgs& a, uint32_t cnt, size_t stride, uint64_t chunk, uint64_t s0, uint64_t ns) {
+            char* scratch = hs.quant_scratch.get<char>();
+            return launch_history_quantiles(a, cnt, ranks, hs.quant_stage.get<double>(), scratch, scratch + chunk * stride * kHistBytes, stride,
+                                            h->desc.n_entities, period, first_tick, s0, ns, every, hs.ring, h->elem_size(), h->stream.get());
+        });
 } SIXDOF_ABI_CATCH(err_of(h))
 
 int sixdof_download_column(sixdof_handle* h, uint64_t component_id) try {

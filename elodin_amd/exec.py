@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Callable, Optional, Sequence
 
 import os
 from pathlib import Path
@@ -49,6 +49,16 @@ class TickTimings:  # profile.rs TickTimings
     ticks: int = 0
     kernel_sum_ms: float = 0.0
     graph_launches: int = 0    # how many of `launches` were replayed from a captured hipGraph
+
+
+@dataclass(frozen=True)
+class _Reduction:
+    """One reduction over the ring into (group, element) bins, as HipExec._reduce and _stream_reduce call it."""
+    fn: str                 # the library entry point
+    async_flag: int
+    planes: int             # doubles per bin in a raw block [samples, period, planes, w]
+    extra: tuple            # its ctypes arguments between `period` and the buffers
+    to_dict: Callable       # (names, raw blocks) -> the dict handed to the caller
 
 
 class HipExec:
@@ -531,13 +541,11 @@ class HipExec:
         seconds.  (The ring size is the one enable_history was last called with: after a stream_history, which sizes its own
         ring, call enable_history again.)"""
         n_batches, ticks_per_batch, every = int(n_batches), int(ticks_per_batch), int(every)
-        if every < 1 or ticks_per_batch < 1 or ticks_per_batch % every != 0:
-            raise ValueError(f"stream_series: ticks_per_batch ({ticks_per_batch}) must be a positive multiple of every ({every})")
+        n_samples = self._stream_shape("stream_series", ticks_per_batch, every)
         if not getattr(self, "_watch", ((), 0))[0]:
             raise ValueError("stream_series: no watch (set_watch)")
         if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
             self.enable_history(ticks_per_batch)
-        n_samples = ticks_per_batch // every
         bufs, ptrs = zip(*[self._series_buffers(n_samples) for _ in range(2)])
 
         def read(first_tick, k):
@@ -547,14 +555,61 @@ class HipExec:
         self.sync()              # nothing of an earlier streaming run is in flight
         return self._stream_batches(n_batches, ticks_per_batch, every, read, lambda k: bufs[k], consume, flags)   # samples end on the batch's last tick
 
+    # ---- reductions over the ring into (group, element) bins: envelopes and quantiles -----------------------------------
+    def _envelope_reduction(self) -> _Reduction:
+        return _Reduction("sixdof_history_envelope", L.ENVELOPE_ASYNC, 5, (), self._envelope_dict)
+
+    def _quantile_reduction(self, q) -> _Reduction:
+        num, den = self.quantile_ranks(q)
+        return _Reduction("sixdof_history_quantiles", L.QUANTILE_ASYNC, 1 + 2 * len(num), ((C.c_uint32 * len(num))(*num), den, len(num)),
+                          lambda names, raw: self._quantile_dict(names, raw, num, den))
+
+    @staticmethod
+    def _stream_shape(who: str, ticks_per_batch: int, every: int) -> int:
+        """Samples per batch of a stream_* call, or its ValueError."""
+        if every < 1 or ticks_per_batch < 1 or ticks_per_batch % every != 0:
+            raise ValueError(f"{who}: ticks_per_batch ({ticks_per_batch}) must be a positive multiple of every ({every})")
+        return ticks_per_batch // every
+
+    def _reduce_buffers(self, red: _Reduction, names, n_samples: int, period: int):
+        raw = [np.empty((n_samples, max(period, 1), red.planes, self._recorded_width(name)), dtype=np.float64) for name in names]
+        return raw, (C.c_void_p * max(1, len(names)))(*[a.ctypes.data for a in raw])
+
+    def _reduce_read(self, red: _Reduction, comp, first_tick: int, n_samples: int, every: int, period: int, ptrs, flags: int) -> None:
+        rc = getattr(self._lib, red.fn)(self._h, comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), first_tick, n_samples, every, period,
+                                        *red.extra, ptrs, flags)
+        if rc != L.OK:
+            _raise(self._h, rc, red.fn)
+
+    def _reduce(self, red: _Reduction, names, first_tick: int, last_tick: int, every: int, period: int) -> dict:
+        """One blocking read of the samples first_tick, first_tick + every, ... <= last_tick."""
+        names = [names] if isinstance(names, str) else list(names)
+        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
+        n_samples = self._sample_count(first_tick, last_tick, every)
+        raw, ptrs = self._reduce_buffers(red, names, n_samples, period)
+        comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
+        self._reduce_read(red, comp, first_tick, n_samples, every, max(period, 0), ptrs, 0)
+        return red.to_dict(names, raw)
+
+    def _stream_reduce(self, who: str, red: _Reduction, names, n_batches: int, ticks_per_batch: int, every: int, period: int, consume,
+                       flags: int) -> float:
+        """Every batch's samples read asynchronously into one of two host buffer sets while the next batch computes."""
+        names = [names] if isinstance(names, str) else list(names)
+        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
+        n_samples = self._stream_shape(who, ticks_per_batch, every)
+        if period < 1:
+            raise ValueError(f"{who}: period must be at least 1")
+        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
+            self.enable_history(ticks_per_batch)
+        raw, ptrs = zip(*[self._reduce_buffers(red, names, n_samples, period) for _ in range(2)])
+        comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
+        self.sync()              # nothing of an earlier streaming run is in flight
+        return self._stream_batches(n_batches, ticks_per_batch, every,
+                                    lambda first_tick, k: self._reduce_read(red, comp, first_tick, n_samples, every, period, ptrs[k], red.async_flag),
+                                    lambda k: red.to_dict(names, raw[k]), consume, flags)
+
     # ---- ring envelopes: count / min / max / mean / spread across the rows of every sampled tick -------------------
     ENVELOPE_STATS = ("count", "min", "max", "mean", "m2")
-
-    def _envelope_buffers(self, names, n_samples: int, period: int):
-        raw = [np.empty((n_samples, max(period, 1), 5, self._recorded_width(name)), dtype=np.float64) for name in names]
-        ptrs = (C.c_void_p * max(1, len(names)))(*[a.ctypes.data for a in raw])
-        comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
-        return raw, ptrs, comp
 
     @classmethod
     def _envelope_dict(cls, names, raw) -> dict:
@@ -574,15 +629,7 @@ class HipExec:
         of the rows r with r % period == g (period = 1: all rows).  Non-finite elements are skipped and show as count below
         n / period; count == 0 leaves the statistics NaN.  Accumulated in f64; m2 is the sum of squared deviations from the mean
         and std = sqrt(m2 / count).  Stateless: no watch is involved."""
-        names = [names] if isinstance(names, str) else list(names)
-        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
-        n_samples = self._sample_count(first_tick, last_tick, every)
-        raw, ptrs, comp = self._envelope_buffers(names, n_samples, period)
-        rc = self._lib.sixdof_history_envelope(self._h, comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), first_tick, n_samples, every,
-                                               max(period, 0), ptrs, 0)
-        if rc != L.OK:
-            _raise(self._h, rc, "sixdof_history_envelope")
-        return self._envelope_dict(names, raw)
+        return self._reduce(self._envelope_reduction(), names, first_tick, last_tick, every, period)
 
     def stream_envelope(self, names: Sequence[str], n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, consume=None,
                         flags: int = 0) -> float:
@@ -591,24 +638,7 @@ class HipExec:
         unless enable_history already made one at least that large).  `consume(batch_index, first_tick, {name: {statistic:
         [ticks_per_batch // every, period, w]}})` sees a batch once it has landed — first_tick is the batch's first SAMPLED
         tick; the arrays are views of buffers reused two batches later.  Returns the wall time in seconds."""
-        names = [names] if isinstance(names, str) else list(names)
-        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
-        if every < 1 or ticks_per_batch < 1 or ticks_per_batch % every != 0:
-            raise ValueError(f"stream_envelope: ticks_per_batch ({ticks_per_batch}) must be a positive multiple of every ({every})")
-        if period < 1:
-            raise ValueError("stream_envelope: period must be at least 1")
-        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
-            self.enable_history(ticks_per_batch)
-        n_samples = ticks_per_batch // every
-        raw, ptrs, comps = zip(*[self._envelope_buffers(names, n_samples, period) for _ in range(2)])
-        comp_p = comps[0].ctypes.data_as(C.POINTER(C.c_uint64))
-
-        def read(first_tick, k):
-            rc = self._lib.sixdof_history_envelope(self._h, comp_p, len(names), first_tick, n_samples, every, period, ptrs[k], L.ENVELOPE_ASYNC)
-            if rc != L.OK:
-                _raise(self._h, rc, "sixdof_history_envelope")
-        self.sync()              # nothing of an earlier streaming run is in flight
-        return self._stream_batches(n_batches, ticks_per_batch, every, read, lambda k: self._envelope_dict(names, raw[k]), consume, flags)
+        return self._stream_reduce("stream_envelope", self._envelope_reduction(), names, n_batches, ticks_per_batch, every, period, consume, flags)
 
     # ---- ring quantiles: exact order statistics across the rows of every sampled tick ---------------------------------
     @staticmethod
@@ -645,12 +675,6 @@ class HipExec:
             raise ValueError(f"quantiles: the ranks' common denominator {den} does not fit 32 bits")
         return [int(f * den) for f in fr], den
 
-    def _quantile_buffers(self, names, n_samples: int, period: int, n_ranks: int):
-        raw = [np.empty((n_samples, max(period, 1), 1 + 2 * n_ranks, self._recorded_width(name)), dtype=np.float64) for name in names]
-        ptrs = (C.c_void_p * max(1, len(names)))(*[a.ctypes.data for a in raw])
-        comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
-        return raw, ptrs, comp
-
     @staticmethod
     def _quantile_dict(names, raw, num, den) -> dict:
         """[s, period, 1 + 2Q, w] blocks -> {name: {"count": int64 [s, period, w], "lower", "upper", "linear": [s, period, Q, w]}}.
@@ -676,17 +700,7 @@ class HipExec:
         are skipped), lower = x(floor(q (m-1))) and upper = x(ceil(q (m-1))), rank arithmetic in integers: both are elements
         of the ring, bit for bit (-0.0 below +0.0).  linear = lower + (upper - lower) * frac, frac = (num (m-1) mod den) / den in
         f64 on the host.  count == 0 leaves the three NaN.  Stateless: no watch is involved."""
-        names = [names] if isinstance(names, str) else list(names)
-        num, den = self.quantile_ranks(q)
-        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
-        n_samples = self._sample_count(first_tick, last_tick, every)
-        raw, ptrs, comp = self._quantile_buffers(names, n_samples, period, len(num))
-        nums = (C.c_uint32 * len(num))(*num)
-        rc = self._lib.sixdof_history_quantiles(self._h, comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), first_tick, n_samples, every,
-                                                max(period, 0), nums, den, len(num), ptrs, 0)
-        if rc != L.OK:
-            _raise(self._h, rc, "sixdof_history_quantiles")
-        return self._quantile_dict(names, raw, num, den)
+        return self._reduce(self._quantile_reduction(q), names, first_tick, last_tick, every, period)
 
     def stream_quantiles(self, names: Sequence[str], n_batches: int, ticks_per_batch: int, q, every: int = 1, period: int = 1, consume=None,
                          flags: int = 0) -> float:
@@ -695,27 +709,7 @@ class HipExec:
         here unless enable_history already made one at least that large).  `consume(batch_index, first_tick, {name: {"count",
         "lower", "upper", "linear"}})` sees a batch once it has landed — first_tick is the batch's first SAMPLED tick; lower and
         upper are views of buffers reused two batches later.  Returns the wall time in seconds."""
-        names = [names] if isinstance(names, str) else list(names)
-        num, den = self.quantile_ranks(q)
-        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
-        if every < 1 or ticks_per_batch < 1 or ticks_per_batch % every != 0:
-            raise ValueError(f"stream_quantiles: ticks_per_batch ({ticks_per_batch}) must be a positive multiple of every ({every})")
-        if period < 1:
-            raise ValueError("stream_quantiles: period must be at least 1")
-        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
-            self.enable_history(ticks_per_batch)
-        n_samples = ticks_per_batch // every
-        raw, ptrs, comps = zip(*[self._quantile_buffers(names, n_samples, period, len(num)) for _ in range(2)])
-        comp_p = comps[0].ctypes.data_as(C.POINTER(C.c_uint64))
-        nums = (C.c_uint32 * len(num))(*num)
-
-        def read(first_tick, k):
-            rc = self._lib.sixdof_history_quantiles(self._h, comp_p, len(names), first_tick, n_samples, every, period, nums, den, len(num), ptrs[k],
-                                                    L.QUANTILE_ASYNC)
-            if rc != L.OK:
-                _raise(self._h, rc, "sixdof_history_quantiles")
-        self.sync()              # nothing of an earlier streaming run is in flight
-        return self._stream_batches(n_batches, ticks_per_batch, every, read, lambda k: self._quantile_dict(names, raw[k], num, den), consume, flags)
+        return self._stream_reduce("stream_quantiles", self._quantile_reduction(q), names, n_batches, ticks_per_batch, every, period, consume, flags)
 
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))

@@ -288,6 +288,23 @@ def test_a_tick_reads_the_same_bits_however_it_is_read():
     hip.close()
 
 
+def test_more_components_than_one_launch_covers():
+    """34 component ids — the four fields cycled — cross the 32 components of one launch: the second launch reuses the scratch
+    offsets of the first.  Every buffer is, byte for byte, the same field's buffer of a four-id read of the same two samples."""
+    hip, _ = _exec(65, 4)
+    hip.enable_history(4)
+    hip.run(4)
+    num, den = hip.quantile_ranks([0.01, 0.5, 0.99])
+    names = [FIELDS[k % 4] for k in range(34)]
+    block = lambda c, fill: np.full((2, 5, 7, _width(c)), fill)
+    many, four = [block(c, -7.0) for c in names], [block(c, -9.0) for c in FIELDS]
+    assert _raw(hip, names, 3, 2, 1, 5, num, den, many) == L.OK and _raw(hip, FIELDS, 3, 2, 1, 5, num, den, four) == L.OK
+    assert all(np.all(b[:, :, 0] == 13) for b in four)                 # filled: 65 rows in 5 groups
+    for k, b in enumerate(many):
+        assert b.tobytes() == four[k % 4].tobytes(), (k, names[k])
+    hip.close()
+
+
 # ---- 7. linear ---------------------------------------------------------------------------------------------------------
 def test_linear_is_the_documented_formula_of_lower_upper_and_count():
     n = 300
