@@ -29,6 +29,8 @@ ENVELOPE_ASYNC = 1   # sixdof_history_envelope flags
 ENVELOPE_MAX_BINS = 512   # period * width one call reduces (csrc/envelope_plan.hpp: kEnvelopeMaxBins)
 QUANTILE_ASYNC = 1   # sixdof_history_quantiles flags
 QUANTILE_MAX_RANKS = 16   # ranks one call selects (SIXDOF_QUANTILE_MAX_RANKS)
+EXTREMES_ASYNC, EXTREMES_CONTINUE, EXTREMES_HOLD = 1, 2, 4   # sixdof_history_extremes flags
+EXTREMES_PLANES = 6       # count, min, tick_min, max, tick_max, first_nonfinite (SIXDOF_EXTREMES_PLANES)
 
 EFF_CONST_WRENCH = 1
 EFF_UNIFORM_GRAVITY = 2
@@ -147,6 +149,8 @@ SYMBOLS = {
                                           C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_history_quantiles": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                            C.POINTER(C.c_uint32), C.c_uint32, C.c_size_t, C.POINTER(C.c_void_p), C.c_uint32]),
+    "sixdof_history_extremes": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p),
+                                          C.c_uint32]),
     "sixdof_set_model_apollo": (C.c_int, [_H, C.c_void_p]),
     "sixdof_download_column": (C.c_int, [_H, C.c_uint64]),
     "sixdof_upload_column": (C.c_int, [_H, C.c_uint64]),

@@ -858,6 +858,26 @@ class Exec:
         out["time"] = time
         return out
 
+    def history_extremes(self, components, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
+        """Every executor row collapsed ACROSS TIME: {component: {"count", "argmin", "argmax", "first_nonfinite": int64 [rows, w];
+        "min", "max", "t_min", "t_max", "t_first_nonfinite": f64 [rows, w]}} over world ticks first_tick, first_tick + every, ...
+        <= last_tick, reduced on the device out of the ring (enable_history) — peak and when, lowest and when, the tick a row
+        went non-finite.  Tick fields are world ticks, the EARLIEST sampled tick that holds the extreme; 0 means none, and the
+        matching t_* (seconds) is NaN.  min and max are elements of the ring, bit for bit."""
+        comps = [components] if isinstance(components, str) else list(components)
+        for comp in comps:
+            self._refuse_unrecorded("history_extremes", comp, comp)
+        (first, last, step), _ = self._sampled_ticks("history_extremes", first_tick, last_tick, every)
+        s = getattr(self, "_substeps", 1)
+        out: Dict[str, Any] = {}
+        for comp, d in self._hip.history_extremes(comps, first, last, step).items():
+            d = dict(d)
+            for tick_field, seconds in (("argmin", "t_min"), ("argmax", "t_max"), ("first_nonfinite", "t_first_nonfinite")):
+                d[tick_field] = d[tick_field] // s          # exact: every sample is a multiple of the sub-step count
+                d[seconds] = np.where(d[tick_field] == 0, np.nan, d[tick_field].astype(np.float64) * self._dt)
+            out[comp] = d
+        return out
+
     def column_ids(self, name: str) -> np.ndarray:
         """Entity id of each row of column_array(name)."""
         n = len(self._main_column_array(name))

@@ -20,6 +20,7 @@
 #include "../../include/sixdof_hip.h"
 #include "aql_chain.hpp"
 #include "envelope_plan.hpp"
+#include "extremes_plan.hpp"
 #include "history_plan.hpp"
 #include "kernels.hpp"
 #include "quantile_plan.hpp"
@@ -355,6 +356,57 @@ hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components,
         if (elem == 8) quantiles_of_tick<double>(src, n, d.w, period, ranks, h, st, to);
         else quantiles_of_tick<float>(src, n, d.w, period, ranks, h, st, to);
     }));
+}
+// the walk and the merge themselves (extremes_kernels.hip), serially: extremes_plan.hpp's rule in the kernels' segmentation — with
+// more than one segment every (segment, element) record goes through the launch's scratch, as on the device
+template <class E>
+static void extremes_of_component(const RingBinDesc& d, double* out, uint64_t* scratch, uint64_t stride, uint32_t segments, bool merge_into, uint64_t n,
+                                  uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
+    const uint64_t total = n * d.w, step = every % ring;
+    for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
+        const uint64_t lo = extremes_segment_start(n_samples, segments, seg), hi = extremes_segment_start(n_samples, segments, seg + 1);
+        for (uint64_t i = 0; i < total; i++) {
+            uint64_t slot = sample_slot(first_tick, lo, every, ring), tick = first_tick + lo * every;
+            ExtremesRecord r = extremes_empty();
+            for (uint64_t j = lo; j < hi; j++, tick += every, slot = next_sample_slot(slot, step, ring)) {
+                E x;
+                std::memcpy(&x, static_cast<const char*>(d.ring) + (slot * total + i) * sizeof(E), sizeof(E));
+                extremes_sample<E>(r, x, tick);
+            }
+            double* o = out + d.out_offset + i;
+            if (segments == 1) {
+                if (merge_into) r = extremes_merge(extremes_absorb<E>(o, total), r);
+                extremes_emit<E>(r, o, total);
+            } else {
+                extremes_store(r, scratch + uint64_t(seg) * kExtremesFields * stride + d.scratch_offset + i, stride);
+            }
+        }
+    }
+    for (uint64_t i = 0; segments > 1 && i < total; i++) {                 // stage 2
+        double* o = out + d.out_offset + i;
+        ExtremesRecord r = merge_into ? extremes_absorb<E>(o, total) : extremes_empty();
+        for (uint32_t s = 0; s < segments; s++) r = extremes_merge(r, extremes_load(scratch + uint64_t(s) * kExtremesFields * stride + d.scratch_offset + i, stride));
+        extremes_emit<E>(r, o, total);
+    }
+}
+hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, double* out, void* scratch, uint64_t scratch_stride, uint32_t segments,
+                                   bool merge_into, uint64_t n, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem,
+                                   hipStream_t) {
+    uint32_t widths[kRingBinMaxComponents] = {};
+    for (uint32_t k = 0; k < n_components && k < kRingBinMaxComponents; k++) widths[k] = a.c[k].w;
+    if (!extremes_launch_ok(n_components, kRingBinMaxComponents, widths, n, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
+    if (n == 0) return launch(true);
+    if (segments > 1 && !need(live(scratch, extremes_scratch_bytes(segments, scratch_stride)), "extremes scratch records")) return launch(false);
+    for (uint32_t k = 0; k < n_components; k++) {
+        const RingBinDesc& d = a.c[k];
+        const uint64_t total = n * d.w;
+        if (!need(segments == 1 || d.scratch_offset + total <= scratch_stride, "extremes scratch of one segment")) return launch(false);
+        if (!need(live(d.ring, ring * total * elem) && live(out + d.out_offset, kExtremesPlanes * total * sizeof(double)), "ring or extremes staging"))
+            return launch(false);
+        if (elem == 8) extremes_of_component<double>(d, out, static_cast<uint64_t*>(scratch), scratch_stride, segments, merge_into, n, first_tick, n_samples, every, ring);
+        else extremes_of_component<float>(d, out, static_cast<uint64_t*>(scratch), scratch_stride, segments, merge_into, n, first_tick, n_samples, every, ring);
+    }
+    return launch(true);
 }
 hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags, unsigned long long* count, hipStream_t) {
     return launch(need(live(pos, n * 7 * elem) && live(vel, n * 6 * elem) && live(count, 8) && (!flags || live(flags, n)), "count_nonfinite buffers"));

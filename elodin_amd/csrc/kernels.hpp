@@ -194,6 +194,16 @@ hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components,
                                     void* state, uint64_t slot_stride, uint64_t n, uint32_t period, uint64_t first_tick,
                                     uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
 
+// ---- ring extremes: per row and element, min / max over the sampled ticks and the ticks they fall on (extremes_kernels.hip) ---
+// 6 planes; here a component's block in `out` is [6][n * w] doubles at out_offset, and a scratch unit is one element: its records
+// start at scratch_offset in every segment's `scratch_stride` units.  All n_samples samples of the range first_tick, first_tick +
+// every, ... in `segments` time segments (extremes_plan.hpp); with more than one, `scratch` holds segments * 6 * scratch_stride
+// 64-bit words.  merge_into: `out` holds the planes of the samples before this range, and the result covers both.  The caller has
+// validated the range (sampled_range_ok, extremes_ticks_ok).
+hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, double* out, void* scratch, uint64_t scratch_stride,
+                                   uint32_t segments, bool merge_into, uint64_t n, uint64_t first_tick, uint64_t n_samples, uint64_t every,
+                                   uint64_t ring, size_t elem, hipStream_t s);
+
 hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags,
                             unsigned long long* count, hipStream_t s);
 

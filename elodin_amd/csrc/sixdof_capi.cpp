@@ -31,6 +31,7 @@
 #include "device_mem.hpp"
 #include "aql_chain.hpp"
 #include "envelope_plan.hpp"
+#include "extremes_plan.hpp"
 #include "quantile_plan.hpp"
 #include "history_plan.hpp"
 #include "step_plan.hpp"
@@ -158,6 +159,17 @@ struct History {
     DeviceBuffer env_stage, env_partial;
     // sixdof_history_quantiles: its staging, and the histograms and slot states of one launch; the same rules
     DeviceBuffer quant_stage, quant_scratch;
+    // sixdof_history_extremes: its staging, which is also the accumulator a SIXDOF_EXTREMES_CONTINUE call merges into, and the
+    // segment records of one launch; the same rules.  `extremes` says what the accumulator holds, if anything.
+    DeviceBuffer ext_stage, ext_scratch;
+    struct Extremes {
+        bool valid = false;                  // the previous call succeeded and nothing has replaced what it read since
+        std::vector<uint64_t> ids;           // its component list, in order
+        std::vector<const void*> rings;      // ring base and width of each as they were: a replaced program changes them
+        std::vector<size_t> widths;
+        uint64_t n = 0;
+        uint64_t last_tick = 0;              // the last tick accumulated
+    } extremes;
     void reset() { *this = History{}; }
 };
 
@@ -476,6 +488,7 @@ void sixdof_destroy(sixdof_handle* h) try {
 int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_cols) try {
     if (!h || (!cols && n_cols)) return SIXDOF_ERR_INVALID_ARGUMENT;
     h->bound = h->resident = false;   // until the end of this call: a failed bind leaves the handle unbound
+    h->hist.extremes.valid = false;   // the rows an extremes accumulator covers may be other rows from here on
     HIP_TRY(h, hipSetDevice(h->device));
     h->replay.drop();
     if (h->d_watch_rows) {      // a watch holds rows of the join this call replaces
@@ -1393,7 +1406,7 @@ int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_c
 
 // A read whose results are computed on the compute stream, out of the ring into a device staging buffer, and brought from
 // there to the caller's buffers, blocking or over the copy lane: sixdof_watch_read and, through ring_bin_read below,
-// sixdof_history_envelope and sixdof_history_quantiles.  The lane and the rules of the staging buffer live here and nowhere
+// sixdof_history_envelope and sixdof_history_quantiles, and sixdof_history_extremes.  The lane and the rules of the staging buffer live here and nowhere
 // in the callers: add() the components, claim() the buffers, launch into them, deliver().
 struct StagedRead {
     // one component: ring base and width as they are NOW, its block in the staging buffer (256-byte aligned), where it goes
@@ -1405,10 +1418,11 @@ struct StagedRead {
     size_t stage_bytes = 0;
 
     // `per_width` elements of `elem` bytes for every element of a row; `unrecorded`: the message when the ring does not hold `id`
-    int add(uint64_t id, void* host, size_t per_width, size_t elem, const char* unrecorded) {
+    // (host_needed = false: a read that delivers nothing, sixdof_history_extremes with SIXDOF_EXTREMES_HOLD)
+    int add(uint64_t id, void* host, size_t per_width, size_t elem, const char* unrecorded, bool host_needed = true) {
         Part p{};
         if (!watch_lookup(h, id, &p.ring, &p.w) || !p.ring) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, std::string(who) + ": " + unrecorded);
-        if (!host) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, std::string(who) + ": null host buffer");
+        if (!host && host_needed) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, std::string(who) + ": null host buffer");
         p.host = host, p.bytes = per_width * p.w * elem, p.offset = stage_bytes;
         stage_bytes += (p.bytes + 255) / 256 * 256;
         parts.push_back(p);
@@ -1625,6 +1639,88 @@ int sixdof_history_quantiles(sixdof_handle* h, const uint64_t* component_ids, si
             return launch_history_quantiles(a, cnt, ranks, hs.quant_stage.get<double>(), scratch, scratch + chunk * stride * kHistBytes, stride,
                                             h->desc.n_entities, period, first_tick, s0, ns, every, hs.ring, h->elem_size(), h->stream.get());
         });
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// The extremes of every row over the sampled ticks of a range.  Ordering, ring reads and the copy lane exactly as for
+// sixdof_watch_read above; not through ring_bin_read, whose output and chunk rule are per sample and (group, element) bin: here
+// ALL samples of the range go into one launch per batch of components, cut into time segments, and the output is per row.  The
+// staging buffer is the accumulator: a SIXDOF_EXTREMES_CONTINUE call merges into what the previous call left there.
+// Commit on success: History::extremes is invalid from the first step that can fail in the runtime to the last enqueue.
+int sixdof_history_extremes(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
+                            uint64_t n_samples, uint64_t every, double* const host_dst[], uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    const std::string who = "history_extremes";
+    if (flags & ~(SIXDOF_EXTREMES_ASYNC | SIXDOF_EXTREMES_CONTINUE | SIXDOF_EXTREMES_HOLD)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": unknown flags");
+    History& hs = h->hist;
+    if (!hs.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": no history ring (sixdof_set_history)");
+    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": every must be at least 1");
+    if (n_samples == 0 || n_components == 0) return SIXDOF_OK;
+    const bool hold = (flags & SIXDOF_EXTREMES_HOLD) != 0, merge_into = (flags & SIXDOF_EXTREMES_CONTINUE) != 0;
+    if (!component_ids || (!host_dst && !hold)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
+    if (!sampled_range_ok(first_tick, n_samples, every, hs.first_tick, h->tick, hs.ring))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": ticks are not (all) in the ring");
+    if (!extremes_ticks_ok(first_tick, n_samples, every))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": a sampled tick of 2^53 or more has no double of its own");
+    const uint64_t n = h->desc.n_entities;
+    StagedRead rd{h, "history_extremes", &hs.ext_stage};
+    for (size_t k = 0; k < n_components; k++) {
+        const int rc = rd.add(component_ids[k], hold ? nullptr : host_dst[k], static_cast<size_t>(n) * kExtremesPlanes, sizeof(double),
+                              "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded", !hold);
+        if (rc != SIXDOF_OK) return rc;
+    }
+    History::Extremes& acc = hs.extremes;
+    if (merge_into) {
+        bool same = acc.valid && acc.n == n && acc.ids.size() == n_components && std::equal(acc.ids.begin(), acc.ids.end(), component_ids);
+        for (size_t k = 0; same && k < n_components; k++) same = acc.rings[k] == rd.parts[k].ring && acc.widths[k] == rd.parts[k].w;
+        if (!same)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": SIXDOF_EXTREMES_CONTINUE: there is no accumulator of these components, rows and rings to continue "
+                                                              "(the previous call failed or read something else, or the ring, the columns or the program were replaced since)");
+        if (first_tick <= acc.last_tick)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": SIXDOF_EXTREMES_CONTINUE: first_tick " + std::to_string(first_tick) + " is not above tick " +
+                                                              std::to_string(acc.last_tick) + ", the last one accumulated");
+    }
+    // one launch per batch of at most kRingBinMaxComponents components; its segment records stay within a fixed scratch budget
+    const char* forced_env = std::getenv("SIXDOF_EXTREMES_SEGMENTS");   // 0 or unset: the plan's choice (A/B runs, tests)
+    const uint64_t forced = forced_env ? std::strtoull(forced_env, nullptr, 10) : 0;
+    constexpr uint64_t kScratchBudget = uint64_t(64) << 20;
+    struct Batch { size_t k0; uint32_t count; uint64_t units; uint32_t segments; };
+    std::vector<Batch> batches;
+    uint64_t scratch_bytes = 0;
+    for (size_t k0 = 0; k0 < n_components; k0 += kRingBinMaxComponents) {
+        Batch b{k0, static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_components - k0)), 0, 1};
+        for (uint32_t k = 0; k < b.count; k++) b.units += n * rd.parts[k0 + k].w;
+        b.segments = forced ? extremes_clamp_segments(forced, n_samples) : extremes_segments(b.units, n_samples);
+        b.segments = extremes_fit_segments(b.segments, b.units, kScratchBudget);
+        scratch_bytes = std::max(scratch_bytes, extremes_scratch_bytes(b.segments, b.units));
+        batches.push_back(b);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    acc.valid = false;
+    if (int rc = rd.claim(&hs.ext_scratch, static_cast<size_t>(scratch_bytes)); rc != SIXDOF_OK) return rc;
+    for (const Batch& b : batches) {
+        RingBinArgs a{};
+        uint64_t unit0 = 0;
+        for (uint32_t k = 0; k < b.count; k++) {
+            const StagedRead::Part& p = rd.parts[b.k0 + k];
+            a.c[k].ring = p.ring;
+            a.c[k].out_offset = p.offset / sizeof(double);
+            a.c[k].scratch_offset = unit0;
+            a.c[k].w = static_cast<uint32_t>(p.w);
+            unit0 += n * p.w;
+        }
+        hipError_t e = launch_history_extremes(a, b.count, hs.ext_stage.get<double>(), hs.ext_scratch.get(), b.units, b.segments, merge_into, n, first_tick,
+                                               n_samples, every, hs.ring, h->elem_size(), h->stream.get());
+        if (e != hipSuccess) return h->hip_fail(e, "history_extremes");
+    }
+    if (!hold)
+        if (int rc = rd.deliver((flags & SIXDOF_EXTREMES_ASYNC) != 0); rc != SIXDOF_OK) return rc;
+    acc.ids.assign(component_ids, component_ids + n_components);
+    acc.rings.clear(), acc.widths.clear();
+    for (const StagedRead::Part& p : rd.parts) acc.rings.push_back(p.ring), acc.widths.push_back(p.w);
+    acc.n = n;
+    acc.last_tick = first_tick + (n_samples - 1) * every;
+    acc.valid = true;
+    return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
 int sixdof_download_column(sixdof_handle* h, uint64_t component_id) try {

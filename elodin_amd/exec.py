@@ -711,6 +711,75 @@ class HipExec:
         upper are views of buffers reused two batches later.  Returns the wall time in seconds."""
         return self._stream_reduce("stream_quantiles", self._quantile_reduction(q), names, n_batches, ticks_per_batch, every, period, consume, flags)
 
+    # ---- ring extremes: every row collapsed across time, and the ticks its extremes fall on -----------------------------
+    EXTREMES_FIELDS = ("count", "min", "argmin", "max", "argmax", "first_nonfinite")      # the six planes, in order
+
+    @staticmethod
+    def _extremes_dict(names, raw) -> dict:
+        """[6, n, w] blocks -> {name: {"count", "argmin", "argmax", "first_nonfinite": int64 [n, w]; "min", "max": f64 [n, w]}}.
+        The integer planes arrive as doubles below 2^53: the conversion is exact."""
+        out = {}
+        for name, a in zip(names, raw):
+            out[name] = {k: a[i] if k in ("min", "max") else a[i].astype(np.int64) for i, k in enumerate(HipExec.EXTREMES_FIELDS)}
+        return out
+
+    def _extremes_buffers(self, names):
+        """One [6, n, w] block per name, holding what a range without samples reduces to: count 0, NaN extremes, no ticks."""
+        raw = [np.zeros((L.EXTREMES_PLANES, self.n, self._recorded_width(name)), dtype=np.float64) for name in names]
+        for a in raw:
+            a[1], a[3] = np.nan, np.nan
+        return raw, (C.c_void_p * max(1, len(names)))(*[a.ctypes.data for a in raw])
+
+    def _extremes_read(self, comp, first_tick: int, n_samples: int, every: int, ptrs, flags: int) -> None:
+        rc = self._lib.sixdof_history_extremes(self._h, comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), first_tick, n_samples, every, ptrs, flags)
+        if rc != L.OK:
+            _raise(self._h, rc, "sixdof_history_extremes")
+
+    def history_extremes(self, names: Sequence[str], first_tick: int, last_tick: int, every: int = 1) -> dict:
+        """{name: {"count", "argmin", "argmax", "first_nonfinite": int64 [n, w]; "min", "max": f64 [n, w]}}: every row collapsed
+        across the ticks first_tick, first_tick + every, ... <= last_tick, reduced on the device out of the ring.  Per row and
+        element: count of the samples at which it is finite, its smallest and largest finite value — elements of the ring, bit
+        for bit, -0.0 below +0.0 — with the EARLIEST sampled tick that holds each, and the earliest sampled tick at which it is
+        not finite.  0 in a tick field means none; count == 0 leaves min and max NaN.  Stateless: no watch is involved."""
+        names = [names] if isinstance(names, str) else list(names)
+        first_tick, last_tick, every = int(first_tick), int(last_tick), int(every)
+        raw, ptrs = self._extremes_buffers(names)
+        comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
+        self._extremes_read(comp, first_tick, self._sample_count(first_tick, last_tick, every), every, ptrs, 0)
+        return self._extremes_dict(names, raw)
+
+    def stream_extremes(self, names: Sequence[str], n_batches: int, ticks_per_batch: int, every: int = 1, flags: int = 0):
+        """history_extremes over a run longer than the ring: n_batches batches of ticks_per_batch ticks are stepped, and after
+        every batch its samples — every `every`-th tick, ending on the batch's last — are merged into the accumulator on the
+        device (SIXDOF_EXTREMES_HOLD, SIXDOF_EXTREMES_CONTINUE from the second batch on).  Nothing crosses the link until the last
+        batch's call delivers.  The ring is read on the compute stream, so a ring one batch deep is enough (enabled here unless
+        enable_history already made one at least that large).  Returns (wall time in seconds, the dict of history_extremes);
+        whatever happens, the caller's flags are restored and the handle is drained."""
+        import time
+        names = [names] if isinstance(names, str) else list(names)
+        n_batches, ticks_per_batch, every = int(n_batches), int(ticks_per_batch), int(every)
+        n_samples = self._stream_shape("stream_extremes", ticks_per_batch, every)
+        if n_batches < 1:
+            raise ValueError("stream_extremes: at least one batch")
+        raw, ptrs = self._extremes_buffers(names)
+        comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
+        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
+            self.enable_history(ticks_per_batch)
+        self.sync()              # nothing of an earlier streaming run is in flight
+        self.set_flags(flags | L.FLAG_ASYNC_STEP)
+        t0 = time.perf_counter()
+        try:
+            for i in range(n_batches):
+                first = self.tick + every                                # samples end on the batch's last tick
+                self.invoke_batch(ticks_per_batch)
+                last = i + 1 == n_batches
+                self._extremes_read(comp, first, n_samples, every, ptrs if last else None,
+                                    (L.EXTREMES_CONTINUE if i else 0) | (0 if last else L.EXTREMES_HOLD))
+        finally:
+            self.set_flags(flags)
+            self.sync()
+        return time.perf_counter() - t0, self._extremes_dict(names, raw)
+
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))
 

@@ -325,6 +325,14 @@ class Campaign:
         count below n_runs."""
         return self.exec.history_quantiles(components, first_tick, last_tick, q, every, period=self.entities_per_run)
 
+    def extremes(self, components, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
+        """Every run collapsed across time, out of the device ring (self.exec.enable_history): {component: {"count", "argmin",
+        "argmax", "first_nonfinite", "min", "max", "t_min", "t_max", "t_first_nonfinite": [run, entity-of-run, w]}} over world ticks
+        first_tick, first_tick + every, ... <= last_tick — what goes into a results table: a run's peak and when, its lowest
+        value, the tick at which it went non-finite (0: never)."""
+        out = self.exec.history_extremes(components, first_tick, last_tick, every)
+        return {comp: {k: v.reshape(self.n_runs, self.entities_per_run, v.shape[-1]) for k, v in d.items()} for comp, d in out.items()}
+
     def result_table(self, names: Sequence[str]) -> np.ndarray:
         """The runs' `el.monte_carlo.result(...)` records as [n_runs, len(names)] (NaN where a run reported nothing)."""
         out = np.full((self.n_runs, len(names)), np.nan)

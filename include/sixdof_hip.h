@@ -490,6 +490,47 @@ int sixdof_history_quantiles(sixdof_handle* h, const uint64_t* component_ids, si
                              uint64_t n_samples, uint64_t every, uint32_t period, const uint32_t* rank_num, uint32_t rank_den,
                              size_t n_ranks, double* const host_dst[], uint32_t flags);
 
+/* ---- ring extremes: every row collapsed across time ------------------------------------------------------------------
+ * What a campaign's results table wants per run is peak dynamic pressure and when, apogee and when, the lowest altitude, the tick
+ * at which a run went non-finite — per row, collapsed across time, reduced on the device: six numbers per element, once.
+ *
+ * Samples and components are sixdof_history_envelope's: sample j is the state after tick first_tick + j * every, components are
+ * the ones sixdof_history_read accepts (anything else: SIXDOF_ERR_COMPONENT_NOT_FOUND); an id may appear more than once.  For
+ * component k, row r < n and element c < w_k, host_dst[k] receives [6][n][w_k] doubles, plane-major:
+ *   plane 0  count             samples at which the element is finite
+ *   plane 1  min               the smallest finite value
+ *   plane 2  tick_min          the EARLIEST sampled tick that holds it
+ *   plane 3  max               the largest finite value
+ *   plane 4  tick_max          the EARLIEST sampled tick that holds it
+ *   plane 5  first_nonfinite   the earliest sampled tick at which the element is not finite; 0: none
+ * The order is sixdof_history_quantiles': the total order of the sign-magnitude bit pattern, -0.0 below +0.0, and "holds it" means
+ * bit-equal.  count = 0: min and max are NaN, their ticks 0.  Ticks are counts of completed ticks as the handle counts them, as
+ * doubles; tick 0 is never in the ring, so 0 means "none"; a range whose last sampled tick is 2^53 or more is refused.  Every
+ * value is an element of the ring converted to double (exact for an f32 handle).  No floating-point arithmetic and no atomics:
+ * a later sample replaces an extreme only when strictly smaller or larger, a rule that is exact and associative in time order,
+ * so the result is bit-identical however the range is cut into time segments (SIXDOF_EXTREMES_SEGMENTS in the environment
+ * forces a count; 0 or unset: the library's choice), launches or calls.
+ * SIXDOF_EXTREMES_HOLD: reduce and keep the result in the device accumulator (the call's staging buffer, freed with the ring);
+ * nothing is delivered, host_dst is ignored.  SIXDOF_EXTREMES_CONTINUE: merge into the accumulator the previous successful call
+ * left instead of starting afresh — how a run longer than the ring is reduced batch by batch with nothing crossing the link until
+ * the last call.  Accepted only if the previous call succeeded with the same component ids in the same order, ring bases, widths
+ * and row count are unchanged, no sixdof_set_history or sixdof_bind_columns came since, and first_tick is above the last tick
+ * accumulated; otherwise SIXDOF_ERR_INVALID_ARGUMENT and the accumulator stays as it was.
+ * SIXDOF_EXTREMES_ASYNC: the rules of SIXDOF_WATCH_ASYNC — the copies go on the copy stream, sixdof_download_wait blocks until
+ * they have landed, host_dst stays allocated (and page-locked) until sixdof_sync.  Either way the ring is read on the compute
+ * stream: a later sixdof_step may overwrite the slots at once, and a ring one batch deep is enough.
+ * n_samples = 0 is a no-op that leaves the accumulator alone.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied and the
+ * accumulator as it was: no ring, every = 0, a sampled tick that is not (or no longer) in the ring, unknown flags, a null
+ * component_ids, a null buffer without SIXDOF_EXTREMES_HOLD.  A call that fails in the runtime leaves the ring as it was and the
+ * accumulator invalid: the next SIXDOF_EXTREMES_CONTINUE is refused, a fresh call works; a staging or scratch buffer that could
+ * not be grown is absent (size 0) and the next call allocates it again. */
+#define SIXDOF_EXTREMES_ASYNC    1u
+#define SIXDOF_EXTREMES_CONTINUE 2u
+#define SIXDOF_EXTREMES_HOLD     4u
+#define SIXDOF_EXTREMES_PLANES   6
+int sixdof_history_extremes(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
+                            uint64_t n_samples, uint64_t every, double* const host_dst[], uint32_t flags);
+
 /* ---- rollout models: systems piped AROUND six_dof, fused with it (the pipes of examples/<name>/sim.py) ------------- */
 struct sixdof_apollo_tables; /* include/sixdof_apollo.h */
 /* Select the Apollo-lander rollout model (examples/apollo-lander/sim.py:517-526 + the guidance sidecar
