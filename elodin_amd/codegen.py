@@ -377,10 +377,11 @@ class _Emitter:
                 sc["lines"].append(f"{sc['indent']}}}")
                 return sc["names"][id(e)]
             wide = self._is_wide(e)
-            if u.relaxed and not wide and e.op == "div" and e.args[0].is_const(1.0):
+            if u.relaxed and not wide and e.op == "div" and e.value == dsl.RELAXED_RCP:
                 # RELAXED ARITHMETIC (dsl.relaxed_arithmetic): the shared reciprocal of a denominator is v_rcp_f64 + two Newton steps
                 # (7 instructions against the 11 of an IEEE divide, 1 ulp), and 1 / sqrt(s) the hardware seed + one cubic correction
-                # (spatial.hpp rsqrt_pos: 5 against a library sqrt and a divide)
+                # (spatial.hpp rsqrt_pos: 5 against a library sqrt and a divide).  Only the reciprocals the rewrite created (tagged
+                # dsl.RELAXED_RCP): a `1.0 / x` of the user's, or one built while the relaxation was suspended, is an IEEE m_div
                 d = e.args[1]
                 if d.op == "sqrt" and not self._is_wide(d.args[0]):
                     rhs = f"m_rsqrt_relaxed({ref(d.args[0], sc)})"
@@ -802,14 +803,15 @@ def _emit_systems(u: _Unit, systems, cold: Optional[Dict[int, int]] = None, stor
     return "\n".join(out)
 
 
-_RELAXED_PRELUDE = '''// relaxed arithmetic only (dsl.relaxed_arithmetic): 1 / x as v_rcp_f64 + two Newton steps (1 ulp; x = 0 / inf keep the seed's
-// inf / 0), 1 / sqrt(x) as the seed + one cubic correction
+_RELAXED_PRELUDE = '''// relaxed arithmetic only (dsl.relaxed_arithmetic): 1 / x as v_rcp_f64 + two Newton steps (1 ulp).  The Newton result is taken
+// only from a finite, non-zero seed: x = 0 / inf / NaN keep the seed's inf / 0 / NaN, and so does a subnormal x whose reciprocal
+// overflows (seed inf, like an IEEE divide).  1 / sqrt(x) as the seed + one cubic correction (2 ulp, finite x > 0)
 __device__ __forceinline__ double m_rcp_relaxed(double x) {
     const double r0 = __builtin_amdgcn_rcp(x);
     const double e = fma(-x, r0, 1.0);
     double r = fma(e, r0, r0);
     r = fma(fma(-x, r, 1.0), r, r);
-    return e == e ? r : r0;
+    return __builtin_amdgcn_class(r0, 0x198) ? r : r0;      // 0x198: +-normal | +-subnormal
 }
 __device__ __forceinline__ float m_rcp_relaxed(float x) { return 1.0f / x; }
 __device__ __forceinline__ double m_rsqrt_relaxed(double x) { return rsqrt_pos(x); }

@@ -32,21 +32,25 @@ import numpy as _numpy          # host arrays met inside traced code (module-lev
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 Number = Union[int, float]
+_EXACT_CONSUMERS = frozenset(("floor", "ceil", "trunc", "rint", "lt", "le", "eq", "mod"))      # see RELAXED ARITHMETIC below
 
 
 class Expr:
     """One scalar node of the DAG."""
-    __slots__ = ("op", "args", "value", "name", "seq")
+    __slots__ = ("op", "args", "value", "name", "seq", "quot")
     _interned: Dict[tuple, "Expr"] = {}
     _count = [0]      # creation counter: `seq` orders nodes the way the user's program created them (arguments first)
 
     def __new__(cls, op: str, args: tuple = (), value=None, name: Optional[str] = None):
+        if op in _EXACT_CONSUMERS:      # relaxed arithmetic: a rounding / compare sees the exact quotient (see RELAXED ARITHMETIC)
+            args = tuple(_exact_quotient(a) for a in args)
         key = (op, tuple(id(a) for a in args), value, name)
         hit = cls._interned.get(key)
         if hit is not None:
             return hit
         self = object.__new__(cls)
         self.op, self.args, self.value, self.name = op, args, value, name
+        self.quot = None      # (a, d) on the product that relaxed arithmetic built for a / d (_bin)
         self.seq = cls._count[0]
         cls._count[0] += 1
         cls._interned[key] = self
@@ -411,7 +415,31 @@ def _un(op: str, x) -> "Expr":
 # the quotients of one denominator (a quaternion normalised, inverted, a wrench over one mass) share ONE division through the
 # hash-consing of nodes, and lets the compiler contract `a * b + c` (System.fp_contract -> codegen).  Results differ from the
 # reference's in the last bits (<= a few ulp per operation), not bit for bit.
+# An ulp in a quotient is a whole unit behind a rounding or a compare (49 * (1 / 49) = 0.9999999999999999, whose floor is 0), so:
+# PROTECTED — a quotient consumed DIRECTLY (or through `neg` / `abs`, which are exact) by floor, ceil, trunc (the float-to-integer convert),
+# rint, a compare (lt, le, eq and what is spelled with them: gt, ge, ne, a select's predicate) or mod is an exact IEEE `div` for
+# that consumer; every other consumer of the same quotient keeps the shared reciprocal.  NOT PROTECTED — a quotient that reaches
+# a rounding or a compare through further arithmetic (`floor(x / y + 0.5)`, `x / y - k < 0`): it carries its few ulp there.
+# The reciprocal the rewrite creates is its own node (`div(1, d)` with value RELAXED_RCP: codegen's m_rcp_relaxed /
+# m_rsqrt_relaxed); a `1.0 / x` the user wrote, and one built while the relaxation is suspended, keeps its IEEE divide.
 _RELAXED = [False]
+RELAXED_RCP = "rcp"
+
+
+def _exact_quotient(x):
+    """x with the product relaxed arithmetic made of a quotient (Expr.quot), directly or under neg / abs, as the exact div."""
+    if not isinstance(x, Expr):
+        return x
+    if x.quot is not None:
+        saved, _RELAXED[0] = _RELAXED[0], False
+        try:
+            return _bin("div", *x.quot)
+        finally:
+            _RELAXED[0] = saved
+    if x.op in ("neg", "abs"):      # sign changes are exact; a chain of them, because stablehlo.remainder adds an abs of its own
+        inner = _exact_quotient(x.args[0])
+        return x if inner is x.args[0] else Expr(x.op, (inner,))
+    return x
 
 
 class relaxed_arithmetic:
@@ -449,7 +477,8 @@ def _unit_norm_squared(n: "Expr") -> bool:
         if c.op != "mul":
             return False
         a, b = c.args
-        cand = b if (b.op == "div" and b.args[0].is_const(1.0)) else (a if (a.op == "div" and a.args[0].is_const(1.0)) else None)
+        rcp = lambda x: x.op == "div" and x.value == RELAXED_RCP
+        cand = b if rcp(b) else (a if rcp(a) else None)
         if cand is None or (r is not None and cand is not r):
             return False
         r = cand
@@ -466,12 +495,17 @@ def _bin(op: str, a, b) -> Expr:
         if op == "mul" and (a.is_const(0.0) or b.is_const(0.0)):
             return const(0.0)
         if op == "div" and a.op != "const":
+            m = None
             if b.op == "const" and b.value not in (0.0,) and b.value == b.value and abs(b.value) != float("inf"):
-                return _bin("mul", a, const(1.0 / b.value))
-            if b.op != "const":
+                m = _bin("mul", a, const(1.0 / b.value))
+            elif b.op != "const":
                 if _unit_norm_squared(b):      # a / |q^|^2 for q^ = q / |q|: the reference's `inverse` of a normalised quaternion (quaternion.rs:141-155)
                     return a
-                return _bin("mul", a, Expr("div", (const(1.0), b)))
+                m = _bin("mul", a, Expr("div", (const(1.0), b), RELAXED_RCP))
+            if m is not None:
+                if m.op == "mul" and m.args[0] is a:      # the product remembers its quotient: _exact_quotient, for a rounding or a compare
+                    m.quot = (a, b)
+                return m
     if op in ("add", "sub", "mul", "div"):
         if a.op == "const" and b.op == "select" and _const_tree(b):
             return _map_const_tree(b, lambda c: _bin(op, a, c))

@@ -2654,7 +2654,10 @@ def world_program(text: str, slots: Sequence, out_slots: Optional[Sequence] = No
     k: (source rows, target rows)} in slot order — rows of ONE world; hand them to the executor as entity ids of its rows
     (HipExec graph_edges=, with graph_replicas=(worlds, N) for a Monte-Carlo of such worlds).
     arith="relaxed": the systems AND the fold bodies are traced under dsl.relaxed_arithmetic (world_system's switch: finite values
-    assumed, one reciprocal per denominator, a * b + c contracted) — inside 1e-9 of the reference, not its last bits."""
+    assumed, one reciprocal per denominator, a * b + c contracted) — inside 1e-9 of the reference, not its last bits.  Protected: a
+    quotient consumed directly (or through negate / abs) by floor, ceil, round_nearest_even, a convert to an integer, a compare
+    (so a select's predicate) or remainder is an exact IEEE divide for that consumer.  Not protected: a quotient that reaches
+    a rounding or a compare through further arithmetic (`floor(x / y + 0.5)`) keeps its few ulp, and may step a whole unit there."""
     if arith not in ("reference", "relaxed"):
         raise ValueError("arith must be 'reference' or 'relaxed'")
     funcs = parse_module(text)
@@ -2839,6 +2842,11 @@ def world_system(text: str, slots: Sequence, out_slots: Optional[Sequence] = Non
     arith: "reference" — the module's arithmetic operation for operation (bit for bit the oracle's on the golden worlds);
            "relaxed"   — dsl.relaxed_arithmetic: finite values assumed (`0 * x` = 0, so a read that only feeds one disappears),
                          one division per denominator, `a * b + c` contracted: inside 1e-9, not the reference's last bits.
+                         Protected: a quotient consumed directly (or through negate / abs) by floor, ceil, round_nearest_even,
+                         a convert to an integer, a compare (so a select's predicate) or remainder is an exact IEEE divide
+                         for that consumer (`floor(t / period)` counts like the reference).  Not protected: a quotient that
+                         reaches a rounding or a compare through further arithmetic (`floor(x / y + 0.5)`) keeps its few ulp
+                         and may step a whole unit there.  A `1.0 / x` written in the module stays an IEEE divide.
     one_world (lane mode): the caller promises that the executor's rows are the entities of ONE world — the singleton slots
            (Globals: tick, dt), replicated per row, then hold one value in every row and the kernel reads them once per
            wavefront (16 B per entity-tick less at configs[1]).  Not for a Monte-Carlo of worlds stacked in one executor."""
