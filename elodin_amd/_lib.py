@@ -31,6 +31,11 @@ QUANTILE_ASYNC = 1   # sixdof_history_quantiles flags
 QUANTILE_MAX_RANKS = 16   # ranks one call selects (SIXDOF_QUANTILE_MAX_RANKS)
 EXTREMES_ASYNC, EXTREMES_CONTINUE, EXTREMES_HOLD = 1, 2, 4   # sixdof_history_extremes flags
 EXTREMES_PLANES = 6       # count, min, tick_min, max, tick_max, first_nonfinite (SIXDOF_EXTREMES_PLANES)
+EVENT_LT, EVENT_LE, EVENT_GT, EVENT_GE = 0, 1, 2, 3   # sixdof_event_trigger.op
+EVENT_LEVEL, EVENT_CROSSING = 0, 1                    # sixdof_event_trigger.mode
+EVENTS_ASYNC, EVENTS_CONTINUE, EVENTS_HOLD = 1, 2, 4  # sixdof_history_events flags
+EVENTS_PLANES = 4         # tick, value, tick_before, value_before (SIXDOF_EVENTS_PLANES)
+EVENTS_MAX_TRIGGERS = 8   # triggers one call walks (SIXDOF_EVENTS_MAX_TRIGGERS)
 
 EFF_CONST_WRENCH = 1
 EFF_UNIFORM_GRAVITY = 2
@@ -69,6 +74,11 @@ class Timings(C.Structure):
     _fields_ = [("h2d_upload_ms", C.c_double), ("kernel_invoke_ms", C.c_double), ("d2h_download_ms", C.c_double),
                 ("kernel_device_ms", C.c_double), ("launches", C.c_uint64), ("ticks", C.c_uint64),
                 ("kernel_sum_ms", C.c_double), ("graph_launches", C.c_uint64)]
+
+
+class EventTrigger(C.Structure):   # sixdof_event_trigger, 32 bytes
+    _fields_ = [("component_id", C.c_uint64), ("element", C.c_uint32), ("group", C.c_uint32), ("op", C.c_uint32), ("mode", C.c_uint32),
+                ("level", C.c_double)]
 
 
 class Slot(C.Structure):
@@ -151,6 +161,8 @@ SYMBOLS = {
                                            C.POINTER(C.c_uint32), C.c_uint32, C.c_size_t, C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_history_extremes": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p),
                                           C.c_uint32]),
+    "sixdof_history_events": (C.c_int, [_H, C.POINTER(EventTrigger), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64,
+                                        C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_set_model_apollo": (C.c_int, [_H, C.c_void_p]),
     "sixdof_download_column": (C.c_int, [_H, C.c_uint64]),
     "sixdof_upload_column": (C.c_int, [_H, C.c_uint64]),

@@ -878,6 +878,40 @@ class Exec:
             out[comp] = d
         return out
 
+    def history_events(self, events, capture, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> Dict[str, Any]:
+        """At what tick did each run reach a condition, and what was its state there: {"tick", "tick_before": int64 [T, runs];
+        "value", "value_before", "t", "t_before", "t_cross": f64 [T, runs]; "capture": {component: f64 [T, rows, w]}} for the T
+        events (elodin_amd.Event) over world ticks first_tick, first_tick + every, ... <= last_tick, found on the device out of the
+        ring (enable_history).  A run is `period` consecutive executor rows.  tick is the first sampled world tick at which the
+        event's element meets its threshold (0: never; value, t and the run's captured rows are then NaN), tick_before the
+        finite sample before it (0: none).  t and t_before are seconds.  t_cross is the time at which the straight line from
+        (t_before, value_before) to (t, value) passes the event's level, evaluated here on the host; it equals t where there is
+        no sample before or the two values are equal."""
+        evs = [events] if not isinstance(events, (list, tuple)) else list(events)
+        caps = [capture] if isinstance(capture, str) else list(capture)
+        for comp in [e.component for e in evs] + caps:
+            self._refuse_unrecorded("history_events", comp, comp)
+        (first, last, step), _ = self._sampled_ticks("history_events", first_tick, last_tick, every)
+        s = getattr(self, "_substeps", 1)
+        out: Dict[str, Any] = dict(self._hip.history_events(evs, caps, first, last, step, period))
+        for tick_field, seconds in (("tick", "t"), ("tick_before", "t_before")):
+            out[tick_field] = out[tick_field] // s          # exact: every sample is a multiple of the sub-step count
+            out[seconds] = np.where(out[tick_field] == 0, np.nan, out[tick_field].astype(np.float64) * self._dt)
+        out["t_cross"] = self._crossing_time(np.array([float(e.level) for e in evs]), out)
+        return out
+
+    @staticmethod
+    def _crossing_time(levels, ev) -> np.ndarray:
+        """[T, runs] seconds: where the line through (t_before, value_before) and (t, value) meets the event's level; t where
+        there is no sample before or the line is flat."""
+        t, t0, v, v0 = ev["t"], ev["t_before"], ev["value"], ev["value_before"]
+        usable = (ev["tick_before"] != 0) & (v != v0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            frac = (levels[:, None] - v0) / (v - v0)
+            # the sample before does not meet the level and the event does, so frac is in [0, 1]; the clamp only takes off what
+            # the last rounding may add beyond t
+            return np.where(usable, np.minimum(np.maximum(t0 + frac * (t - t0), t0), t), t)
+
     def column_ids(self, name: str) -> np.ndarray:
         """Entity id of each row of column_array(name)."""
         n = len(self._main_column_array(name))

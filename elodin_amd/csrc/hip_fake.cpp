@@ -20,6 +20,7 @@
 #include "../../include/sixdof_hip.h"
 #include "aql_chain.hpp"
 #include "envelope_plan.hpp"
+#include "events_plan.hpp"
 #include "extremes_plan.hpp"
 #include "history_plan.hpp"
 #include "kernels.hpp"
@@ -405,6 +406,83 @@ hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, 
             return launch(false);
         if (elem == 8) extremes_of_component<double>(d, out, static_cast<uint64_t*>(scratch), scratch_stride, segments, merge_into, n, first_tick, n_samples, every, ring);
         else extremes_of_component<float>(d, out, static_cast<uint64_t*>(scratch), scratch_stride, segments, merge_into, n, first_tick, n_samples, every, ring);
+    }
+    return launch(true);
+}
+// the walk, the merge and the capture themselves (events_kernels.hip), serially: events_plan.hpp's rule in the kernels' segmentation
+// — with more than one segment every (segment, trigger, run) record goes through the launch's scratch, as on the device
+template <class E>
+static void events_of_trigger(const EventsTrigger& t, uint32_t trig, uint32_t n_triggers, uint64_t* rec, double* out, uint64_t* scratch, uint32_t segments,
+                              bool merge_into, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
+    const uint64_t runs = n / period, total = n * t.w, step = every % ring;
+    for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
+        const uint64_t lo = extremes_segment_start(n_samples, segments, seg), hi = extremes_segment_start(n_samples, segments, seg + 1);
+        for (uint64_t run = 0; run < runs; run++) {
+            uint64_t slot = sample_slot(first_tick, lo, every, ring), tick = first_tick + lo * every;
+            uint64_t* mine = rec + uint64_t(trig) * kEventsFields * runs + run;
+            EventsRecord r = segments == 1 && merge_into ? events_load(mine, runs) : events_empty();
+            for (uint64_t j = lo; j < hi && !events_settled(r, t.mode); j++, tick += every, slot = next_sample_slot(slot, step, ring)) {
+                E x;
+                std::memcpy(&x, static_cast<const char*>(t.ring) + (slot * total + (run * period + t.group) * t.w + t.element) * sizeof(E), sizeof(E));
+                events_sample<E>(r, x, tick, t.op, t.level);
+            }
+            if (segments == 1) {
+                events_store(r, mine, runs);
+                events_emit<E>(r, t.mode, out + uint64_t(trig) * kEventsPlanes * runs + run, runs);
+            } else {
+                events_store(r, scratch + (uint64_t(seg) * n_triggers + trig) * kEventsFields * runs + run, runs);
+            }
+        }
+    }
+    for (uint64_t run = 0; segments > 1 && run < runs; run++) {            // stage 2
+        uint64_t* mine = rec + uint64_t(trig) * kEventsFields * runs + run;
+        EventsRecord r = merge_into ? events_load(mine, runs) : events_empty();
+        for (uint32_t s = 0; s < segments; s++) r = events_merge(r, events_load(scratch + (uint64_t(s) * n_triggers + trig) * kEventsFields * runs + run, runs));
+        events_store(r, mine, runs);
+        events_emit<E>(r, t.mode, out + uint64_t(trig) * kEventsPlanes * runs + run, runs);
+    }
+}
+hipError_t launch_history_events(const EventsArgs& a, uint32_t n_triggers, void* rec, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n,
+                                 uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t) {
+    if (!events_launch_ok(a, n_triggers, n, period, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
+    if (n == 0) return launch(true);
+    const uint64_t units = n / period * n_triggers;
+    if (segments > 1 && !need(live(scratch, events_scratch_bytes(segments, units)), "events scratch records")) return launch(false);
+    if (!need(live(rec, events_record_bytes(units)) && live(out, units * kEventsPlanes * sizeof(double)), "events records or staging")) return launch(false);
+    for (uint32_t k = 0; k < n_triggers; k++) {
+        const EventsTrigger& t = a.t[k];
+        if (!need(live(t.ring, ring * n * t.w * elem), "ring of a trigger")) return launch(false);
+        uint64_t *r = static_cast<uint64_t*>(rec), *sc = static_cast<uint64_t*>(scratch);
+        if (elem == 8) events_of_trigger<double>(t, k, n_triggers, r, out, sc, segments, merge_into, n, period, first_tick, n_samples, every, ring);
+        else events_of_trigger<float>(t, k, n_triggers, r, out, sc, segments, merge_into, n, period, first_tick, n_samples, every, ring);
+    }
+    return launch(true);
+}
+hipError_t launch_events_capture(const EventsArgs& a, uint32_t n_triggers, const RingBinArgs& c, uint32_t n_captures, const void* rec, double* out, bool merge_into,
+                                 uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t) {
+    uint32_t widths[kRingBinMaxComponents] = {};
+    for (uint32_t k = 0; k < n_captures && k < kRingBinMaxComponents; k++) widths[k] = c.c[k].w;
+    if (!events_capture_ok(a, n_triggers, n_captures, kRingBinMaxComponents, widths, n, period, first_tick, n_samples, every) || ring == 0) return launch(false);
+    if (n == 0) return launch(true);
+    const uint64_t runs = n / period, last = first_tick + (n_samples - 1) * every;
+    const uint64_t* r = static_cast<const uint64_t*>(rec);
+    if (!need(live(rec, events_record_bytes(runs * n_triggers)), "events records")) return launch(false);
+    for (uint32_t k = 0; k < n_captures; k++) {
+        const RingBinDesc& d = c.c[k];
+        const uint64_t total = n * d.w;
+        if (!need(live(d.ring, ring * total * elem) && live(out + d.out_offset, n_triggers * total * sizeof(double)), "ring or capture staging")) return launch(false);
+        for (uint32_t trig = 0; trig < n_triggers; trig++)
+            for (uint64_t i = 0; i < total; i++) {
+                const uint64_t tick = events_stored_tick(r + uint64_t(trig) * kEventsFields * runs + i / d.w / period, runs, a.t[trig].mode);
+                double* o = out + d.out_offset + uint64_t(trig) * total + i;
+                if (events_tick_sampled(tick, first_tick, last, every)) {
+                    const char* from = static_cast<const char*>(d.ring) + (history_slot(tick, ring) * total + i) * elem;
+                    if (elem == 8) std::memcpy(o, from, 8);
+                    else { float f; std::memcpy(&f, from, 4); *o = f; }
+                } else if (!merge_into) {
+                    *o = __builtin_nan("");
+                }
+            }
     }
     return launch(true);
 }

@@ -1,8 +1,8 @@
 // history_plan.hpp — where a recorded tick sits in the telemetry ring, and which sampled ranges can be read from it.  Pure
 // arithmetic, no HIP.  Every reader of the ring validates with it — sixdof_history_read, sixdof_history_stream,
-// sixdof_watch_read, sixdof_history_envelope, sixdof_history_quantiles, sixdof_history_extremes (sixdof_capi.cpp) — and everything that touches a slot
+// sixdof_watch_read, sixdof_history_envelope, sixdof_history_quantiles, sixdof_history_extremes, sixdof_history_events (sixdof_capi.cpp) — and everything that touches a slot
 // addresses with it: those readers, snapshot_tick_to_ring and sixdof_step's overwrite check on the host, history_gather_kernel (join_kernels.hip) and
-// the envelope, quantile and extremes kernels (envelope_kernels.hip, quantile_kernels.hip, extremes_kernels.hip) on the device, the fake runtime's
+// the envelope, quantile, extremes and events kernels (envelope_kernels.hip, quantile_kernels.hip, extremes_kernels.hip, events_kernels.hip) on the device, the fake runtime's
 // launchers (hip_fake.cpp).
 // history_plan_test.cpp checks it on the host.
 #pragma once
@@ -28,7 +28,7 @@ SIXDOF_HOST_DEVICE inline uint64_t sample_slot(uint64_t first_tick, uint64_t j, 
 }
 
 // The slot of the sample after the one in `slot`, without a division: step = every % ring.  What a thread that walks a whole
-// range calls per sample (extremes_kernels.hip); equal to sample_slot of the next index.
+// range calls per sample (extremes_kernels.hip, events_kernels.hip); equal to sample_slot of the next index.
 SIXDOF_HOST_DEVICE inline uint64_t next_sample_slot(uint64_t slot, uint64_t step, uint64_t ring) {
     slot += step;     // both below ring <= 2^32
     return slot >= ring ? slot - ring : slot;

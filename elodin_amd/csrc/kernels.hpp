@@ -204,6 +204,23 @@ hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, 
                                    uint32_t segments, bool merge_into, uint64_t n, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                                    uint64_t ring, size_t elem, hipStream_t s);
 
+// ---- ring events: per trigger and run, the first threshold crossing over the sampled ticks and the state there (events_kernels.hip) ---
+struct EventsArgs;   // events_plan.hpp: the triggers (ring base, width, element, group, op, mode, level) of one launch, at most 8
+// All n_samples samples of the range first_tick, first_tick + every, ... in `segments` time segments (events_plan.hpp).  `rec`:
+// the records, [n_triggers][10][runs] 64-bit words with runs = n / period, written by every launch and read first when merge_into
+// (they then hold the samples before this range, and the result covers both); `out`: the four planes, [n_triggers][4][runs]
+// doubles; with more than one segment `scratch` holds segments * n_triggers * 10 * runs words.  The caller has validated the range
+// (sampled_range_ok, extremes_ticks_ok) and the triggers (events_launch_ok).
+hipError_t launch_history_events(const EventsArgs& a, uint32_t n_triggers, void* rec, double* out, void* scratch, uint32_t segments, bool merge_into,
+                                 uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem,
+                                 hipStream_t s);
+// After it, on the same stream: for at most kRingBinMaxComponents captured components (c: ring, width and out_offset, where the
+// component's [n_triggers][n * w] doubles start in `out`), the ring's elements at the tick `rec` reports for the element's run,
+// where that tick is one of this range's samples; elsewhere NaN, or (merge_into) what `out` held.
+hipError_t launch_events_capture(const EventsArgs& a, uint32_t n_triggers, const RingBinArgs& c, uint32_t n_captures, const void* rec, double* out,
+                                 bool merge_into, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring,
+                                 size_t elem, hipStream_t s);
+
 hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags,
                             unsigned long long* count, hipStream_t s);
 

@@ -31,6 +31,7 @@
 #include "device_mem.hpp"
 #include "aql_chain.hpp"
 #include "envelope_plan.hpp"
+#include "events_plan.hpp"
 #include "extremes_plan.hpp"
 #include "quantile_plan.hpp"
 #include "history_plan.hpp"
@@ -170,6 +171,19 @@ struct History {
         uint64_t n = 0;
         uint64_t last_tick = 0;              // the last tick accumulated
     } extremes;
+    // sixdof_history_events: its records and its staging (the event planes and the captures), which together are the accumulator a
+    // SIXDOF_EVENTS_CONTINUE call merges into, and the segment records of one launch; the same rules.
+    DeviceBuffer ev_rec, ev_stage, ev_scratch;
+    struct Events {
+        bool valid = false;
+        std::vector<sixdof_event_trigger> triggers;   // field for field
+        std::vector<uint64_t> capture_ids;
+        std::vector<const void*> rings;               // ring base and width of every trigger, then of every capture, as they were
+        std::vector<size_t> widths;
+        uint64_t n = 0;
+        uint32_t period = 0;
+        uint64_t last_tick = 0;                       // the last tick accumulated
+    } events;
     void reset() { *this = History{}; }
 };
 
@@ -489,6 +503,7 @@ int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_co
     if (!h || (!cols && n_cols)) return SIXDOF_ERR_INVALID_ARGUMENT;
     h->bound = h->resident = false;   // until the end of this call: a failed bind leaves the handle unbound
     h->hist.extremes.valid = false;   // the rows an extremes accumulator covers may be other rows from here on
+    h->hist.events.valid = false;     // and those of an events accumulator
     HIP_TRY(h, hipSetDevice(h->device));
     h->replay.drop();
     if (h->d_watch_rows) {      // a watch holds rows of the join this call replaces
@@ -1406,7 +1421,7 @@ int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_c
 
 // A read whose results are computed on the compute stream, out of the ring into a device staging buffer, and brought from
 // there to the caller's buffers, blocking or over the copy lane: sixdof_watch_read and, through ring_bin_read below,
-// sixdof_history_envelope and sixdof_history_quantiles, and sixdof_history_extremes.  The lane and the rules of the staging buffer live here and nowhere
+// sixdof_history_envelope and sixdof_history_quantiles, and sixdof_history_extremes and sixdof_history_events.  The lane and the rules of the staging buffer live here and nowhere
 // in the callers: add() the components, claim() the buffers, launch into them, deliver().
 struct StagedRead {
     // one component: ring base and width as they are NOW, its block in the staging buffer (256-byte aligned), where it goes
@@ -1427,6 +1442,11 @@ struct StagedRead {
         stage_bytes += (p.bytes + 255) / 256 * 256;
         parts.push_back(p);
         return SIXDOF_OK;
+    }
+    // a block of the staging buffer that belongs to no component (sixdof_history_events: the event planes)
+    void add_block(void* host, size_t bytes) {
+        parts.push_back(Part{nullptr, 1, bytes, stage_bytes, host});
+        stage_bytes += (bytes + 255) / 256 * 256;
     }
     // After this the compute stream may write the staging buffer, large enough for every part, and `scratch` (if any) of at
     // least scratch_bytes.  A buffer that could not be grown is left empty: the next read allocates it again.
@@ -1718,6 +1738,113 @@ int sixdof_history_extremes(sixdof_handle* h, const uint64_t* component_ids, siz
     acc.rings.clear(), acc.widths.clear();
     for (const StagedRead::Part& p : rd.parts) acc.rings.push_back(p.ring), acc.widths.push_back(p.w);
     acc.n = n;
+    acc.last_tick = first_tick + (n_samples - 1) * every;
+    acc.valid = true;
+    return SIXDOF_OK;
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// The first event of every run per trigger, and the rows of the captured components at it.  Ordering, ring reads, the copy lane
+// and commit on success exactly as for sixdof_history_extremes above.  One walk (and merge) launch covers all triggers; one capture
+// launch behind it covers at most kRingBinMaxComponents captured components.  The accumulator is the record buffer (ev_rec: what
+// the rule continues from) together with the staging buffer (ev_stage: the event planes, rewritten by every call, and the
+// captures, of which a continuing call rewrites only the runs whose event it saw).
+int sixdof_history_events(sixdof_handle* h, const sixdof_event_trigger* triggers, size_t n_triggers, const uint64_t* capture_ids,
+                          size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
+                          double* event_dst, double* const capture_dst[], uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    const std::string who = "history_events";
+    if (flags & ~(SIXDOF_EVENTS_ASYNC | SIXDOF_EVENTS_CONTINUE | SIXDOF_EVENTS_HOLD)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": unknown flags");
+    History& hs = h->hist;
+    if (!hs.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": no history ring (sixdof_set_history)");
+    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": every must be at least 1");
+    if (n_triggers == 0 || n_triggers > SIXDOF_EVENTS_MAX_TRIGGERS)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(n_triggers) + " triggers, 1 to " + std::to_string(SIXDOF_EVENTS_MAX_TRIGGERS) + " can be asked for");
+    if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
+    const uint64_t n = h->desc.n_entities;
+    if (n % period != 0)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+    const bool hold = (flags & SIXDOF_EVENTS_HOLD) != 0, merge_into = (flags & SIXDOF_EVENTS_CONTINUE) != 0;
+    if (!triggers || (n_captures && !capture_ids) || (!hold && (!event_dst || (n_captures && !capture_dst))))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
+    EventsArgs a{};
+    for (size_t k = 0; k < n_triggers; k++) {
+        const sixdof_event_trigger& t = triggers[k];
+        const std::string which = who + ": trigger " + std::to_string(k);
+        if (t.op > SIXDOF_EVENT_GE) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown op " + std::to_string(t.op));
+        if (t.mode > SIXDOF_EVENT_CROSSING) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown mode " + std::to_string(t.mode));
+        if (!std::isfinite(t.level)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": the level is not finite");
+        if (t.group >= period) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": group " + std::to_string(t.group) + " is not below period " + std::to_string(period));
+        size_t w = 0;
+        if (!watch_lookup(h, t.component_id, &a.t[k].ring, &w) || !a.t[k].ring)
+            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, which + ": only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
+        if (t.element >= w) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": element " + std::to_string(t.element) + " is not below the component's width " + std::to_string(w));
+        a.t[k].level = t.level, a.t[k].w = static_cast<uint32_t>(w), a.t[k].element = t.element, a.t[k].group = t.group, a.t[k].op = t.op, a.t[k].mode = t.mode;
+    }
+    if (n_samples == 0) return SIXDOF_OK;
+    if (!sampled_range_ok(first_tick, n_samples, every, hs.first_tick, h->tick, hs.ring))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": ticks are not (all) in the ring");
+    if (!extremes_ticks_ok(first_tick, n_samples, every))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": a sampled tick of 2^53 or more has no double of its own");
+    const uint64_t runs = n / period, units = runs * n_triggers;
+    StagedRead rd{h, "history_events", &hs.ev_stage};
+    rd.add_block(hold ? nullptr : event_dst, static_cast<size_t>(units) * kEventsPlanes * sizeof(double));
+    for (size_t k = 0; k < n_captures; k++) {
+        const int rc = rd.add(capture_ids[k], hold ? nullptr : capture_dst[k], static_cast<size_t>(n) * n_triggers, sizeof(double),
+                              "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded", !hold);
+        if (rc != SIXDOF_OK) return rc;
+    }
+    History::Events& acc = hs.events;
+    if (merge_into) {
+        bool same = acc.valid && acc.n == n && acc.period == period && acc.triggers.size() == n_triggers && acc.capture_ids.size() == n_captures &&
+                    std::equal(acc.capture_ids.begin(), acc.capture_ids.end(), capture_ids);
+        for (size_t k = 0; same && k < n_triggers; k++) {
+            const sixdof_event_trigger &p = acc.triggers[k], &t = triggers[k];
+            same = p.component_id == t.component_id && p.element == t.element && p.group == t.group && p.op == t.op && p.mode == t.mode &&
+                   std::memcmp(&p.level, &t.level, sizeof(double)) == 0 && acc.rings[k] == a.t[k].ring && acc.widths[k] == a.t[k].w;
+        }
+        for (size_t k = 0; same && k < n_captures; k++) same = acc.rings[n_triggers + k] == rd.parts[1 + k].ring && acc.widths[n_triggers + k] == rd.parts[1 + k].w;
+        if (!same)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": SIXDOF_EVENTS_CONTINUE: there is no accumulator of these triggers, captures, period, rows and rings to continue "
+                                                              "(the previous call failed or read something else, or the ring, the columns or the program were replaced since)");
+        if (first_tick <= acc.last_tick)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": SIXDOF_EVENTS_CONTINUE: first_tick " + std::to_string(first_tick) + " is not above tick " +
+                                                              std::to_string(acc.last_tick) + ", the last one accumulated");
+    }
+    const char* forced_env = std::getenv("SIXDOF_EVENTS_SEGMENTS");   // 0 or unset: the plan's choice (A/B runs, tests)
+    const uint64_t forced = forced_env ? std::strtoull(forced_env, nullptr, 10) : 0;
+    constexpr uint64_t kScratchBudget = uint64_t(64) << 20;
+    uint32_t segments = forced ? extremes_clamp_segments(forced, n_samples) : events_segments(units, n_samples);
+    segments = events_fit_segments(segments, units, kScratchBudget);
+    HIP_TRY(h, hipSetDevice(h->device));
+    acc.valid = false;
+    if (int rc = rd.claim(&hs.ev_scratch, static_cast<size_t>(events_scratch_bytes(segments, units))); rc != SIXDOF_OK) return rc;
+    if (events_record_bytes(units) > hs.ev_rec.bytes()) {   // never for a continuing call: its records are as large as the accumulator's
+        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));   // an earlier call's launches may still use the old buffer
+        HIP_TRY(h, hs.ev_rec.alloc(static_cast<size_t>(events_record_bytes(units))));
+    }
+    const uint32_t nt = static_cast<uint32_t>(n_triggers);
+    hipError_t e = launch_history_events(a, nt, hs.ev_rec.get(), hs.ev_stage.get<double>(), hs.ev_scratch.get(), segments, merge_into, n, period, first_tick,
+                                         n_samples, every, hs.ring, h->elem_size(), h->stream.get());
+    if (e != hipSuccess) return h->hip_fail(e, "history_events");
+    for (size_t k0 = 0; k0 < n_captures; k0 += kRingBinMaxComponents) {
+        const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_captures - k0));
+        RingBinArgs c{};
+        for (uint32_t k = 0; k < cnt; k++) {
+            const StagedRead::Part& p = rd.parts[1 + k0 + k];
+            c.c[k].ring = p.ring, c.c[k].out_offset = p.offset / sizeof(double), c.c[k].w = static_cast<uint32_t>(p.w);
+        }
+        e = launch_events_capture(a, nt, c, cnt, hs.ev_rec.get(), hs.ev_stage.get<double>(), merge_into, n, period, first_tick, n_samples, every, hs.ring,
+                                  h->elem_size(), h->stream.get());
+        if (e != hipSuccess) return h->hip_fail(e, "history_events capture");
+    }
+    if (!hold)
+        if (int rc = rd.deliver((flags & SIXDOF_EVENTS_ASYNC) != 0); rc != SIXDOF_OK) return rc;
+    acc.triggers.assign(triggers, triggers + n_triggers);
+    acc.capture_ids.assign(capture_ids, capture_ids + n_captures);
+    acc.rings.clear(), acc.widths.clear();
+    for (uint32_t k = 0; k < nt; k++) acc.rings.push_back(a.t[k].ring), acc.widths.push_back(a.t[k].w);
+    for (size_t k = 0; k < n_captures; k++) acc.rings.push_back(rd.parts[1 + k].ring), acc.widths.push_back(rd.parts[1 + k].w);
+    acc.n = n, acc.period = period;
     acc.last_tick = first_tick + (n_samples - 1) * every;
     acc.valid = true;
     return SIXDOF_OK;

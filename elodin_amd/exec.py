@@ -52,6 +52,22 @@ class TickTimings:  # profile.rs TickTimings
 
 
 @dataclass(frozen=True)
+class Event:
+    """One trigger of HipExec.history_events: element `element` of `component` in row `group` of every run meets `op level`.
+    mode "level": the earliest finite sample at which it does; "crossing": the earliest at which it does and the previous finite
+    sample did not (a condition that holds from the first sample on never fires)."""
+    component: str
+    element: int
+    op: str                 # "<", "<=", ">" or ">="
+    level: float
+    mode: str = "crossing"
+    group: int = 0
+
+    OPS = {"<": L.EVENT_LT, "<=": L.EVENT_LE, ">": L.EVENT_GT, ">=": L.EVENT_GE}
+    MODES = {"level": L.EVENT_LEVEL, "crossing": L.EVENT_CROSSING}
+
+
+@dataclass(frozen=True)
 class _Reduction:
     """One reduction over the ring into (group, element) bins, as HipExec._reduce and _stream_reduce call it."""
     fn: str                 # the library entry point
@@ -779,6 +795,95 @@ class HipExec:
             self.set_flags(flags)
             self.sync()
         return time.perf_counter() - t0, self._extremes_dict(names, raw)
+
+    # ---- ring events: the first threshold crossing of every run, and the state there -----------------------------------
+    EVENTS_FIELDS = ("tick", "value", "tick_before", "value_before")      # the four planes, in order
+
+    @staticmethod
+    def _events_dict(capture_names, raw_events, raw_captures) -> dict:
+        """A [T, 4, runs] block and one [T, n, w] block per captured name -> {"tick", "tick_before": int64 [T, runs]; "value",
+        "value_before": f64 [T, runs]; "capture": {name: f64 [T, n, w]}}.  The tick planes arrive as doubles below 2^53: the
+        conversion is exact."""
+        out = {k: raw_events[:, i] if k.startswith("value") else raw_events[:, i].astype(np.int64) for i, k in enumerate(HipExec.EVENTS_FIELDS)}
+        out["capture"] = dict(zip(capture_names, raw_captures))
+        return out
+
+    @staticmethod
+    def _event_triggers(events):
+        """The ctypes array of sixdof_event_trigger for a list of Event, or its ValueError."""
+        events = [events] if isinstance(events, Event) else list(events)
+        if not 1 <= len(events) <= L.EVENTS_MAX_TRIGGERS:
+            raise ValueError(f"history_events: {len(events)} events, 1 to {L.EVENTS_MAX_TRIGGERS} can be asked for")
+        arr = (L.EventTrigger * len(events))()
+        for t, e in zip(arr, events):
+            if e.op not in Event.OPS or e.mode not in Event.MODES:
+                raise ValueError(f"history_events: {e!r}: op is one of {list(Event.OPS)}, mode one of {list(Event.MODES)}")
+            t.component_id, t.element, t.group = L.component_id(e.component), int(e.element), int(e.group)
+            t.op, t.mode, t.level = Event.OPS[e.op], Event.MODES[e.mode], float(e.level)
+        return arr
+
+    def _events_buffers(self, n_events: int, capture, period: int):
+        """The [T, 4, runs] block and one [T, n, w] block per captured name, holding what a range without samples gives: no event."""
+        raw = np.zeros((n_events, L.EVENTS_PLANES, self.n // max(period, 1)), dtype=np.float64)
+        raw[:, 1], raw[:, 3] = np.nan, np.nan
+        caps = [np.full((n_events, self.n, self._recorded_width(name)), np.nan, dtype=np.float64) for name in capture]
+        return raw, caps, (C.c_void_p * max(1, len(caps)))(*[a.ctypes.data for a in caps])
+
+    def _events_read(self, triggers, comp, period: int, first_tick: int, n_samples: int, every: int, raw, ptrs, flags: int) -> None:
+        rc = self._lib.sixdof_history_events(self._h, triggers, len(triggers), comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), period, first_tick,
+                                             n_samples, every, None if raw is None else raw.ctypes.data, ptrs, flags)
+        if rc != L.OK:
+            _raise(self._h, rc, "sixdof_history_events")
+
+    def history_events(self, events, capture: Sequence[str], first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> dict:
+        """{"tick", "tick_before": int64 [T, runs]; "value", "value_before": f64 [T, runs]; "capture": {name: f64 [T, n, w]}}: per
+        Event and run (period consecutive rows; runs = n // period), over the ticks first_tick, first_tick + every, ... <=
+        last_tick, the first sampled tick at which the event's element meets its threshold, the element's value there, and tick
+        and value of the finite sample before — found on the device out of the ring.  capture[name][e, r] is row r of `name` at
+        the event tick of r's run for event e.  tick 0 means no event: value and the run's captured rows are then NaN;
+        tick_before 0 means no sample before it.  Non-finite samples are skipped.  Stateless: no watch is involved."""
+        triggers = self._event_triggers(events)
+        capture = [capture] if isinstance(capture, str) else list(capture)
+        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
+        raw, caps, ptrs = self._events_buffers(len(triggers), capture, period)
+        comp = np.array([L.component_id(n) for n in capture], dtype=np.uint64)
+        self._events_read(triggers, comp, max(period, 0), first_tick, self._sample_count(first_tick, last_tick, every), every, raw, ptrs, 0)
+        return self._events_dict(capture, raw, caps)
+
+    def stream_events(self, events, capture: Sequence[str], n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, flags: int = 0):
+        """history_events over a run longer than the ring: n_batches batches of ticks_per_batch ticks are stepped, and after every
+        batch its samples — every `every`-th tick, ending on the batch's last — are merged into the accumulator on the device
+        (SIXDOF_EVENTS_HOLD, SIXDOF_EVENTS_CONTINUE from the second batch on); a run's rows are captured in the batch that sees its
+        event.  Nothing crosses the link until the last batch's call delivers.  The ring is read on the compute stream, so a ring
+        one batch deep is enough (enabled here unless enable_history already made one at least that large).  Returns (wall time
+        in seconds, the dict of history_events); whatever happens, the caller's flags are restored and the handle is drained."""
+        import time
+        triggers = self._event_triggers(events)
+        capture = [capture] if isinstance(capture, str) else list(capture)
+        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
+        n_samples = self._stream_shape("stream_events", ticks_per_batch, every)
+        if n_batches < 1:
+            raise ValueError("stream_events: at least one batch")
+        if period < 1:
+            raise ValueError("stream_events: period must be at least 1")
+        raw, caps, ptrs = self._events_buffers(len(triggers), capture, period)
+        comp = np.array([L.component_id(n) for n in capture], dtype=np.uint64)
+        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
+            self.enable_history(ticks_per_batch)
+        self.sync()              # nothing of an earlier streaming run is in flight
+        self.set_flags(flags | L.FLAG_ASYNC_STEP)
+        t0 = time.perf_counter()
+        try:
+            for i in range(n_batches):
+                first = self.tick + every                                # samples end on the batch's last tick
+                self.invoke_batch(ticks_per_batch)
+                last = i + 1 == n_batches
+                self._events_read(triggers, comp, period, first, n_samples, every, raw if last else None, ptrs if last else None,
+                                  (L.EVENTS_CONTINUE if i else 0) | (0 if last else L.EVENTS_HOLD))
+        finally:
+            self.set_flags(flags)
+            self.sync()
+        return time.perf_counter() - t0, self._events_dict(capture, raw, caps)
 
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))

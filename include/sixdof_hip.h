@@ -531,6 +531,62 @@ int sixdof_history_quantiles(sixdof_handle* h, const uint64_t* component_ids, si
 int sixdof_history_extremes(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
                             uint64_t n_samples, uint64_t every, double* const host_dst[], uint32_t flags);
 
+/* ---- ring events: the first threshold crossing of every run and the state there ------------------------------------------
+ * What a campaign's results table asks most often: at what tick did this run reach a condition — touchdown, apogee, burn-out,
+ * leaving a corridor — and what was its state at that tick.  The tick differs per run and the ring is overwritten batch by batch,
+ * so event and state are found and captured on the device, in the call that sees the event.
+ *
+ * A run is `period` consecutive rows (n_entities % period == 0; runs = n_entities / period).  A trigger reads element `element`
+ * of component `component_id` in row run * period + group of every run.  Its predicate is x op level: an IEEE compare of the
+ * ring's element, widened to double (exact for an f32 handle), against a finite level, so -0.0 equals +0.0.  A non-finite sample
+ * is skipped as if it had not been sampled: it neither holds nor fails and is never a "before" sample.  SIXDOF_EVENT_LEVEL: the
+ * event is the earliest finite sample at which the predicate holds.  SIXDOF_EVENT_CROSSING: the earliest finite sample at which it
+ * holds and the previous finite sample did not; a predicate that holds from the first sample on never fires.
+ *
+ * Samples are the ticks first_tick, first_tick + every, ... (n_samples of them), all in the ring.  event_dst is
+ * [n_triggers][SIXDOF_EVENTS_PLANES][runs] doubles, plane-major: the event tick (0: none), the element's value at it (NaN: none),
+ * the tick of the finite sample before it (0: none — also where a LEVEL event fell on the first finite sample) and that sample's
+ * value (NaN: none).  capture_dst[k] is [n_triggers][n_entities][w_k] doubles: every row of component capture_ids[k] at the event
+ * tick of the row's run for that trigger, NaN where the run has no event; n_captures = 0 reports the events only.  Ticks are
+ * exact in doubles: a range whose last sampled tick is 2^53 or more is refused.  No floating-point arithmetic beyond the compare
+ * and the widening and no atomics: the rule is exact and associative in time order, so every output is bit-identical however the
+ * range is cut into time segments (SIXDOF_EVENTS_SEGMENTS in the environment forces a count; 0 or unset: the library's choice),
+ * launches or calls.
+ * SIXDOF_EVENTS_HOLD: reduce and keep the result in the device accumulator (the records and the call's staging buffer, freed
+ * with the ring); nothing is delivered, event_dst and capture_dst are ignored.  SIXDOF_EVENTS_CONTINUE: merge into the
+ * accumulator the previous successful call left instead of starting afresh; a capture taken by an earlier call stays.  Accepted
+ * only if the previous call succeeded with the same triggers field for field, the same capture ids in the same order and the
+ * same period, ring bases, widths and row count are unchanged, no sixdof_set_history or sixdof_bind_columns came since, and
+ * first_tick is above the last tick accumulated; otherwise SIXDOF_ERR_INVALID_ARGUMENT and the accumulator stays as it was.
+ * SIXDOF_EVENTS_ASYNC: the rules of SIXDOF_WATCH_ASYNC.  Either way the ring is read on the compute stream: a later sixdof_step
+ * may overwrite the slots at once, and a ring one batch deep is enough.
+ * n_samples = 0 is a no-op that leaves the accumulator alone.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied and the
+ * accumulator as it was: no ring, every = 0, a sampled tick that is not (or no longer) in the ring or is 2^53 or more, unknown
+ * flags, a null triggers, a null capture_ids with n_captures > 0, a null event_dst, capture_dst or buffer without
+ * SIXDOF_EVENTS_HOLD, n_triggers = 0 or above SIXDOF_EVENTS_MAX_TRIGGERS, period = 0 or not dividing n_entities, group >= period,
+ * element >= the component's width, an unknown op or mode, a level that is not finite.  A trigger or capture component the ring
+ * does not record: SIXDOF_ERR_COMPONENT_NOT_FOUND.  A call that fails in the runtime leaves the ring as it was and the
+ * accumulator invalid, as for sixdof_history_extremes. */
+typedef struct sixdof_event_trigger {   /* 32 bytes */
+    uint64_t component_id;
+    uint32_t element, group, op, mode;
+    double level;
+} sixdof_event_trigger;
+#define SIXDOF_EVENT_LT 0u
+#define SIXDOF_EVENT_LE 1u
+#define SIXDOF_EVENT_GT 2u
+#define SIXDOF_EVENT_GE 3u
+#define SIXDOF_EVENT_LEVEL    0u
+#define SIXDOF_EVENT_CROSSING 1u
+#define SIXDOF_EVENTS_ASYNC    1u
+#define SIXDOF_EVENTS_CONTINUE 2u
+#define SIXDOF_EVENTS_HOLD     4u
+#define SIXDOF_EVENTS_PLANES   4
+#define SIXDOF_EVENTS_MAX_TRIGGERS 8
+int sixdof_history_events(sixdof_handle* h, const sixdof_event_trigger* triggers, size_t n_triggers, const uint64_t* capture_ids,
+                          size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
+                          double* event_dst, double* const capture_dst[], uint32_t flags);
+
 /* ---- rollout models: systems piped AROUND six_dof, fused with it (the pipes of examples/<name>/sim.py) ------------- */
 struct sixdof_apollo_tables; /* include/sixdof_apollo.h */
 /* Select the Apollo-lander rollout model (examples/apollo-lander/sim.py:517-526 + the guidance sidecar
