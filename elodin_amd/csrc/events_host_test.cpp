@@ -1,5 +1,5 @@
 // events_host_test.cpp — sixdof_history_events (sixdof_capi.cpp) over the fake runtime (hip_fake.cpp), whose launchers walk, merge and
-// capture through events_plan.hpp in the kernels' time segments, under AddressSanitizer / UBSan, no GPU: `make events_test`,
+// capture through events_plan.hpp in the kernels' time segments and through time_scan.hpp's scan_walk, the loop the walk kernel writes out, under AddressSanitizer / UBSan, no GPU: `make events_test`,
 // tests/test_history_events_host.py.
 //
 // The ring and the fault sweep are ring_host_fixture.hpp's.  Checked: the rule exhaustively — every sequence of up to 8 samples
@@ -11,8 +11,6 @@
 // placed on a crossing (its "before" sample is the last sample of the earlier call) and against forced segment counts; every
 // refusal with nothing copied and the accumulator untouched; the conditions of SIXDOF_EVENTS_CONTINUE; 33 captured components;
 // every fallible runtime call failed once.
-#include <cstdlib>
-
 #include "events_plan.hpp"
 #include "ring_host_fixture.hpp"
 
@@ -22,11 +20,7 @@ constexpr size_t kPlanes = SIXDOF_EVENTS_PLANES;
 constexpr uint32_t kHold = SIXDOF_EVENTS_HOLD, kContinue = SIXDOF_EVENTS_CONTINUE;
 constexpr uint32_t kLevel = SIXDOF_EVENT_LEVEL, kCrossing = SIXDOF_EVENT_CROSSING;
 
-void force_segments(uint64_t count) {
-    if (count) setenv("SIXDOF_EVENTS_SEGMENTS", std::to_string(count).c_str(), 1);
-    else unsetenv("SIXDOF_EVENTS_SEGMENTS");
-}
-bool same_bits(const std::vector<double>& a, const std::vector<double>& b) { return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0; }
+void force_segments(uint64_t count) { force_segments("SIXDOF_EVENTS_SEGMENTS", count); }
 const double kNaN = std::numeric_limits<double>::quiet_NaN();
 
 bool compare(double x, uint32_t op, double level) {
@@ -125,11 +119,11 @@ void plan_arithmetic() {
     for (uint64_t units : {uint64_t(1), uint64_t(125), uint64_t(7168), uint64_t(65535)})
         for (uint64_t ns : {uint64_t(1), uint64_t(13), uint64_t(64), uint64_t(1024), uint64_t(1) << 31}) {
             const uint32_t s = events_segments(units, ns);
-            if (s < 1 || s > ns || s > kExtremesMaxSegments) complain("plan: events_segments out of range");
+            if (s < 1 || s > ns || s > kScanMaxSegments) complain("plan: events_segments out of range");
         }
     const uint64_t rec = kEventsFields * 8;
-    if (events_fit_segments(8, 1000, rec * 1000 * 3) != 3 || events_fit_segments(8, 1000, rec * 1000) != 1 || events_fit_segments(1, 1u << 30, 1) != 1) complain("plan: events_fit_segments");
-    if (events_scratch_bytes(1, 1000) != 0 || events_scratch_bytes(3, 1000) != 3 * rec * 1000 || events_record_bytes(7) != 7 * rec) complain("plan: events_scratch_bytes");
+    if (scan_fit_segments(8, 1000, kEventsFields, rec * 1000 * 3) != 3 || scan_fit_segments(8, 1000, kEventsFields, rec * 1000) != 1 || scan_fit_segments(1, 1u << 30, kEventsFields, 1) != 1) complain("plan: scan_fit_segments");
+    if (scan_scratch_bytes(1, 1000, kEventsFields) != 0 || scan_scratch_bytes(3, 1000, kEventsFields) != 3 * rec * 1000 || events_record_bytes(7) != 7 * rec) complain("plan: scan_scratch_bytes");
     if (!events_tick_sampled(7, 7, 13, 3) || !events_tick_sampled(13, 7, 13, 3) || events_tick_sampled(8, 7, 13, 3) || events_tick_sampled(4, 7, 13, 3) ||
         events_tick_sampled(16, 7, 13, 3) || events_tick_sampled(0, 7, 13, 3))
         complain("plan: events_tick_sampled");
@@ -509,7 +503,7 @@ int main() {
     refusals();
     continue_conditions();
     more_captures_than_one_launch();
-    setenv("SIXDOF_EVENTS_SEGMENTS", "2", 1);
+    force_segments(2);
     failure_injection("events_host_test", kSwept, {true, false, true});
     force_segments(0);
     return verdict("events_host_test");

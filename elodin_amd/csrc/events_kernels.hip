@@ -10,8 +10,8 @@
 // segment in time order.  Consecutive lanes are period * w elements apart: at period 1 a wave's load touches a contiguous span of
 // 64 * w elements and uses 1 / w of it (one f64 in seven of world_pos: 512 of 3,584 bytes), at a larger period 1 / (period * w)
 // — the price of reading one element of a row-major block; the cache lines are the ones a reader of whole rows would fetch
-// once.  The addresses of a thread's samples do not depend on each other: kEventsLoads of them are loaded before the
-// first is used, and the slot advances by an add and a compare.  A thread whose record is settled (events_settled) stops loading;
+// once.  The loop is time_scan.hpp's scan_walk written out (see below): kScanLoads samples are loaded before the first is used, the
+// slot advances by an add and a compare.  A thread whose record is settled (events_settled) stops loading;
 // a wave goes on while any of its lanes does.  With one segment the thread starts from the accumulator's record of a continuing
 // call — by the rule's associativity the same as merging it in front of its own, and a run that has had its event loads nothing
 // — stores the record and writes the four planes; with more, its record goes to scratch, field-major so that the stores stay
@@ -39,23 +39,25 @@ __global__ __launch_bounds__(kEventsThreads) void events_walk_kernel(EventsArgs 
     const uint64_t run = (uint64_t)blockIdx.x * kEventsThreads + threadIdx.x;
     if (run >= runs) return;
     const uint32_t seg = blockIdx.y, trig = blockIdx.z, n_triggers = gridDim.z;
-    const uint64_t lo = extremes_segment_start(n_samples, segments, seg), hi = extremes_segment_start(n_samples, segments, seg + 1);
+    const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
     const uint64_t total = n * t.w;
     const E* __restrict__ src = static_cast<const E*>(t.ring) + (run * period + t.group) * t.w + t.element;
     const uint64_t step = every % ring;
     uint64_t slot = sample_slot(first_tick, lo, every, ring), tick = first_tick + lo * every;
     uint64_t* __restrict__ mine = rec + (uint64_t)trig * kEventsFields * runs + run;
     EventsRecord r = segments == 1 && merge_into ? events_load(mine, runs) : events_empty();
+    // scan_walk's loop, written out: through scan_walk this kernel measured about 1 % slower where a thread's chain is long
+    // (profiles/time_scan_refactor.md).  The host twin runs scan_walk with EventsRule; events_host_test holds the two together.
     uint64_t j = lo;
-    for (; j + kEventsLoads <= hi && !events_settled(r, t.mode); j += kEventsLoads) {
-        E x[kEventsLoads];
+    for (; j + kScanLoads <= hi && !events_settled(r, t.mode); j += kScanLoads) {
+        E x[kScanLoads];
 #pragma unroll
-        for (uint32_t q = 0; q < kEventsLoads; q++) {
+        for (uint32_t q = 0; q < kScanLoads; q++) {
             x[q] = src[slot * total];
             slot = next_sample_slot(slot, step, ring);
         }
 #pragma unroll
-        for (uint32_t q = 0; q < kEventsLoads; q++) {
+        for (uint32_t q = 0; q < kScanLoads; q++) {
             events_sample<E>(r, x[q], tick, t.op, t.level);
             tick += every;
         }

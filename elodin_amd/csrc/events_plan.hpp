@@ -15,12 +15,14 @@
 // the first sample where that one holds, and the first crossing otherwise (events_emit).  Once a record has its crossing it is
 // FROZEN: accumulate and merge leave it bit for bit.  The rule is exact and associative in time order, so the outputs cannot
 // depend on how the samples of a range are cut into segments, launches or calls.  Ticks are counts of completed ticks (never 0
-// for a sample, so 0 means "none").
+// for a sample, so 0 means "none").  One thread owns one (trigger, run) and walks its samples in time order: the walk (EventsRule
+// below; the kernel writes scan_walk's loop out), the cut into time segments and the scratch of their records are time_scan.hpp's.
 #pragma once
 
 #include <cstdint>
 
-#include "extremes_plan.hpp"
+#include "quantile_plan.hpp"
+#include "time_scan.hpp"
 
 namespace sixdof {
 
@@ -28,8 +30,6 @@ constexpr uint32_t kEventsThreads = 256;         // threads of a block
 constexpr uint32_t kEventsPlanes = 4;            // SIXDOF_EVENTS_PLANES: tick, value, tick before, value before
 constexpr uint32_t kEventsFields = 10;           // 64-bit fields of a record
 constexpr uint32_t kEventsMaxTriggers = 8;       // SIXDOF_EVENTS_MAX_TRIGGERS
-constexpr uint32_t kEventsLoads = 4;             // samples a thread loads before it uses the first, as kExtremesLoads
-constexpr uint64_t kEventsMinChain = 16;         // no segment shorter than this by the plan's own choice
 constexpr uint64_t kEventsFillThreads = 16384;   // threads below which the plan cuts the samples: see events_segments
 
 constexpr uint32_t kEventLt = 0, kEventLe = 1, kEventGt = 2, kEventGe = 3;   // SIXDOF_EVENT_LT ..
@@ -96,6 +96,14 @@ SIXDOF_HOST_DEVICE inline void events_sample(EventsRecord& rec, E x, uint64_t ti
     const uint64_t u = QuantileBits<E>::raw(x);
     events_accumulate(rec, u, tick, QuantileBits<E>::finite(u), events_holds(static_cast<double>(x), op, level));
 }
+// The rule of one trigger as scan_walk takes it: a walk ends where its record is settled.
+struct EventsRule {
+    double level;
+    uint32_t op, mode;
+    template <class E>
+    SIXDOF_HOST_DEVICE void sample(EventsRecord& rec, E x, uint64_t tick) const { events_sample<E>(rec, x, tick, op, level); }
+    SIXDOF_HOST_DEVICE bool settled(const EventsRecord& rec) const { return events_settled(rec, mode); }
+};
 
 // The four planes of one (trigger, run), `plane_stride` doubles apart: event tick (0: none), the value at it (NaN: none), the
 // tick of the finite sample before it (0: none) and that sample's value (NaN: none).  Conversions only.
@@ -132,34 +140,15 @@ SIXDOF_HOST_DEVICE inline bool events_tick_sampled(uint64_t tick, uint64_t first
 }
 
 // ---- geometry -------------------------------------------------------------------------------------------------------------
-// Time segments of a read, a function of (runs x triggers, n_samples) alone.  The shape is extremes_segments': where the
-// threads are fewer than kEventsFillThreads the samples are cut until that many run, no segment shorter than kEventsMinChain
-// samples; from there on one segment, which needs no scratch and no merge launch.  extremes_segments' constants (262,144 threads,
-// chains of 16) were measured for the extremes walk, whose lanes read consecutive elements, not for this one, whose lanes are
-// period * w elements apart — a wave's load touches w times the cache lines — and whose settled threads stop early.  The
-// threshold here is chosen from the forced-segment table in profiles/history_events.md (one world_pos trigger, 1,024 ticks): at
-// 1,024 runs 0.315 ms in one segment, 0.170 in 2, 0.098 in 4, 0.064 in 8, 0.052 in 16, 0.055 in 32 and 0.079 in 64; at 65,536 runs
-// 0.626 ms in one, 0.638 in 2, 0.655 in 4 and 0.70 from 8 on.  So about 16,384 threads fill the chip for this walk: the rule picks
-// 16 at 1,024 runs and 1 at 65,536.  Sizes between the two, and the chain length, have not been measured.
-SIXDOF_HOST_DEVICE inline uint32_t events_segments(uint64_t units, uint64_t n_samples) {
-    if (units == 0 || units >= kEventsFillThreads) return 1;
-    uint64_t s = (kEventsFillThreads + units - 1) / units;
-    const uint64_t longest = n_samples / kEventsMinChain;
-    s = s > longest ? longest : s;
-    s = s > kExtremesMaxSegments ? kExtremesMaxSegments : s;
-    return static_cast<uint32_t>(s < 1 ? 1 : s);
-}
-// A forced count (SIXDOF_EVENTS_SEGMENTS) is clamped by extremes_clamp_segments, the cut is extremes_segment_start's.
-// The most segments, at most `segments`, whose records of `units` (trigger, run) pairs fit `budget` bytes of scratch.
-SIXDOF_HOST_DEVICE inline uint32_t events_fit_segments(uint32_t segments, uint64_t units, uint64_t budget) {
-    const uint64_t per_segment = units * kEventsFields * sizeof(uint64_t);
-    if (segments <= 1 || per_segment == 0) return segments < 1 ? 1 : segments;
-    const uint64_t fit = budget / per_segment;
-    return fit < 2 ? 1 : fit < segments ? static_cast<uint32_t>(fit) : segments;
-}
-SIXDOF_HOST_DEVICE inline uint64_t events_scratch_bytes(uint32_t segments, uint64_t units) {
-    return segments <= 1 ? 0 : uint64_t(segments) * units * kEventsFields * sizeof(uint64_t);
-}
+// Time segments of a read, scan_segments of (runs x triggers, n_samples).  The extremes' threshold (262,144 threads) was measured
+// for a walk whose lanes read consecutive elements, not for this one, whose lanes are period * w elements apart — a wave's load
+// touches w times the cache lines — and whose settled threads stop early.  The threshold here is chosen from the forced-segment
+// table in profiles/history_events.md (one world_pos trigger, 1,024 ticks): at 1,024 runs 0.315 ms in one segment, 0.170 in 2,
+// 0.098 in 4, 0.064 in 8, 0.052 in 16, 0.055 in 32 and 0.079 in 64; at 65,536 runs 0.626 ms in one, 0.638 in 2, 0.655 in 4 and
+// 0.70 from 8 on.  So about 16,384 threads fill the chip for this walk: the rule picks 16 at 1,024 runs and 1 at 65,536.  Sizes
+// between the two, and the chain length, have not been measured.
+SIXDOF_HOST_DEVICE inline uint32_t events_segments(uint64_t units, uint64_t n_samples) { return scan_segments(units, n_samples, kEventsFillThreads); }
+// The record buffer of `units` (trigger, run) pairs: what a continuing call starts from.
 SIXDOF_HOST_DEVICE inline uint64_t events_record_bytes(uint64_t units) { return units * kEventsFields * sizeof(uint64_t); }
 
 // One trigger as the kernels see it.
@@ -176,8 +165,8 @@ struct EventsArgs { EventsTrigger t[kEventsMaxTriggers]; };   // by value: 320 b
 inline bool events_launch_ok(const EventsArgs& a, uint32_t n_triggers, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples,
                              uint64_t every, uint32_t segments) {
     if (n_triggers == 0 || n_triggers > kEventsMaxTriggers || period == 0 || n % period != 0) return false;
-    if (n_samples == 0 || (n_samples >> 32) || segments == 0 || segments > kExtremesMaxSegments || segments > n_samples) return false;
-    if (!extremes_ticks_ok(first_tick, n_samples, every)) return false;
+    if (n_samples == 0 || (n_samples >> 32) || segments == 0 || segments > kScanMaxSegments || segments > n_samples) return false;
+    if (!scan_ticks_ok(first_tick, n_samples, every)) return false;
     if ((n / period + kEventsThreads - 1) / kEventsThreads > 0x7fffffffull) return false;
     for (uint32_t k = 0; k < n_triggers; k++) {
         const EventsTrigger& t = a.t[k];

@@ -1,5 +1,5 @@
 // extremes_host_test.cpp — sixdof_history_extremes (sixdof_capi.cpp) over the fake runtime (hip_fake.cpp), whose launcher walks and
-// merges through extremes_plan.hpp in the kernels' time segments, under AddressSanitizer / UBSan, no GPU: `make extremes_test`,
+// merges through extremes_plan.hpp in the kernels' time segments and the kernels' own loop (time_scan.hpp), under AddressSanitizer / UBSan, no GPU: `make extremes_test`,
 // tests/test_history_extremes_host.py.
 //
 // The ring and the fault sweep are ring_host_fixture.hpp's.  Checked: every plane bitwise against a plain loop over the fixture's
@@ -8,8 +8,6 @@
 // every k-th tick or hold one sample; one call against the same range in 2 and 3 calls (SIXDOF_EXTREMES_HOLD, then
 // SIXDOF_EXTREMES_CONTINUE) and against forced segment counts; every refusal with nothing copied and the accumulator untouched;
 // the conditions of SIXDOF_EXTREMES_CONTINUE; 33 component entries; every fallible runtime call failed once.
-#include <cstdlib>
-
 #include "extremes_plan.hpp"
 #include "ring_host_fixture.hpp"
 
@@ -19,11 +17,7 @@ using sixdof::QuantileBits;
 constexpr size_t kPlanes = SIXDOF_EXTREMES_PLANES;
 constexpr uint32_t kHold = SIXDOF_EXTREMES_HOLD, kContinue = SIXDOF_EXTREMES_CONTINUE;
 
-void force_segments(uint64_t count) {
-    if (count) setenv("SIXDOF_EXTREMES_SEGMENTS", std::to_string(count).c_str(), 1);
-    else unsetenv("SIXDOF_EXTREMES_SEGMENTS");
-}
-bool same_bits(const std::vector<double>& a, const std::vector<double>& b) { return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0; }
+void force_segments(uint64_t count) { force_segments("SIXDOF_EXTREMES_SEGMENTS", count); }
 
 // The six planes [6][n * w] of column k over the samples first, first + every, ...: a plain loop over what was uploaded.
 template <class T>
@@ -126,22 +120,22 @@ void plan_arithmetic() {
     for (uint64_t total : {uint64_t(1), uint64_t(125), uint64_t(7168), uint64_t(65535)})
         for (uint64_t ns : {uint64_t(1), uint64_t(13), uint64_t(64), uint64_t(1024), uint64_t(1) << 31}) {
             const uint32_t s = extremes_segments(total, ns);
-            if (s < 1 || s > ns || s > kExtremesMaxSegments) complain("plan: extremes_segments out of range");
+            if (s < 1 || s > ns || s > kScanMaxSegments) complain("plan: extremes_segments out of range");
             uint64_t covered = 0;
             for (uint32_t g = 0; g < s; g++) {
-                const uint64_t lo = extremes_segment_start(ns, s, g), hi = extremes_segment_start(ns, s, g + 1);
+                const uint64_t lo = scan_segment_start(ns, s, g), hi = scan_segment_start(ns, s, g + 1);
                 if (hi <= lo || lo != covered) complain("plan: the segments do not tile the samples");
                 covered = hi;
             }
             if (covered != ns) complain("plan: the segments do not end on the last sample");
         }
-    if (extremes_clamp_segments(9, 4) != 4 || extremes_clamp_segments(1u << 20, 1u << 24) != kExtremesMaxSegments) complain("plan: extremes_clamp_segments");
-    if (extremes_fit_segments(8, 1000, 48 * 1000 * 3) != 3 || extremes_fit_segments(8, 1000, 48 * 1000) != 1 || extremes_fit_segments(1, 1u << 30, 1) != 1) complain("plan: extremes_fit_segments");
-    if (extremes_scratch_bytes(1, 1000) != 0 || extremes_scratch_bytes(3, 1000) != 3 * 48 * 1000) complain("plan: extremes_scratch_bytes");
+    if (scan_clamp_segments(9, 4) != 4 || scan_clamp_segments(1u << 20, 1u << 24) != kScanMaxSegments) complain("plan: scan_clamp_segments");
+    if (scan_fit_segments(8, 1000, kExtremesFields, 48 * 1000 * 3) != 3 || scan_fit_segments(8, 1000, kExtremesFields, 48 * 1000) != 1 || scan_fit_segments(1, 1u << 30, kExtremesFields, 1) != 1) complain("plan: scan_fit_segments");
+    if (scan_scratch_bytes(1, 1000, kExtremesFields) != 0 || scan_scratch_bytes(3, 1000, kExtremesFields) != 3 * 48 * 1000) complain("plan: scan_scratch_bytes");
     const uint64_t top = uint64_t(1) << 53;
-    if (!extremes_ticks_ok(top - 1, 1, 1) || extremes_ticks_ok(top - 1, 2, 1) || extremes_ticks_ok(top, 1, 1) || !extremes_ticks_ok(1, 3, (top - 2) / 2) ||
-        extremes_ticks_ok(2, 3, (top - 2) / 2) || extremes_ticks_ok(1, 2, ~uint64_t(0)) || extremes_ticks_ok(0, 1, 1))
-        complain("plan: extremes_ticks_ok");
+    if (!scan_ticks_ok(top - 1, 1, 1) || scan_ticks_ok(top - 1, 2, 1) || scan_ticks_ok(top, 1, 1) || !scan_ticks_ok(1, 3, (top - 2) / 2) ||
+        scan_ticks_ok(2, 3, (top - 2) / 2) || scan_ticks_ok(1, 2, ~uint64_t(0)) || scan_ticks_ok(0, 1, 1))
+        complain("plan: scan_ticks_ok");
     // the slot a walking thread advances by an add and a compare is the slot of the next sample
     for (uint64_t ring : {uint64_t(1), uint64_t(5), uint64_t(8), uint64_t(1) << 32})
         for (uint64_t every : {uint64_t(1), uint64_t(3), uint64_t(8), uint64_t(13), (uint64_t(1) << 32) + 3})
@@ -325,7 +319,7 @@ int main() {
     refusals();
     continue_conditions();
     more_components_than_one_launch();
-    setenv("SIXDOF_EXTREMES_SEGMENTS", "2", 1);
+    force_segments(2);
     failure_injection("extremes_host_test", kSwept, {true, false, true});
     force_segments(0);
     return verdict("extremes_host_test");

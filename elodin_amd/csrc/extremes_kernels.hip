@@ -7,8 +7,7 @@
 //
 // Stage 1, extremes_walk_kernel: grid (ceil(n * w / 256), segments, components).  One thread owns element i of the flat tick
 // block and walks the samples of its segment in time order; consecutive lanes read consecutive elements, so a wave load is 512
-// contiguous bytes of f64 (256 of f32), as in the envelope.  The addresses of a thread's samples do not depend on each other:
-// kExtremesLoads of them are loaded before the first is used, and the slot advances by an add and a compare, not a division.
+// contiguous bytes of f64 (256 of f32), as in the envelope.  The loop is time_scan.hpp's scan_walk, which loads ahead of its use.
 // The record lives in registers on integer keys; the finite test looks at the exponent bits.  With one segment the thread
 // merges the accumulator of a continuing call in front of its record and writes the six planes itself; with more, its record
 // goes to scratch, field-major so that the stores stay coalesced.
@@ -30,30 +29,8 @@ __global__ __launch_bounds__(kExtremesThreads) void extremes_walk_kernel(RingBin
     const uint64_t i = (uint64_t)blockIdx.x * kExtremesThreads + threadIdx.x;
     if (i >= total) return;      // a narrower component than the one that sized the grid, or the ragged last block
     const uint32_t seg = blockIdx.y;
-    const uint64_t lo = extremes_segment_start(n_samples, segments, seg), hi = extremes_segment_start(n_samples, segments, seg + 1);
-    const E* __restrict__ src = static_cast<const E*>(d.ring) + i;
-    const uint64_t step = every % ring;
-    uint64_t slot = sample_slot(first_tick, lo, every, ring), tick = first_tick + lo * every;
-    ExtremesRecord r = extremes_empty();
-    uint64_t j = lo;
-    for (; j + kExtremesLoads <= hi; j += kExtremesLoads) {
-        E x[kExtremesLoads];
-#pragma unroll
-        for (uint32_t q = 0; q < kExtremesLoads; q++) {
-            x[q] = src[slot * total];
-            slot = next_sample_slot(slot, step, ring);
-        }
-#pragma unroll
-        for (uint32_t q = 0; q < kExtremesLoads; q++) {
-            extremes_sample<E>(r, x[q], tick);
-            tick += every;
-        }
-    }
-    for (; j < hi; j++) {
-        extremes_sample<E>(r, src[slot * total], tick);
-        slot = next_sample_slot(slot, step, ring);
-        tick += every;
-    }
+    const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
+    ExtremesRecord r = scan_walk(extremes_empty(), ExtremesRule{}, static_cast<const E*>(d.ring) + i, total, lo, hi, first_tick, every, ring);
     if (segments == 1) {
         double* __restrict__ o = out + d.out_offset + i;
         if (merge_into) r = extremes_merge(extremes_absorb<E>(o, total), r);

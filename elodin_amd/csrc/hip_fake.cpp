@@ -358,22 +358,16 @@ hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components,
         else quantiles_of_tick<float>(src, n, d.w, period, ranks, h, st, to);
     }));
 }
-// the walk and the merge themselves (extremes_kernels.hip), serially: extremes_plan.hpp's rule in the kernels' segmentation — with
-// more than one segment every (segment, element) record goes through the launch's scratch, as on the device
+// the walk and the merge themselves (extremes_kernels.hip), serially: extremes_plan.hpp's rule in the kernels' segmentation and the
+// kernels' own loop (time_scan.hpp: scan_walk) — with more than one segment every (segment, element) record goes through the launch's scratch, as on the device
 template <class E>
 static void extremes_of_component(const RingBinDesc& d, double* out, uint64_t* scratch, uint64_t stride, uint32_t segments, bool merge_into, uint64_t n,
                                   uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
-    const uint64_t total = n * d.w, step = every % ring;
+    const uint64_t total = n * d.w;
     for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
-        const uint64_t lo = extremes_segment_start(n_samples, segments, seg), hi = extremes_segment_start(n_samples, segments, seg + 1);
+        const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
         for (uint64_t i = 0; i < total; i++) {
-            uint64_t slot = sample_slot(first_tick, lo, every, ring), tick = first_tick + lo * every;
-            ExtremesRecord r = extremes_empty();
-            for (uint64_t j = lo; j < hi; j++, tick += every, slot = next_sample_slot(slot, step, ring)) {
-                E x;
-                std::memcpy(&x, static_cast<const char*>(d.ring) + (slot * total + i) * sizeof(E), sizeof(E));
-                extremes_sample<E>(r, x, tick);
-            }
+            ExtremesRecord r = scan_walk(extremes_empty(), ExtremesRule{}, static_cast<const E*>(d.ring) + i, total, lo, hi, first_tick, every, ring);
             double* o = out + d.out_offset + i;
             if (segments == 1) {
                 if (merge_into) r = extremes_merge(extremes_absorb<E>(o, total), r);
@@ -397,7 +391,7 @@ hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, 
     for (uint32_t k = 0; k < n_components && k < kRingBinMaxComponents; k++) widths[k] = a.c[k].w;
     if (!extremes_launch_ok(n_components, kRingBinMaxComponents, widths, n, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
     if (n == 0) return launch(true);
-    if (segments > 1 && !need(live(scratch, extremes_scratch_bytes(segments, scratch_stride)), "extremes scratch records")) return launch(false);
+    if (segments > 1 && !need(live(scratch, scan_scratch_bytes(segments, scratch_stride, kExtremesFields)), "extremes scratch records")) return launch(false);
     for (uint32_t k = 0; k < n_components; k++) {
         const RingBinDesc& d = a.c[k];
         const uint64_t total = n * d.w;
@@ -410,22 +404,17 @@ hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, 
     return launch(true);
 }
 // the walk, the merge and the capture themselves (events_kernels.hip), serially: events_plan.hpp's rule in the kernels' segmentation
-// — with more than one segment every (segment, trigger, run) record goes through the launch's scratch, as on the device
+// and scan_walk, whose loop the kernel writes out — with more than one segment every (segment, trigger, run) record goes through the launch's scratch, as on the device
 template <class E>
 static void events_of_trigger(const EventsTrigger& t, uint32_t trig, uint32_t n_triggers, uint64_t* rec, double* out, uint64_t* scratch, uint32_t segments,
                               bool merge_into, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
-    const uint64_t runs = n / period, total = n * t.w, step = every % ring;
+    const uint64_t runs = n / period;
     for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
-        const uint64_t lo = extremes_segment_start(n_samples, segments, seg), hi = extremes_segment_start(n_samples, segments, seg + 1);
+        const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
         for (uint64_t run = 0; run < runs; run++) {
-            uint64_t slot = sample_slot(first_tick, lo, every, ring), tick = first_tick + lo * every;
             uint64_t* mine = rec + uint64_t(trig) * kEventsFields * runs + run;
-            EventsRecord r = segments == 1 && merge_into ? events_load(mine, runs) : events_empty();
-            for (uint64_t j = lo; j < hi && !events_settled(r, t.mode); j++, tick += every, slot = next_sample_slot(slot, step, ring)) {
-                E x;
-                std::memcpy(&x, static_cast<const char*>(t.ring) + (slot * total + (run * period + t.group) * t.w + t.element) * sizeof(E), sizeof(E));
-                events_sample<E>(r, x, tick, t.op, t.level);
-            }
+            EventsRecord r = scan_walk(segments == 1 && merge_into ? events_load(mine, runs) : events_empty(), EventsRule{t.level, t.op, t.mode},
+                                       static_cast<const E*>(t.ring) + (run * period + t.group) * t.w + t.element, n * t.w, lo, hi, first_tick, every, ring);
             if (segments == 1) {
                 events_store(r, mine, runs);
                 events_emit<E>(r, t.mode, out + uint64_t(trig) * kEventsPlanes * runs + run, runs);
@@ -447,7 +436,7 @@ hipError_t launch_history_events(const EventsArgs& a, uint32_t n_triggers, void*
     if (!events_launch_ok(a, n_triggers, n, period, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
     if (n == 0) return launch(true);
     const uint64_t units = n / period * n_triggers;
-    if (segments > 1 && !need(live(scratch, events_scratch_bytes(segments, units)), "events scratch records")) return launch(false);
+    if (segments > 1 && !need(live(scratch, scan_scratch_bytes(segments, units, kEventsFields)), "events scratch records")) return launch(false);
     if (!need(live(rec, events_record_bytes(units)) && live(out, units * kEventsPlanes * sizeof(double)), "events records or staging")) return launch(false);
     for (uint32_t k = 0; k < n_triggers; k++) {
         const EventsTrigger& t = a.t[k];

@@ -199,7 +199,7 @@ hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components,
 // start at scratch_offset in every segment's `scratch_stride` units.  All n_samples samples of the range first_tick, first_tick +
 // every, ... in `segments` time segments (extremes_plan.hpp); with more than one, `scratch` holds segments * 6 * scratch_stride
 // 64-bit words.  merge_into: `out` holds the planes of the samples before this range, and the result covers both.  The caller has
-// validated the range (sampled_range_ok, extremes_ticks_ok).
+// validated the range (sampled_range_ok, scan_ticks_ok).
 hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, double* out, void* scratch, uint64_t scratch_stride,
                                    uint32_t segments, bool merge_into, uint64_t n, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                                    uint64_t ring, size_t elem, hipStream_t s);
@@ -210,7 +210,7 @@ struct EventsArgs;   // events_plan.hpp: the triggers (ring base, width, element
 // the records, [n_triggers][10][runs] 64-bit words with runs = n / period, written by every launch and read first when merge_into
 // (they then hold the samples before this range, and the result covers both); `out`: the four planes, [n_triggers][4][runs]
 // doubles; with more than one segment `scratch` holds segments * n_triggers * 10 * runs words.  The caller has validated the range
-// (sampled_range_ok, extremes_ticks_ok) and the triggers (events_launch_ok).
+// (sampled_range_ok, scan_ticks_ok) and the triggers (events_launch_ok).
 hipError_t launch_history_events(const EventsArgs& a, uint32_t n_triggers, void* rec, double* out, void* scratch, uint32_t segments, bool merge_into,
                                  uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem,
                                  hipStream_t s);

@@ -1,12 +1,15 @@
-// ring_host_fixture.hpp — what envelope_host_test.cpp and quantile_host_test.cpp share: the fake runtime's hooks, a recorded ring
-// kept on the host too, and the cases every reduction over the ring (sixdof_capi.cpp: ring_bin_read) has to pass whatever it
-// computes — the common refusals, more components than one launch covers, every fallible runtime call failed once.  Each
-// program is one translation unit, so everything here sits in its anonymous namespace.
+// ring_host_fixture.hpp — what envelope_host_test.cpp, quantile_host_test.cpp, extremes_host_test.cpp and events_host_test.cpp
+// share: the fake runtime's hooks, a recorded ring kept on the host too, and the fault sweep every reader of the ring has to
+// pass whatever it computes — every fallible runtime call failed once.  For the two per-sample reductions (sixdof_capi.cpp:
+// ring_bin_read) also their common refusals and more components than one launch covers; for the two scans over time
+// (time_scan_read) the forced segment count and the bitwise compare.  Each program is one translation unit, so everything here
+// sits in its anonymous namespace.
 #pragma once
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <limits>
@@ -35,6 +38,13 @@ void complain(const std::string& what) {
     if (g_failures < 40) std::fprintf(stderr, "FAIL: %s\n", what.c_str());
     g_failures++;
 }
+
+// The segment count a scan is forced to through its environment variable `name`; 0: the plan's own choice again.
+void force_segments(const char* name, uint64_t count) {
+    if (count) setenv(name, std::to_string(count).c_str(), 1);
+    else unsetenv(name);
+}
+bool same_bits(const std::vector<double>& a, const std::vector<double>& b) { return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0; }
 
 const char* kNames[4] = {"world_pos", "world_vel", "world_accel", "force"};
 const uint64_t kWidths[4] = {7, 6, 6, 6};

@@ -160,30 +160,21 @@ struct History {
     DeviceBuffer env_stage, env_partial;
     // sixdof_history_quantiles: its staging, and the histograms and slot states of one launch; the same rules
     DeviceBuffer quant_stage, quant_scratch;
-    // sixdof_history_extremes: its staging, which is also the accumulator a SIXDOF_EXTREMES_CONTINUE call merges into, and the
-    // segment records of one launch; the same rules.  `extremes` says what the accumulator holds, if anything.
-    DeviceBuffer ext_stage, ext_scratch;
-    struct Extremes {
+    // A scan over time (time_scan_read: sixdof_history_extremes, sixdof_history_events): its staging, which is also the accumulator
+    // a *_CONTINUE call merges into, the segment records of one launch and — the events only — the records its rule continues
+    // from; the same rules.  `acc` says what the accumulator holds, if anything.
+    struct ScanState {
         bool valid = false;                  // the previous call succeeded and nothing has replaced what it read since
-        std::vector<uint64_t> ids;           // its component list, in order
-        std::vector<const void*> rings;      // ring base and width of each as they were: a replaced program changes them
+        std::vector<uint64_t> signature;     // what was asked for, in plain words: the same request gives the same words
+        std::vector<const void*> rings;      // ring base and width of everything read, as they were: a replaced program changes them
         std::vector<size_t> widths;
         uint64_t n = 0;
         uint64_t last_tick = 0;              // the last tick accumulated
-    } extremes;
-    // sixdof_history_events: its records and its staging (the event planes and the captures), which together are the accumulator a
-    // SIXDOF_EVENTS_CONTINUE call merges into, and the segment records of one launch; the same rules.
-    DeviceBuffer ev_rec, ev_stage, ev_scratch;
-    struct Events {
-        bool valid = false;
-        std::vector<sixdof_event_trigger> triggers;   // field for field
-        std::vector<uint64_t> capture_ids;
-        std::vector<const void*> rings;               // ring base and width of every trigger, then of every capture, as they were
-        std::vector<size_t> widths;
-        uint64_t n = 0;
-        uint32_t period = 0;
-        uint64_t last_tick = 0;                       // the last tick accumulated
-    } events;
+    };
+    struct TimeScan {
+        DeviceBuffer stage, scratch, rec;
+        ScanState acc;
+    } extremes, events;
     void reset() { *this = History{}; }
 };
 
@@ -502,8 +493,7 @@ void sixdof_destroy(sixdof_handle* h) try {
 int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_cols) try {
     if (!h || (!cols && n_cols)) return SIXDOF_ERR_INVALID_ARGUMENT;
     h->bound = h->resident = false;   // until the end of this call: a failed bind leaves the handle unbound
-    h->hist.extremes.valid = false;   // the rows an extremes accumulator covers may be other rows from here on
-    h->hist.events.valid = false;     // and those of an events accumulator
+    h->hist.extremes.acc.valid = h->hist.events.acc.valid = false;   // the rows a scan's accumulator covers may be other rows from here on
     HIP_TRY(h, hipSetDevice(h->device));
     h->replay.drop();
     if (h->d_watch_rows) {      // a watch holds rows of the join this call replaces
@@ -1420,9 +1410,9 @@ int sixdof_set_watch(sixdof_handle* h, const uint64_t* component_ids, size_t n_c
 } SIXDOF_ABI_CATCH(err_of(h))
 
 // A read whose results are computed on the compute stream, out of the ring into a device staging buffer, and brought from
-// there to the caller's buffers, blocking or over the copy lane: sixdof_watch_read and, through ring_bin_read below,
-// sixdof_history_envelope and sixdof_history_quantiles, and sixdof_history_extremes and sixdof_history_events.  The lane and the rules of the staging buffer live here and nowhere
-// in the callers: add() the components, claim() the buffers, launch into them, deliver().
+// there to the caller's buffers, blocking or over the copy lane.  Its users: sixdof_watch_read, ring_bin_read (the envelopes and
+// the quantiles) and time_scan_read (the extremes and the events).  The lane and the rules of the staging buffer live here and
+// nowhere in the callers: add() the components, claim() the buffers, launch into them, deliver().
 struct StagedRead {
     // one component: ring base and width as they are NOW, its block in the staging buffer (256-byte aligned), where it goes
     struct Part { const void* ring; size_t w, bytes, offset; void* host; };
@@ -1433,7 +1423,7 @@ struct StagedRead {
     size_t stage_bytes = 0;
 
     // `per_width` elements of `elem` bytes for every element of a row; `unrecorded`: the message when the ring does not hold `id`
-    // (host_needed = false: a read that delivers nothing, sixdof_history_extremes with SIXDOF_EXTREMES_HOLD)
+    // (host_needed = false: a read that delivers nothing, a scan that holds)
     int add(uint64_t id, void* host, size_t per_width, size_t elem, const char* unrecorded, bool host_needed = true) {
         Part p{};
         if (!watch_lookup(h, id, &p.ring, &p.w) || !p.ring) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, std::string(who) + ": " + unrecorded);
@@ -1661,193 +1651,215 @@ int sixdof_history_quantiles(sixdof_handle* h, const uint64_t* component_ids, si
         });
 } SIXDOF_ABI_CATCH(err_of(h))
 
-// The extremes of every row over the sampled ticks of a range.  Ordering, ring reads and the copy lane exactly as for
-// sixdof_watch_read above; not through ring_bin_read, whose output and chunk rule are per sample and (group, element) bin: here
-// ALL samples of the range go into one launch per batch of components, cut into time segments, and the output is per row.  The
-// staging buffer is the accumulator: a SIXDOF_EXTREMES_CONTINUE call merges into what the previous call left there.
-// Commit on success: History::extremes is invalid from the first step that can fail in the runtime to the last enqueue.
-int sixdof_history_extremes(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
-                            uint64_t n_samples, uint64_t every, double* const host_dst[], uint32_t flags) try {
-    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
-    const std::string who = "history_extremes";
-    if (flags & ~(SIXDOF_EXTREMES_ASYNC | SIXDOF_EXTREMES_CONTINUE | SIXDOF_EXTREMES_HOLD)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": unknown flags");
+}  // extern "C"
+
+// A scan of the ring over time: sixdof_history_extremes and sixdof_history_events.  Ordering, ring reads and the copy lane exactly
+// as for sixdof_watch_read above; not through ring_bin_read, whose output and chunk rule are per sample: here ALL samples of the
+// range go into one launch, cut into time segments (time_scan.hpp), and the output is per row or run.  The staging buffer is the
+// accumulator: a call with `continues` merges into what the previous call left there, a call with `holds` delivers nothing.
+// Commit on success: the accumulator is invalid from the first step that can fail in the runtime to the last enqueue.  What a
+// scan is:
+struct TimeScanSpec {
+    const char* who;                                             // the entry point, for its messages
+    uint32_t async, continues, holds;                            // the three flags it knows
+    const char* continue_name;                                   // how `continues` is spelled in its messages
+    const char* accumulator_of;                                  // what a continuing call has to repeat, for its message
+    const char* segments_env;                                    // 0 or unset: the plan's choice (A/B runs, tests)
+    uint32_t (*segments)(uint64_t units, uint64_t n_samples);    // the plan's choice
+    uint32_t fields;                                             // 64-bit words of a record in scratch
+    History::TimeScan* scan;
+};
+// Refuses, plans, launches, delivers and commits.  own_checks(nothing) -> status: the entry point's own argument checks, in their
+// place after the common three; `nothing` arrives as "no samples" and may be set where there is nothing to read for another
+// reason, the call then returns SIXDOF_OK.  parts(rd, next, units) -> status: adds the StagedRead parts, fills next.signature, .rings
+// and .widths, and appends the units of every launch.  launch(rd, i, units, segments, merge_into) -> status: launch i, its segment
+// records within a fixed scratch budget.
+template <class Checks, class Parts, class Launch>
+static int time_scan_read(sixdof_handle* h, const TimeScanSpec& spec, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint32_t flags,
+                          Checks own_checks, Parts parts, Launch launch) {
+    const std::string who = spec.who;
+    if (flags & ~(spec.async | spec.continues | spec.holds)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": unknown flags");
     History& hs = h->hist;
     if (!hs.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": no history ring (sixdof_set_history)");
     if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": every must be at least 1");
-    if (n_samples == 0 || n_components == 0) return SIXDOF_OK;
-    const bool hold = (flags & SIXDOF_EXTREMES_HOLD) != 0, merge_into = (flags & SIXDOF_EXTREMES_CONTINUE) != 0;
-    if (!component_ids || (!host_dst && !hold)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
+    bool nothing = n_samples == 0;
+    if (int rc = own_checks(nothing); rc != SIXDOF_OK) return rc;
+    if (nothing) return SIXDOF_OK;
     if (!sampled_range_ok(first_tick, n_samples, every, hs.first_tick, h->tick, hs.ring))
         return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": ticks are not (all) in the ring");
-    if (!extremes_ticks_ok(first_tick, n_samples, every))
+    if (!scan_ticks_ok(first_tick, n_samples, every))
         return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": a sampled tick of 2^53 or more has no double of its own");
-    const uint64_t n = h->desc.n_entities;
-    StagedRead rd{h, "history_extremes", &hs.ext_stage};
-    for (size_t k = 0; k < n_components; k++) {
-        const int rc = rd.add(component_ids[k], hold ? nullptr : host_dst[k], static_cast<size_t>(n) * kExtremesPlanes, sizeof(double),
-                              "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded", !hold);
-        if (rc != SIXDOF_OK) return rc;
-    }
-    History::Extremes& acc = hs.extremes;
+    StagedRead rd{h, spec.who, &spec.scan->stage};
+    History::ScanState next;
+    next.n = h->desc.n_entities, next.last_tick = first_tick + (n_samples - 1) * every;
+    std::vector<uint64_t> units;
+    if (int rc = parts(rd, next, units); rc != SIXDOF_OK) return rc;
+    History::ScanState& acc = spec.scan->acc;
+    const bool merge_into = (flags & spec.continues) != 0;
     if (merge_into) {
-        bool same = acc.valid && acc.n == n && acc.ids.size() == n_components && std::equal(acc.ids.begin(), acc.ids.end(), component_ids);
-        for (size_t k = 0; same && k < n_components; k++) same = acc.rings[k] == rd.parts[k].ring && acc.widths[k] == rd.parts[k].w;
-        if (!same)
-            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": SIXDOF_EXTREMES_CONTINUE: there is no accumulator of these components, rows and rings to continue "
-                                                              "(the previous call failed or read something else, or the ring, the columns or the program were replaced since)");
+        const std::string what = who + ": " + spec.continue_name + ": ";
+        if (!acc.valid || acc.n != next.n || acc.signature != next.signature || acc.rings != next.rings || acc.widths != next.widths)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, what + "there is no accumulator of these " + spec.accumulator_of + " to continue "
+                                                               "(the previous call failed or read something else, or the ring, the columns or the program were replaced since)");
         if (first_tick <= acc.last_tick)
-            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": SIXDOF_EXTREMES_CONTINUE: first_tick " + std::to_string(first_tick) + " is not above tick " +
-                                                              std::to_string(acc.last_tick) + ", the last one accumulated");
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, what + "first_tick " + std::to_string(first_tick) + " is not above tick " + std::to_string(acc.last_tick) +
+                                                               ", the last one accumulated");
     }
-    // one launch per batch of at most kRingBinMaxComponents components; its segment records stay within a fixed scratch budget
-    const char* forced_env = std::getenv("SIXDOF_EXTREMES_SEGMENTS");   // 0 or unset: the plan's choice (A/B runs, tests)
+    const char* forced_env = std::getenv(spec.segments_env);
     const uint64_t forced = forced_env ? std::strtoull(forced_env, nullptr, 10) : 0;
     constexpr uint64_t kScratchBudget = uint64_t(64) << 20;
-    struct Batch { size_t k0; uint32_t count; uint64_t units; uint32_t segments; };
-    std::vector<Batch> batches;
+    std::vector<uint32_t> segments;
     uint64_t scratch_bytes = 0;
-    for (size_t k0 = 0; k0 < n_components; k0 += kRingBinMaxComponents) {
-        Batch b{k0, static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_components - k0)), 0, 1};
-        for (uint32_t k = 0; k < b.count; k++) b.units += n * rd.parts[k0 + k].w;
-        b.segments = forced ? extremes_clamp_segments(forced, n_samples) : extremes_segments(b.units, n_samples);
-        b.segments = extremes_fit_segments(b.segments, b.units, kScratchBudget);
-        scratch_bytes = std::max(scratch_bytes, extremes_scratch_bytes(b.segments, b.units));
-        batches.push_back(b);
+    for (uint64_t u : units) {
+        const uint32_t s = forced ? scan_clamp_segments(forced, n_samples) : spec.segments(u, n_samples);
+        segments.push_back(scan_fit_segments(s, u, spec.fields, kScratchBudget));
+        scratch_bytes = std::max(scratch_bytes, scan_scratch_bytes(segments.back(), u, spec.fields));
     }
     HIP_TRY(h, hipSetDevice(h->device));
     acc.valid = false;
-    if (int rc = rd.claim(&hs.ext_scratch, static_cast<size_t>(scratch_bytes)); rc != SIXDOF_OK) return rc;
-    for (const Batch& b : batches) {
-        RingBinArgs a{};
-        uint64_t unit0 = 0;
-        for (uint32_t k = 0; k < b.count; k++) {
-            const StagedRead::Part& p = rd.parts[b.k0 + k];
-            a.c[k].ring = p.ring;
-            a.c[k].out_offset = p.offset / sizeof(double);
-            a.c[k].scratch_offset = unit0;
-            a.c[k].w = static_cast<uint32_t>(p.w);
-            unit0 += n * p.w;
-        }
-        hipError_t e = launch_history_extremes(a, b.count, hs.ext_stage.get<double>(), hs.ext_scratch.get(), b.units, b.segments, merge_into, n, first_tick,
-                                               n_samples, every, hs.ring, h->elem_size(), h->stream.get());
-        if (e != hipSuccess) return h->hip_fail(e, "history_extremes");
-    }
-    if (!hold)
-        if (int rc = rd.deliver((flags & SIXDOF_EXTREMES_ASYNC) != 0); rc != SIXDOF_OK) return rc;
-    acc.ids.assign(component_ids, component_ids + n_components);
-    acc.rings.clear(), acc.widths.clear();
-    for (const StagedRead::Part& p : rd.parts) acc.rings.push_back(p.ring), acc.widths.push_back(p.w);
-    acc.n = n;
-    acc.last_tick = first_tick + (n_samples - 1) * every;
+    if (int rc = rd.claim(&spec.scan->scratch, static_cast<size_t>(scratch_bytes)); rc != SIXDOF_OK) return rc;
+    for (size_t i = 0; i < units.size(); i++)
+        if (int rc = launch(rd, i, units[i], segments[i], merge_into); rc != SIXDOF_OK) return rc;
+    if (!(flags & spec.holds))
+        if (int rc = rd.deliver((flags & spec.async) != 0); rc != SIXDOF_OK) return rc;
+    acc = std::move(next);
     acc.valid = true;
     return SIXDOF_OK;
+}
+
+static const char* const kOnlyRecorded = "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded";
+
+extern "C" {
+
+// The extremes of every row over the sampled ticks of a range: one walk (and merge) launch per batch of at most
+// kRingBinMaxComponents components, a unit is one element of a row.
+int sixdof_history_extremes(sixdof_handle* h, const uint64_t* component_ids, size_t n_components, uint64_t first_tick,
+                            uint64_t n_samples, uint64_t every, double* const host_dst[], uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    History& hs = h->hist;
+    const TimeScanSpec spec{"history_extremes", SIXDOF_EXTREMES_ASYNC, SIXDOF_EXTREMES_CONTINUE, SIXDOF_EXTREMES_HOLD, "SIXDOF_EXTREMES_CONTINUE",
+                            "components, rows and rings", "SIXDOF_EXTREMES_SEGMENTS", extremes_segments, kExtremesFields, &hs.extremes};
+    const bool hold = (flags & SIXDOF_EXTREMES_HOLD) != 0;
+    const uint64_t n = h->desc.n_entities;
+    return time_scan_read(
+        h, spec, first_tick, n_samples, every, flags,
+        [&](bool& nothing) -> int {
+            nothing = nothing || n_components == 0;
+            if (nothing) return SIXDOF_OK;
+            if (!component_ids || (!host_dst && !hold)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, "history_extremes: null argument");
+            return SIXDOF_OK;
+        },
+        [&](StagedRead& rd, History::ScanState& next, std::vector<uint64_t>& units) -> int {
+            for (size_t k = 0; k < n_components; k++) {
+                const int rc = rd.add(component_ids[k], hold ? nullptr : host_dst[k], static_cast<size_t>(n) * kExtremesPlanes, sizeof(double), kOnlyRecorded, !hold);
+                if (rc != SIXDOF_OK) return rc;
+                if (k % kRingBinMaxComponents == 0) units.push_back(0);
+                units.back() += n * rd.parts[k].w;
+                next.rings.push_back(rd.parts[k].ring), next.widths.push_back(rd.parts[k].w);
+            }
+            next.signature.assign(component_ids, component_ids + n_components);
+            return SIXDOF_OK;
+        },
+        [&](const StagedRead& rd, size_t i, uint64_t units, uint32_t segments, bool merge_into) -> int {
+            const size_t k0 = i * kRingBinMaxComponents;
+            const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_components - k0));
+            RingBinArgs a{};
+            uint64_t unit0 = 0;
+            for (uint32_t k = 0; k < cnt; k++) {
+                const StagedRead::Part& p = rd.parts[k0 + k];
+                a.c[k].ring = p.ring;
+                a.c[k].out_offset = p.offset / sizeof(double);
+                a.c[k].scratch_offset = unit0;
+                a.c[k].w = static_cast<uint32_t>(p.w);
+                unit0 += n * p.w;
+            }
+            hipError_t e = launch_history_extremes(a, cnt, hs.extremes.stage.get<double>(), hs.extremes.scratch.get(), units, segments, merge_into, n, first_tick,
+                                                   n_samples, every, hs.ring, h->elem_size(), h->stream.get());
+            return e == hipSuccess ? int(SIXDOF_OK) : h->hip_fail(e, "history_extremes");
+        });
 } SIXDOF_ABI_CATCH(err_of(h))
 
-// The first event of every run per trigger, and the rows of the captured components at it.  Ordering, ring reads, the copy lane
-// and commit on success exactly as for sixdof_history_extremes above.  One walk (and merge) launch covers all triggers; one capture
-// launch behind it covers at most kRingBinMaxComponents captured components.  The accumulator is the record buffer (ev_rec: what
-// the rule continues from) together with the staging buffer (ev_stage: the event planes, rewritten by every call, and the
-// captures, of which a continuing call rewrites only the runs whose event it saw).
+// The first event of every run per trigger, and the rows of the captured components at it.  One walk (and merge) launch covers
+// all triggers, a unit is one (trigger, run); one capture launch behind it covers at most kRingBinMaxComponents captured
+// components.  The accumulator is the record buffer (what the rule continues from) together with the staging buffer (the event
+// planes, rewritten by every call, and the captures, of which a continuing call rewrites only the runs whose event it saw).
 int sixdof_history_events(sixdof_handle* h, const sixdof_event_trigger* triggers, size_t n_triggers, const uint64_t* capture_ids,
                           size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                           double* event_dst, double* const capture_dst[], uint32_t flags) try {
     if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
-    const std::string who = "history_events";
-    if (flags & ~(SIXDOF_EVENTS_ASYNC | SIXDOF_EVENTS_CONTINUE | SIXDOF_EVENTS_HOLD)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": unknown flags");
     History& hs = h->hist;
-    if (!hs.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": no history ring (sixdof_set_history)");
-    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": every must be at least 1");
-    if (n_triggers == 0 || n_triggers > SIXDOF_EVENTS_MAX_TRIGGERS)
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(n_triggers) + " triggers, 1 to " + std::to_string(SIXDOF_EVENTS_MAX_TRIGGERS) + " can be asked for");
-    if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
+    History::TimeScan& sc = hs.events;
+    const TimeScanSpec spec{"history_events", SIXDOF_EVENTS_ASYNC, SIXDOF_EVENTS_CONTINUE, SIXDOF_EVENTS_HOLD, "SIXDOF_EVENTS_CONTINUE",
+                            "triggers, captures, period, rows and rings", "SIXDOF_EVENTS_SEGMENTS", events_segments, kEventsFields, &sc};
+    const std::string who = spec.who;
+    const bool hold = (flags & SIXDOF_EVENTS_HOLD) != 0;
     const uint64_t n = h->desc.n_entities;
-    if (n % period != 0)
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
-    const bool hold = (flags & SIXDOF_EVENTS_HOLD) != 0, merge_into = (flags & SIXDOF_EVENTS_CONTINUE) != 0;
-    if (!triggers || (n_captures && !capture_ids) || (!hold && (!event_dst || (n_captures && !capture_dst))))
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
-    EventsArgs a{};
-    for (size_t k = 0; k < n_triggers; k++) {
-        const sixdof_event_trigger& t = triggers[k];
-        const std::string which = who + ": trigger " + std::to_string(k);
-        if (t.op > SIXDOF_EVENT_GE) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown op " + std::to_string(t.op));
-        if (t.mode > SIXDOF_EVENT_CROSSING) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown mode " + std::to_string(t.mode));
-        if (!std::isfinite(t.level)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": the level is not finite");
-        if (t.group >= period) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": group " + std::to_string(t.group) + " is not below period " + std::to_string(period));
-        size_t w = 0;
-        if (!watch_lookup(h, t.component_id, &a.t[k].ring, &w) || !a.t[k].ring)
-            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, which + ": only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded");
-        if (t.element >= w) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": element " + std::to_string(t.element) + " is not below the component's width " + std::to_string(w));
-        a.t[k].level = t.level, a.t[k].w = static_cast<uint32_t>(w), a.t[k].element = t.element, a.t[k].group = t.group, a.t[k].op = t.op, a.t[k].mode = t.mode;
-    }
-    if (n_samples == 0) return SIXDOF_OK;
-    if (!sampled_range_ok(first_tick, n_samples, every, hs.first_tick, h->tick, hs.ring))
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": ticks are not (all) in the ring");
-    if (!extremes_ticks_ok(first_tick, n_samples, every))
-        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": a sampled tick of 2^53 or more has no double of its own");
-    const uint64_t runs = n / period, units = runs * n_triggers;
-    StagedRead rd{h, "history_events", &hs.ev_stage};
-    rd.add_block(hold ? nullptr : event_dst, static_cast<size_t>(units) * kEventsPlanes * sizeof(double));
-    for (size_t k = 0; k < n_captures; k++) {
-        const int rc = rd.add(capture_ids[k], hold ? nullptr : capture_dst[k], static_cast<size_t>(n) * n_triggers, sizeof(double),
-                              "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded", !hold);
-        if (rc != SIXDOF_OK) return rc;
-    }
-    History::Events& acc = hs.events;
-    if (merge_into) {
-        bool same = acc.valid && acc.n == n && acc.period == period && acc.triggers.size() == n_triggers && acc.capture_ids.size() == n_captures &&
-                    std::equal(acc.capture_ids.begin(), acc.capture_ids.end(), capture_ids);
-        for (size_t k = 0; same && k < n_triggers; k++) {
-            const sixdof_event_trigger &p = acc.triggers[k], &t = triggers[k];
-            same = p.component_id == t.component_id && p.element == t.element && p.group == t.group && p.op == t.op && p.mode == t.mode &&
-                   std::memcmp(&p.level, &t.level, sizeof(double)) == 0 && acc.rings[k] == a.t[k].ring && acc.widths[k] == a.t[k].w;
-        }
-        for (size_t k = 0; same && k < n_captures; k++) same = acc.rings[n_triggers + k] == rd.parts[1 + k].ring && acc.widths[n_triggers + k] == rd.parts[1 + k].w;
-        if (!same)
-            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": SIXDOF_EVENTS_CONTINUE: there is no accumulator of these triggers, captures, period, rows and rings to continue "
-                                                              "(the previous call failed or read something else, or the ring, the columns or the program were replaced since)");
-        if (first_tick <= acc.last_tick)
-            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": SIXDOF_EVENTS_CONTINUE: first_tick " + std::to_string(first_tick) + " is not above tick " +
-                                                              std::to_string(acc.last_tick) + ", the last one accumulated");
-    }
-    const char* forced_env = std::getenv("SIXDOF_EVENTS_SEGMENTS");   // 0 or unset: the plan's choice (A/B runs, tests)
-    const uint64_t forced = forced_env ? std::strtoull(forced_env, nullptr, 10) : 0;
-    constexpr uint64_t kScratchBudget = uint64_t(64) << 20;
-    uint32_t segments = forced ? extremes_clamp_segments(forced, n_samples) : events_segments(units, n_samples);
-    segments = events_fit_segments(segments, units, kScratchBudget);
-    HIP_TRY(h, hipSetDevice(h->device));
-    acc.valid = false;
-    if (int rc = rd.claim(&hs.ev_scratch, static_cast<size_t>(events_scratch_bytes(segments, units))); rc != SIXDOF_OK) return rc;
-    if (events_record_bytes(units) > hs.ev_rec.bytes()) {   // never for a continuing call: its records are as large as the accumulator's
-        HIP_TRY(h, hipStreamSynchronize(h->stream.get()));   // an earlier call's launches may still use the old buffer
-        HIP_TRY(h, hs.ev_rec.alloc(static_cast<size_t>(events_record_bytes(units))));
-    }
     const uint32_t nt = static_cast<uint32_t>(n_triggers);
-    hipError_t e = launch_history_events(a, nt, hs.ev_rec.get(), hs.ev_stage.get<double>(), hs.ev_scratch.get(), segments, merge_into, n, period, first_tick,
-                                         n_samples, every, hs.ring, h->elem_size(), h->stream.get());
-    if (e != hipSuccess) return h->hip_fail(e, "history_events");
-    for (size_t k0 = 0; k0 < n_captures; k0 += kRingBinMaxComponents) {
-        const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_captures - k0));
-        RingBinArgs c{};
-        for (uint32_t k = 0; k < cnt; k++) {
-            const StagedRead::Part& p = rd.parts[1 + k0 + k];
-            c.c[k].ring = p.ring, c.c[k].out_offset = p.offset / sizeof(double), c.c[k].w = static_cast<uint32_t>(p.w);
-        }
-        e = launch_events_capture(a, nt, c, cnt, hs.ev_rec.get(), hs.ev_stage.get<double>(), merge_into, n, period, first_tick, n_samples, every, hs.ring,
-                                  h->elem_size(), h->stream.get());
-        if (e != hipSuccess) return h->hip_fail(e, "history_events capture");
-    }
-    if (!hold)
-        if (int rc = rd.deliver((flags & SIXDOF_EVENTS_ASYNC) != 0); rc != SIXDOF_OK) return rc;
-    acc.triggers.assign(triggers, triggers + n_triggers);
-    acc.capture_ids.assign(capture_ids, capture_ids + n_captures);
-    acc.rings.clear(), acc.widths.clear();
-    for (uint32_t k = 0; k < nt; k++) acc.rings.push_back(a.t[k].ring), acc.widths.push_back(a.t[k].w);
-    for (size_t k = 0; k < n_captures; k++) acc.rings.push_back(rd.parts[1 + k].ring), acc.widths.push_back(rd.parts[1 + k].w);
-    acc.n = n, acc.period = period;
-    acc.last_tick = first_tick + (n_samples - 1) * every;
-    acc.valid = true;
-    return SIXDOF_OK;
+    EventsArgs a{};
+    return time_scan_read(
+        h, spec, first_tick, n_samples, every, flags,
+        [&](bool&) -> int {
+            if (n_triggers == 0 || n_triggers > SIXDOF_EVENTS_MAX_TRIGGERS)
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(n_triggers) + " triggers, 1 to " + std::to_string(SIXDOF_EVENTS_MAX_TRIGGERS) + " can be asked for");
+            if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
+            if (n % period != 0)
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+            if (!triggers || (n_captures && !capture_ids) || (!hold && (!event_dst || (n_captures && !capture_dst))))
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
+            for (size_t k = 0; k < n_triggers; k++) {
+                const sixdof_event_trigger& t = triggers[k];
+                const std::string which = who + ": trigger " + std::to_string(k);
+                if (t.op > SIXDOF_EVENT_GE) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown op " + std::to_string(t.op));
+                if (t.mode > SIXDOF_EVENT_CROSSING) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown mode " + std::to_string(t.mode));
+                if (!std::isfinite(t.level)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": the level is not finite");
+                if (t.group >= period) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": group " + std::to_string(t.group) + " is not below period " + std::to_string(period));
+                size_t w = 0;
+                if (!watch_lookup(h, t.component_id, &a.t[k].ring, &w) || !a.t[k].ring) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, which + ": " + kOnlyRecorded);
+                if (t.element >= w) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": element " + std::to_string(t.element) + " is not below the component's width " + std::to_string(w));
+                a.t[k].level = t.level, a.t[k].w = static_cast<uint32_t>(w), a.t[k].element = t.element, a.t[k].group = t.group, a.t[k].op = t.op, a.t[k].mode = t.mode;
+            }
+            return SIXDOF_OK;
+        },
+        [&](StagedRead& rd, History::ScanState& next, std::vector<uint64_t>& units) -> int {
+            units.push_back(n / period * n_triggers);
+            rd.add_block(hold ? nullptr : event_dst, static_cast<size_t>(units[0]) * kEventsPlanes * sizeof(double));
+            next.signature = {n_triggers, period, n_captures};
+            for (uint32_t k = 0; k < nt; k++) {
+                const sixdof_event_trigger& t = triggers[k];
+                uint64_t level;
+                std::memcpy(&level, &t.level, sizeof(level));
+                next.signature.insert(next.signature.end(), {t.component_id, t.element, t.group, t.op, t.mode, level});
+                next.rings.push_back(a.t[k].ring), next.widths.push_back(a.t[k].w);
+            }
+            for (size_t k = 0; k < n_captures; k++) {
+                const int rc = rd.add(capture_ids[k], hold ? nullptr : capture_dst[k], static_cast<size_t>(n) * n_triggers, sizeof(double), kOnlyRecorded, !hold);
+                if (rc != SIXDOF_OK) return rc;
+                next.signature.push_back(capture_ids[k]);
+                next.rings.push_back(rd.parts[1 + k].ring), next.widths.push_back(rd.parts[1 + k].w);
+            }
+            return SIXDOF_OK;
+        },
+        [&](const StagedRead& rd, size_t, uint64_t units, uint32_t segments, bool merge_into) -> int {
+            if (events_record_bytes(units) > sc.rec.bytes()) {   // never for a continuing call: its records are as large as the accumulator's
+                HIP_TRY(h, hipStreamSynchronize(h->stream.get()));   // an earlier call's launches may still use the old buffer
+                HIP_TRY(h, sc.rec.alloc(static_cast<size_t>(events_record_bytes(units))));
+            }
+            hipError_t e = launch_history_events(a, nt, sc.rec.get(), sc.stage.get<double>(), sc.scratch.get(), segments, merge_into, n, period, first_tick, n_samples,
+                                                 every, hs.ring, h->elem_size(), h->stream.get());
+            if (e != hipSuccess) return h->hip_fail(e, "history_events");
+            for (size_t k0 = 0; k0 < n_captures; k0 += kRingBinMaxComponents) {
+                const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_captures - k0));
+                RingBinArgs c{};
+                for (uint32_t k = 0; k < cnt; k++) {
+                    const StagedRead::Part& p = rd.parts[1 + k0 + k];
+                    c.c[k].ring = p.ring, c.c[k].out_offset = p.offset / sizeof(double), c.c[k].w = static_cast<uint32_t>(p.w);
+                }
+                e = launch_events_capture(a, nt, c, cnt, sc.rec.get(), sc.stage.get<double>(), merge_into, n, period, first_tick, n_samples, every, hs.ring,
+                                          h->elem_size(), h->stream.get());
+                if (e != hipSuccess) return h->hip_fail(e, "history_events capture");
+            }
+            return SIXDOF_OK;
+        });
 } SIXDOF_ABI_CATCH(err_of(h))
 
 int sixdof_download_column(sixdof_handle* h, uint64_t component_id) try {

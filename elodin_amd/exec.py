@@ -771,7 +771,6 @@ class HipExec:
         batch's call delivers.  The ring is read on the compute stream, so a ring one batch deep is enough (enabled here unless
         enable_history already made one at least that large).  Returns (wall time in seconds, the dict of history_extremes);
         whatever happens, the caller's flags are restored and the handle is drained."""
-        import time
         names = [names] if isinstance(names, str) else list(names)
         n_batches, ticks_per_batch, every = int(n_batches), int(ticks_per_batch), int(every)
         n_samples = self._stream_shape("stream_extremes", ticks_per_batch, every)
@@ -779,6 +778,16 @@ class HipExec:
             raise ValueError("stream_extremes: at least one batch")
         raw, ptrs = self._extremes_buffers(names)
         comp = np.array([L.component_id(n) for n in names], dtype=np.uint64)
+        wall = self._stream_accumulate(n_batches, ticks_per_batch, every, L.EXTREMES_CONTINUE, L.EXTREMES_HOLD, flags,
+                                       lambda first, last, fl: self._extremes_read(comp, first, n_samples, every, ptrs if last else None, fl))
+        return wall, self._extremes_dict(names, raw)
+
+    def _stream_accumulate(self, n_batches: int, ticks_per_batch: int, every: int, continue_flag: int, hold_flag: int, flags: int, read) -> float:
+        """The loop of stream_extremes / stream_events: every batch is stepped and its samples — ending on the batch's last tick —
+        are merged into an accumulator on the device by `read(first_tick, last, read_flags)`: held unless the batch is the last,
+        continuing from the second batch on.  A ring one batch deep is enabled unless there is one at least that large.
+        Whatever happens, the caller's flags are restored and the handle is drained.  Returns the wall time in seconds."""
+        import time
         if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
             self.enable_history(ticks_per_batch)
         self.sync()              # nothing of an earlier streaming run is in flight
@@ -789,12 +798,11 @@ class HipExec:
                 first = self.tick + every                                # samples end on the batch's last tick
                 self.invoke_batch(ticks_per_batch)
                 last = i + 1 == n_batches
-                self._extremes_read(comp, first, n_samples, every, ptrs if last else None,
-                                    (L.EXTREMES_CONTINUE if i else 0) | (0 if last else L.EXTREMES_HOLD))
+                read(first, last, (continue_flag if i else 0) | (0 if last else hold_flag))
         finally:
             self.set_flags(flags)
             self.sync()
-        return time.perf_counter() - t0, self._extremes_dict(names, raw)
+        return time.perf_counter() - t0
 
     # ---- ring events: the first threshold crossing of every run, and the state there -----------------------------------
     EVENTS_FIELDS = ("tick", "value", "tick_before", "value_before")      # the four planes, in order
@@ -857,7 +865,6 @@ class HipExec:
         event.  Nothing crosses the link until the last batch's call delivers.  The ring is read on the compute stream, so a ring
         one batch deep is enough (enabled here unless enable_history already made one at least that large).  Returns (wall time
         in seconds, the dict of history_events); whatever happens, the caller's flags are restored and the handle is drained."""
-        import time
         triggers = self._event_triggers(events)
         capture = [capture] if isinstance(capture, str) else list(capture)
         n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
@@ -868,22 +875,10 @@ class HipExec:
             raise ValueError("stream_events: period must be at least 1")
         raw, caps, ptrs = self._events_buffers(len(triggers), capture, period)
         comp = np.array([L.component_id(n) for n in capture], dtype=np.uint64)
-        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
-            self.enable_history(ticks_per_batch)
-        self.sync()              # nothing of an earlier streaming run is in flight
-        self.set_flags(flags | L.FLAG_ASYNC_STEP)
-        t0 = time.perf_counter()
-        try:
-            for i in range(n_batches):
-                first = self.tick + every                                # samples end on the batch's last tick
-                self.invoke_batch(ticks_per_batch)
-                last = i + 1 == n_batches
-                self._events_read(triggers, comp, period, first, n_samples, every, raw if last else None, ptrs if last else None,
-                                  (L.EVENTS_CONTINUE if i else 0) | (0 if last else L.EVENTS_HOLD))
-        finally:
-            self.set_flags(flags)
-            self.sync()
-        return time.perf_counter() - t0, self._events_dict(capture, raw, caps)
+        wall = self._stream_accumulate(n_batches, ticks_per_batch, every, L.EVENTS_CONTINUE, L.EVENTS_HOLD, flags,
+                                       lambda first, last, fl: self._events_read(triggers, comp, period, first, n_samples, every, raw if last else None,
+                                                                                 ptrs if last else None, fl))
+        return wall, self._events_dict(capture, raw, caps)
 
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))
