@@ -36,6 +36,9 @@ EVENT_LEVEL, EVENT_CROSSING = 0, 1                    # sixdof_event_trigger.mod
 EVENTS_ASYNC, EVENTS_CONTINUE, EVENTS_HOLD = 1, 2, 4  # sixdof_history_events flags
 EVENTS_PLANES = 4         # tick, value, tick_before, value_before (SIXDOF_EVENTS_PLANES)
 EVENTS_MAX_TRIGGERS = 8   # triggers one call walks (SIXDOF_EVENTS_MAX_TRIGGERS)
+COVARIANCE_ASYNC = 1      # sixdof_history_covariance flags
+COVARIANCE_MAX_CHANNELS = 6   # channels one call reduces jointly (SIXDOF_COVARIANCE_MAX_CHANNELS)
+COVARIANCE_MAX_PERIOD = 256   # groups one call keeps apart (csrc/covariance_plan.hpp: kCovarianceMaxPeriod)
 
 EFF_CONST_WRENCH = 1
 EFF_UNIFORM_GRAVITY = 2
@@ -79,6 +82,10 @@ class Timings(C.Structure):
 class EventTrigger(C.Structure):   # sixdof_event_trigger, 32 bytes
     _fields_ = [("component_id", C.c_uint64), ("element", C.c_uint32), ("group", C.c_uint32), ("op", C.c_uint32), ("mode", C.c_uint32),
                 ("level", C.c_double)]
+
+
+class CovChannel(C.Structure):   # sixdof_cov_channel, 16 bytes
+    _fields_ = [("component_id", C.c_uint64), ("element", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Slot(C.Structure):
@@ -163,6 +170,8 @@ SYMBOLS = {
                                           C.c_uint32]),
     "sixdof_history_events": (C.c_int, [_H, C.POINTER(EventTrigger), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64,
                                         C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]),
+    "sixdof_history_covariance": (C.c_int, [_H, C.POINTER(CovChannel), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
+                                            C.c_uint32]),
     "sixdof_set_model_apollo": (C.c_int, [_H, C.c_void_p]),
     "sixdof_download_column": (C.c_int, [_H, C.c_uint64]),
     "sixdof_upload_column": (C.c_int, [_H, C.c_uint64]),

@@ -858,6 +858,20 @@ class Exec:
         out["time"] = time
         return out
 
+    def history_covariance(self, channels, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> Dict[str, Any]:
+        """How a few quantities vary TOGETHER across all entities, over time: {"time": seconds, "count": [samples, period], "mean":
+        [samples, period, k], "comoment", "cov", "corr": [samples, period, k, k]} for world ticks first_tick, first_tick + every,
+        ... <= last_tick, reduced on the device out of the ring (enable_history).  `channels`: 2 to 6 (component, element) pairs,
+        from one component or several.  Entry [j, g] covers the executor rows r with r % period == g; a row counts only if all
+        its channel values are finite (listwise), and count shows how many did."""
+        channels = [(str(comp), int(element)) for comp, element in channels]
+        for comp, element in channels:
+            self._refuse_unrecorded("history_covariance", f"{comp}[{element}]", comp)
+        (first, last, step), time = self._sampled_ticks("history_covariance", first_tick, last_tick, every)
+        out: Dict[str, Any] = dict(self._hip.history_covariance(channels, first, last, step, period))
+        out["time"] = time
+        return out
+
     def history_extremes(self, components, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
         """Every executor row collapsed ACROSS TIME: {component: {"count", "argmin", "argmax", "first_nonfinite": int64 [rows, w];
         "min", "max", "t_min", "t_max", "t_first_nonfinite": f64 [rows, w]}} over world ticks first_tick, first_tick + every, ...

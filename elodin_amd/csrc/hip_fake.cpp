@@ -19,6 +19,7 @@
 
 #include "../../include/sixdof_hip.h"
 #include "aql_chain.hpp"
+#include "covariance_plan.hpp"
 #include "envelope_plan.hpp"
 #include "events_plan.hpp"
 #include "extremes_plan.hpp"
@@ -302,6 +303,71 @@ hipError_t launch_history_envelope(const RingBinArgs& a, uint32_t n_components, 
             envelope_emit(r, to + uint64_t(bin / d.w) * kEnvelopeStats * d.w + bin % d.w, d.w);
         }
     }));
+}
+// the joint reduction itself (covariance_kernels.hip), serially: covariance_plan.hpp's arithmetic in the kernels' geometry and
+// merge order, through the launch's own scratch in the kernels' [block][field][period] layout
+template <int K>
+static bool covariance_walk(const CovarianceArgs& a, double* out, double* part, uint64_t partial_stride, uint64_t n, uint32_t period, uint64_t first_tick,
+                            uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem) {
+    constexpr uint32_t F = covariance_fields(K);
+    const CovarianceGeom g = covariance_geom(n, period);
+    if (!need(covariance_scratch_doubles(g, K, period) <= partial_stride, "covariance scratch of one sample")) return false;
+    std::vector<CovarianceRecord<K>> rec(kCovarianceThreads);
+    for (uint64_t j = 0; j < n_samples; j++) {
+        const uint64_t slot = sample_slot(first_tick, sample0 + j, every, ring);
+        const char* src[K];
+        for (int c = 0; c < K; c++) {
+            if (!need(a.c[c].element < a.c[c].w, "covariance channel element")) return false;
+            src[c] = static_cast<const char*>(a.c[c].ring) + slot * n * a.c[c].w * elem;
+            if (!need(live(src[c], n * a.c[c].w * elem), "ring block of a covariance channel")) return false;
+        }
+        double* mine = part + j * partial_stride;
+        double* to = out + (sample0 + j) * period * F;
+        if (!need(live(to, size_t(period) * F * sizeof(double)), "covariance staging")) return false;
+        for (uint32_t b = 0; b < g.blocks; b++) {                       // stage 1
+            for (uint32_t t = 0; t < g.tile; t++) {
+                CovarianceRecord<K> acc = covariance_empty<K>();
+                for (uint64_t row = uint64_t(b) * g.tile + t; row < n; row += uint64_t(g.blocks) * g.tile) {
+                    double x[K];
+                    for (int c = 0; c < K; c++) {
+                        const char* at = src[c] + (row * a.c[c].w + a.c[c].element) * elem;
+                        if (elem == 8) std::memcpy(&x[c], at, 8);
+                        else { float f; std::memcpy(&f, at, 4); x[c] = f; }
+                    }
+                    covariance_accumulate<K>(acc, x);
+                }
+                rec[t] = acc;
+            }
+            for (uint32_t grp = 0; grp < period; grp++) {
+                covariance_tree_fold<K>(&rec[grp], g.per_group, period);
+                for (uint32_t f = 0; f < F; f++) mine[(uint64_t(b) * F + f) * period + grp] = covariance_field(rec[grp], int(f));
+            }
+        }
+        for (uint32_t grp = 0; grp < period; grp++) {                   // stage 2
+            CovarianceRecord<K> r = covariance_empty<K>();
+            for (uint32_t b = 0; b < g.blocks; b++) {
+                CovarianceRecord<K> o;
+                for (uint32_t f = 0; f < F; f++) covariance_field(o, int(f)) = mine[(uint64_t(b) * F + f) * period + grp];
+                r = b == 0 ? o : covariance_merge<K>(r, o);
+            }
+            covariance_emit<K>(r, to + uint64_t(grp) * F);
+        }
+    }
+    return true;
+}
+hipError_t launch_history_covariance(const CovarianceArgs& a, uint32_t k, double* out, void* partial, uint64_t partial_stride, uint64_t n, uint32_t period,
+                                     uint64_t first_tick, uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t) {
+    if (!covariance_launch_ok(k, n_samples, period)) return launch(false);
+    double* part = static_cast<double*>(partial);
+    if (!need(live(part, n_samples * partial_stride * sizeof(double)), "covariance partial records")) return launch(false);
+    if (n == 0) return launch(true);
+    switch (k) {
+    case 2: return launch(covariance_walk<2>(a, out, part, partial_stride, n, period, first_tick, sample0, n_samples, every, ring, elem));
+    case 3: return launch(covariance_walk<3>(a, out, part, partial_stride, n, period, first_tick, sample0, n_samples, every, ring, elem));
+    case 4: return launch(covariance_walk<4>(a, out, part, partial_stride, n, period, first_tick, sample0, n_samples, every, ring, elem));
+    case 5: return launch(covariance_walk<5>(a, out, part, partial_stride, n, period, first_tick, sample0, n_samples, every, ring, elem));
+    default: return launch(covariance_walk<6>(a, out, part, partial_stride, n, period, first_tick, sample0, n_samples, every, ring, elem));
+    }
 }
 // the selection itself (quantile_kernels.hip), serially: quantile_plan.hpp's keys, scan step and lo -> hi rule, pass by pass in the
 // launch's own scratch (one sample's slots at a time: the histograms and states of a bin are where the kernels keep them)

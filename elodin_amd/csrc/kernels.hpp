@@ -221,6 +221,21 @@ hipError_t launch_events_capture(const EventsArgs& a, uint32_t n_triggers, const
                                  bool merge_into, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring,
                                  size_t elem, hipStream_t s);
 
+// ---- ring covariances: count, mean vector and co-moment matrix of k channels across the rows of every sampled tick (covariance_kernels.hip) ---
+constexpr uint32_t kCovarianceArgChannels = 6;   // covariance_plan.hpp: kCovarianceMaxChannels
+struct CovarianceChannel {
+    const void* ring;   // [ring][n, w] blocks of the channel's component
+    uint32_t w;
+    uint32_t element;   // < w
+};
+struct CovarianceArgs { CovarianceChannel c[kCovarianceArgChannels]; };   // by value: 96 bytes of kernel arguments
+// Samples sample0 .. sample0 + n_samples - 1 (n_samples < 65,536) of the range first_tick, first_tick + every, ...: stage 1 writes
+// `partial_stride` doubles per sample into `partial` (covariance_plan.hpp: covariance_scratch_doubles), stage 2 merges them in
+// block order into `out`, [n_samples of the whole read][period][1 + k + k (k + 1) / 2] doubles.  The caller has validated the range
+// (sampled_range_ok), n % period == 0, covariance_supported(k, period) and every element < w.
+hipError_t launch_history_covariance(const CovarianceArgs& a, uint32_t k, double* out, void* partial, uint64_t partial_stride, uint64_t n, uint32_t period,
+                                     uint64_t first_tick, uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
+
 hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags,
                             unsigned long long* count, hipStream_t s);
 

@@ -30,6 +30,7 @@
 #include "abi_guard.hpp"
 #include "device_mem.hpp"
 #include "aql_chain.hpp"
+#include "covariance_plan.hpp"
 #include "envelope_plan.hpp"
 #include "events_plan.hpp"
 #include "extremes_plan.hpp"
@@ -160,6 +161,8 @@ struct History {
     DeviceBuffer env_stage, env_partial;
     // sixdof_history_quantiles: its staging, and the histograms and slot states of one launch; the same rules
     DeviceBuffer quant_stage, quant_scratch;
+    // sixdof_history_covariance: its staging and the stage-1 partial records of one launch; the same rules
+    DeviceBuffer cov_stage, cov_partial;
     // A scan over time (time_scan_read: sixdof_history_extremes, sixdof_history_events): its staging, which is also the accumulator
     // a *_CONTINUE call merges into, the segment records of one launch and — the events only — the records its rule continues
     // from; the same rules.  `acc` says what the accumulator holds, if anything.
@@ -1649,6 +1652,76 @@ int sixdof_history_quantiles(sixdof_handle* h, const uint64_t* component_ids, si
             return launch_history_quantiles(a, cnt, ranks, hs.quant_stage.get<double>(), scratch, scratch + chunk * stride * kHistBytes, stride,
                                             h->desc.n_entities, period, first_tick, s0, ns, every, hs.ring, h->elem_size(), h->stream.get());
         });
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// The joint moments of sampled ticks: count, mean vector and co-moment matrix of 2 .. 6 channels, two reduction launches per chunk
+// of samples.  Ordering, ring reads and the copy lane exactly as for sixdof_history_envelope; not through ring_bin_read, whose
+// contract — bins, output blocks, scratch units — is per component: here a ROW is the unit, its channels may come from several
+// components and there is one output block.  Stateless: the channels are looked up per call.
+int sixdof_history_covariance(sixdof_handle* h, const sixdof_cov_channel* channels, size_t n_channels, uint64_t first_tick, uint64_t n_samples,
+                              uint64_t every, uint32_t period, double* host_dst, uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    History& hs = h->hist;
+    const std::string who = "history_covariance";
+    if (flags & ~SIXDOF_COVARIANCE_ASYNC) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": unknown flags");
+    if (!hs.ring) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": no history ring (sixdof_set_history)");
+    if (every == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": every must be at least 1");
+    if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
+    if (n_channels == 1)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": one channel has no co-moments: its count, mean and m2 are sixdof_history_envelope's");
+    if (n_channels < 2 || n_channels > SIXDOF_COVARIANCE_MAX_CHANNELS)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(n_channels) + " channels, 2 to " + std::to_string(SIXDOF_COVARIANCE_MAX_CHANNELS) + " can be asked for");
+    const uint64_t n = h->desc.n_entities;
+    if (n % period != 0)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+    if (period > kCovarianceMaxPeriod)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period " + std::to_string(period) + " exceeds the " + std::to_string(kCovarianceMaxPeriod) + " groups one block keeps apart");
+    if (n_samples == 0) return SIXDOF_OK;
+    if (!channels || !host_dst) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
+    const uint32_t k = static_cast<uint32_t>(n_channels);
+    const size_t fields = covariance_fields(k);
+    StagedRead rd{h, "history_covariance", &hs.cov_stage};
+    CovarianceArgs args{};
+    std::vector<uint64_t> seen;   // a component is looked up once, however many channels name it
+    for (uint32_t c = 0; c < k; c++) {
+        if (channels[c].reserved != 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": channel " + std::to_string(c) + ": reserved must be 0");
+        size_t at = std::find(seen.begin(), seen.end(), channels[c].component_id) - seen.begin();
+        if (at == seen.size()) {
+            const int rc = rd.add(channels[c].component_id, nullptr, 0, sizeof(double),
+                                  "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded", false);
+            if (rc != SIXDOF_OK) return rc;
+            seen.push_back(channels[c].component_id);
+        }
+        const StagedRead::Part& p = rd.parts[at];
+        if (channels[c].element >= p.w)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": channel " + std::to_string(c) + ": element " + std::to_string(channels[c].element) + " of a component " +
+                                                            std::to_string(p.w) + " wide");
+        args.c[c] = CovarianceChannel{p.ring, static_cast<uint32_t>(p.w), channels[c].element};
+    }
+    if (!sampled_range_ok(first_tick, n_samples, every, hs.first_tick, h->tick, hs.ring))
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": ticks are not (all) in the ring");
+    const size_t out_doubles = static_cast<size_t>(n_samples) * period * fields;
+    if (n == 0) {   // nothing to reduce: count 0, everything else NaN
+        for (size_t i = 0; i < out_doubles; i++) host_dst[i] = i % fields == 0 ? 0.0 : std::nan("");
+        return SIXDOF_OK;
+    }
+    rd.add_block(host_dst, out_doubles * sizeof(double));
+    // samples per launch: the scratch of one launch stays within a fixed budget, and the grid's y extent below 2^16
+    constexpr size_t kScratchBudget = size_t(64) << 20;
+    const size_t stride = covariance_scratch_doubles(covariance_geom(n, period), k, period), per_sample = stride * sizeof(double);
+    const char* chunk_env = std::getenv("SIXDOF_COVARIANCE_CHUNK");   // samples per launch, at most the plan's choice (tests)
+    const uint64_t forced = chunk_env ? std::strtoull(chunk_env, nullptr, 10) : 0;
+    uint64_t chunk = std::min<uint64_t>({n_samples, 65535, std::max<size_t>(1, kScratchBudget / per_sample)});
+    if (forced) chunk = std::min(chunk, forced);
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int rc = rd.claim(&hs.cov_partial, chunk * per_sample); rc != SIXDOF_OK) return rc;
+    double* staged = reinterpret_cast<double*>(hs.cov_stage.get<char>() + rd.parts.back().offset);
+    for (uint64_t s0 = 0; s0 < n_samples; s0 += chunk) {
+        hipError_t e = launch_history_covariance(args, k, staged, hs.cov_partial.get(), stride, n, period, first_tick, s0, std::min<uint64_t>(chunk, n_samples - s0), every,
+                                                 hs.ring, h->elem_size(), h->stream.get());
+        if (e != hipSuccess) return h->hip_fail(e, "history_covariance");
+    }
+    return rd.deliver((flags & SIXDOF_COVARIANCE_ASYNC) != 0);
 } SIXDOF_ABI_CATCH(err_of(h))
 
 }  // extern "C"

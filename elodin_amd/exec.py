@@ -67,6 +67,29 @@ class Event:
     MODES = {"level": L.EVENT_LEVEL, "crossing": L.EVENT_CROSSING}
 
 
+def dispersion_ellipse(cov2, prob: float = 0.99):
+    """(semi_major, semi_minor, angle) of the ellipse that holds the share `prob` of a bivariate normal population with the
+    2 x 2 covariance `cov2` — the landing footprint out of the x / y block of HipExec.history_covariance's "cov".  Closed-form
+    eigen-decomposition of the symmetric matrix (its off-diagonals are averaged); the semi-axes are sqrt(eigenvalue) times
+    sqrt(-2 ln(1 - prob)), the exact chi-square quantile at two degrees of freedom; angle, in radians in (-pi/2, pi/2], turns
+    the first axis onto the major one.  Broadcasts over leading axes: [..., 2, 2] -> three arrays [...].  ValueError: prob
+    outside (0, 1), a shape other than [..., 2, 2]."""
+    cov2 = np.asarray(cov2, dtype=np.float64)
+    if cov2.ndim < 2 or cov2.shape[-2:] != (2, 2):
+        raise ValueError(f"dispersion_ellipse: a [..., 2, 2] covariance is needed, not shape {cov2.shape}")
+    prob = float(prob)
+    if not 0.0 < prob < 1.0:
+        raise ValueError(f"dispersion_ellipse: prob {prob!r} is outside (0, 1)")
+    a, b, d = cov2[..., 0, 0], 0.5 * (cov2[..., 0, 1] + cov2[..., 1, 0]), cov2[..., 1, 1]
+    half_diff = 0.5 * (a - d)
+    major = 0.5 * (a + d) + np.hypot(half_diff, b)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        minor = np.where(major > 0, (a * d - b * b) / major, 0.0)      # the product of the eigenvalues is the determinant: no cancellation
+    scale = np.sqrt(-2.0 * np.log1p(-prob))
+    angle = 0.5 * np.arctan2(b, half_diff)
+    return scale * np.sqrt(np.maximum(major, 0.0)), scale * np.sqrt(np.maximum(minor, 0.0)), angle
+
+
 @dataclass(frozen=True)
 class _Reduction:
     """One reduction over the ring into (group, element) bins, as HipExec._reduce and _stream_reduce call it."""
@@ -726,6 +749,84 @@ class HipExec:
         "lower", "upper", "linear"}})` sees a batch once it has landed — first_tick is the batch's first SAMPLED tick; lower and
         upper are views of buffers reused two batches later.  Returns the wall time in seconds."""
         return self._stream_reduce("stream_quantiles", self._quantile_reduction(q), names, n_batches, ticks_per_batch, every, period, consume, flags)
+
+    # ---- ring covariances: count, mean vector and co-moment matrix of a few channels across the rows of every sampled tick -------
+    @staticmethod
+    def covariance_fields(k: int) -> int:
+        """Doubles of one (sample, group) entry of a k-channel read: count, k means, the k (k + 1) / 2 values of the upper triangle."""
+        return 1 + k + k * (k + 1) // 2
+
+    def _covariance_channels(self, who: str, channels):
+        """[(name, element), ...] -> the ctypes array.  ValueError: fewer than 2 or more than 6 channels, an element outside its
+        component's width (the library refuses the same; here the message names the channel)."""
+        channels = [(str(name), int(element)) for name, element in channels]
+        if len(channels) == 1:
+            raise ValueError(f"{who}: one channel has no co-moments: its count, mean and m2 are history_envelope's")
+        if not 2 <= len(channels) <= L.COVARIANCE_MAX_CHANNELS:
+            raise ValueError(f"{who}: {len(channels)} channels, 2 to {L.COVARIANCE_MAX_CHANNELS} can be asked for")
+        arr = (L.CovChannel * len(channels))()
+        for i, (name, element) in enumerate(channels):
+            w = self._recorded_width(name)
+            if not 0 <= element < w:
+                raise ValueError(f"{who}: channel {i}: element {element} of {name}, which is {w} wide")
+            arr[i].component_id, arr[i].element, arr[i].reserved = L.component_id(name), element, 0
+        return channels, arr
+
+    @staticmethod
+    def _covariance_dict(raw: np.ndarray, k: int) -> dict:
+        """[s, period, 1 + k + k (k + 1) / 2] -> {"count": int64 [s, period], "mean": [s, period, k], "comoment", "cov", "corr":
+        [s, period, k, k]}: the upper triangle mirrored into the full symmetric matrix, cov = comoment / count (the population
+        form, as the envelope's std = sqrt(m2 / count)), corr = C_ab / sqrt(C_aa C_bb), NaN where a diagonal is 0 or count is 0."""
+        s, period = raw.shape[:2]
+        count = raw[:, :, 0]
+        iu = np.triu_indices(k)
+        comoment = np.empty((s, period, k, k), dtype=np.float64)
+        comoment[:, :, iu[0], iu[1]] = raw[:, :, 1 + k:]
+        comoment[:, :, iu[1], iu[0]] = raw[:, :, 1 + k:]
+        diag = np.einsum("spaa->spa", comoment)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            cov = comoment / count[:, :, None, None]
+            scale = np.sqrt(diag[:, :, :, None] * diag[:, :, None, :])
+            corr = np.where(scale > 0, comoment / scale, np.nan)
+        return {"count": count.astype(np.int64), "mean": raw[:, :, 1:1 + k], "comoment": comoment, "cov": cov, "corr": corr}
+
+    def _covariance_read(self, arr, first_tick: int, n_samples: int, every: int, period: int, raw: np.ndarray, flags: int) -> None:
+        rc = self._lib.sixdof_history_covariance(self._h, arr, len(arr), first_tick, n_samples, every, period, raw.ctypes.data, flags)
+        if rc != L.OK:
+            _raise(self._h, rc, "sixdof_history_covariance")
+
+    def history_covariance(self, channels, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> dict:
+        """Joint moments of 2 to 6 channels — `channels` is a sequence of (component name, element) — over the rows of ticks
+        first_tick, first_tick + every, ... <= last_tick, reduced on the device out of the ring: {"count": int64 [s, period],
+        "mean": [s, period, k], "comoment", "cov", "corr": [s, period, k, k]}.  Entry [j, g] covers the rows r with r % period == g
+        (period = 1: all rows).  Listwise: a row counts only if all k channel values are finite, so the matrix is that of one
+        population; count == 0 leaves everything else NaN.  comoment[a, b] = sum (x_a - mean_a)(x_b - mean_b), cov = comoment /
+        count, corr the correlation matrix (NaN where a variance is 0).  Accumulated in f64.  Stateless: no watch is involved."""
+        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
+        channels, arr = self._covariance_channels("history_covariance", channels)
+        n_samples = self._sample_count(first_tick, last_tick, every)
+        raw = np.empty((n_samples, max(period, 1), self.covariance_fields(len(channels))), dtype=np.float64)
+        self._covariance_read(arr, first_tick, n_samples, every, max(period, 0), raw, 0)
+        return self._covariance_dict(raw, len(channels))
+
+    def stream_covariance(self, channels, n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, consume=None, flags: int = 0) -> float:
+        """stream_envelope for covariances: every `every`-th tick of every batch reduced on the compute stream and copied on the
+        copy stream into one of two host buffers while the next batch computes; a ring one batch deep is enough (enabled here
+        unless enable_history already made one at least that large).  `consume(batch_index, first_tick, {"count", "mean",
+        "comoment", "cov", "corr"})` sees a batch once it has landed — first_tick is the batch's first SAMPLED tick; mean is a
+        view of a buffer reused two batches later.  Returns the wall time in seconds."""
+        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
+        channels, arr = self._covariance_channels("stream_covariance", channels)
+        n_samples = self._stream_shape("stream_covariance", ticks_per_batch, every)
+        if period < 1:
+            raise ValueError("stream_covariance: period must be at least 1")
+        if getattr(self, "_ring_ticks", 0) < ticks_per_batch:
+            self.enable_history(ticks_per_batch)
+        raw = [np.empty((n_samples, period, self.covariance_fields(len(channels))), dtype=np.float64) for _ in range(2)]
+        self.sync()              # nothing of an earlier streaming run is in flight
+        return self._stream_batches(n_batches, ticks_per_batch, every,
+                                    lambda first_tick, k: self._covariance_read(arr, first_tick, n_samples, every, period, raw[k], L.COVARIANCE_ASYNC),
+                                    lambda k: self._covariance_dict(raw[k], len(channels)), consume, flags)
 
     # ---- ring extremes: every row collapsed across time, and the ticks its extremes fall on -----------------------------
     EXTREMES_FIELDS = ("count", "min", "argmin", "max", "argmax", "first_nonfinite")      # the six planes, in order

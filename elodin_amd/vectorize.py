@@ -325,6 +325,14 @@ class Campaign:
         count below n_runs."""
         return self.exec.history_quantiles(components, first_tick, last_tick, q, every, period=self.entities_per_run)
 
+    def covariance(self, channels, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
+        """How quantities vary together across the runs, over time, out of the device ring (self.exec.enable_history): {"time":
+        seconds, "count": [sample, entity-of-run], "mean": [sample, entity-of-run, k], "comoment", "cov", "corr": [sample,
+        entity-of-run, k, k]} over world ticks first_tick, first_tick + every, ... <= last_tick, for 2 to 6 channels (component,
+        element).  Entry [j, e] is taken over entity e of every run; a run counts only if all its channel values are finite.
+        The x / y block of "cov" at touchdown is what elodin_amd.dispersion_ellipse turns into the landing footprint."""
+        return self.exec.history_covariance(channels, first_tick, last_tick, every, period=self.entities_per_run)
+
     def extremes(self, components, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
         """Every run collapsed across time, out of the device ring (self.exec.enable_history): {component: {"count", "argmin",
         "argmax", "first_nonfinite", "min", "max", "t_min", "t_max", "t_first_nonfinite": [run, entity-of-run, w]}} over world ticks

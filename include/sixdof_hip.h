@@ -587,6 +587,42 @@ int sixdof_history_events(sixdof_handle* h, const sixdof_event_trigger* triggers
                           size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                           double* event_dst, double* const capture_dst[], uint32_t flags);
 
+/* ---- ring covariances: how quantities vary TOGETHER across the rows, over time ---------------------------------------------
+ * The landing footprint ellipse, the 6 x 6 position / velocity dispersion, whether touchdown speed goes with lateral miss: joint
+ * moments.  The envelope's mean and m2 are the diagonal of this matrix; the off-diagonals cannot be recovered from them.
+ *
+ * A channel is one element of one recorded component (the ones sixdof_history_read accepts; anything else:
+ * SIXDOF_ERR_COMPONENT_NOT_FOUND); 2 <= n_channels = k <= SIXDOF_COVARIANCE_MAX_CHANNELS, from one component or several, a channel
+ * may appear twice.  Samples and groups are sixdof_history_envelope's: for sample j (the state after tick first_tick + j * every)
+ * and group g < period, the rows r with r % period == g are reduced jointly.  host_dst receives
+ * [n_samples][period][1 + k + k (k + 1) / 2] doubles:
+ *   count           rows used.  LISTWISE: a row is used only if all k channel values are finite, otherwise it is skipped for every
+ *                   mean and every co-moment, so the matrix is that of one population (a non-finite value in an element that is
+ *                   not listed skips nothing)
+ *   mean[k]         over those rows
+ *   C[a][b], a <= b row-major upper triangle of sum (x_a - mean_a)(x_b - mean_b) over them (covariance = C / count).
+ * count = 0: everything behind the count is NaN.  Accumulated in f64 whatever the handle's dtype, by the multivariate Welford
+ * update and Chan / Pebay merges, without FMA contraction.  No floating-point atomics; the launch geometry and merge order depend
+ * on (n, period) only, so the values of one (tick, channel list, period) are bit-identical whichever range, `every` or flags read
+ * them, and a channel listed twice gives C_aa, C_ab and C_bb bit-equal.
+ * flags = 0: returns when the data is in host_dst.  SIXDOF_COVARIANCE_ASYNC: the rules of SIXDOF_WATCH_ASYNC — the copies go on
+ * the copy stream, sixdof_download_wait blocks until they have landed, host_dst stays allocated (and page-locked) until
+ * sixdof_sync.  Either way the ring is read on the compute stream: a later sixdof_step may overwrite the slots at once.
+ * n_samples = 0 is a no-op.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied: no ring, every = 0, period = 0, a row count that
+ * is no multiple of period, period above 256 (the groups one block of the kernel keeps apart), n_channels outside 2 .. 6 (one
+ * channel is the envelope's job), a null pointer, an element at or beyond its component's width, reserved != 0, a sampled tick
+ * that is not (or no longer) in the ring, unknown flags.  A call that fails in the runtime leaves the ring as it was; a staging
+ * or partial buffer that could not be grown is absent (size 0) and the next call allocates it again. */
+typedef struct {
+    uint64_t component_id;
+    uint32_t element;  /* < the component's width */
+    uint32_t reserved; /* 0 */
+} sixdof_cov_channel;  /* 16 bytes */
+#define SIXDOF_COVARIANCE_ASYNC 1u
+#define SIXDOF_COVARIANCE_MAX_CHANNELS 6
+int sixdof_history_covariance(sixdof_handle* h, const sixdof_cov_channel* channels, size_t n_channels, uint64_t first_tick,
+                              uint64_t n_samples, uint64_t every, uint32_t period, double* host_dst, uint32_t flags);
+
 /* ---- rollout models: systems piped AROUND six_dof, fused with it (the pipes of examples/<name>/sim.py) ------------- */
 struct sixdof_apollo_tables; /* include/sixdof_apollo.h */
 /* Select the Apollo-lander rollout model (examples/apollo-lander/sim.py:517-526 + the guidance sidecar
