@@ -24,6 +24,9 @@ size_t live_allocations();
 size_t live_streams();
 size_t live_events();
 size_t live_page_locks();
+enum { kAtOnce = 0, kMinimal = 1, kComputeFirst = 2, kCopyFirst = 3 };   // the ordered mode: hip_fake.cpp
+void set_schedule(int schedule);
+const char* schedule_name(int schedule);
 }  // namespace hip_fake
 
 namespace {
@@ -252,27 +255,37 @@ int main(int argc, char** argv) {
     case_rebind();
     check_clean("failed re-bind");
 
-    hip_fake::fail_after(-1);
-    Run clean;
-    clean.scenario();
-    check_clean("fault-free run");
-    if (clean.broken || clean.failed_steps) return std::fprintf(stderr, "capi_lifecycle_test: the fault-free run failed\n"), 1;
-    if (clean.w.nonfinite != 0) complain("fault-free run: count_nonfinite");
-    const long n_calls = clean.calls_before_destroy;
-    const uint64_t want = clean.w.digest();
-    for (long k = 0; k < n_calls; k++) {
-        const std::string run = "fault at call " + std::to_string(k);
-        Run r;
-        hip_fake::fail_after(k);
-        r.scenario();
+    // the sweep, with everything completing at once and once more with every stream a queue that runs at forcing points only: a
+    // fault in a deferred operation is then reported by the step that reaches it, and the reads are the same bytes
+    long n_calls = 0, n_lazy = 0;
+    uint64_t want = 0;
+    for (int schedule : {int(hip_fake::kAtOnce), int(hip_fake::kMinimal)}) {
+        const std::string mode = schedule == hip_fake::kAtOnce ? "" : std::string(hip_fake::schedule_name(schedule)) + ": ";
+        hip_fake::set_schedule(schedule);
         hip_fake::fail_after(-1);
-        if (r.broken) continue;   // said so already
-        if (r.failed_steps != 1) complain(run + ": no step reported it");
-        if (r.w.digest() != want) complain(run + ": the reads after the retry differ from the fault-free run's");
-        check_clean(run);
+        Run clean;
+        clean.scenario();
+        check_clean(mode + "fault-free run");
+        if (clean.broken || clean.failed_steps) return std::fprintf(stderr, "capi_lifecycle_test: the fault-free run failed\n"), 1;
+        if (clean.w.nonfinite != 0) complain(mode + "fault-free run: count_nonfinite");
+        (schedule == hip_fake::kAtOnce ? n_calls : n_lazy) = clean.calls_before_destroy;
+        if (schedule == hip_fake::kAtOnce) want = clean.w.digest();
+        else if (clean.w.digest() != want) complain(mode + "the fault-free run's reads differ from those with everything completing at once");
+        for (long k = 0; k < clean.calls_before_destroy; k++) {
+            const std::string run = mode + "fault at call " + std::to_string(k);
+            Run r;
+            hip_fake::fail_after(k);
+            r.scenario();
+            hip_fake::fail_after(-1);
+            if (r.broken) continue;   // said so already
+            if (r.failed_steps != 1) complain(run + ": no step reported it");
+            if (r.w.digest() != want) complain(run + ": the reads after the retry differ from the fault-free run's");
+            check_clean(run);
+        }
     }
+    hip_fake::set_schedule(hip_fake::kAtOnce);
     if (hip_fake::violations()) complain(std::to_string(hip_fake::violations()) + " violations reported by the fake runtime");
     if (g_failures) return std::fprintf(stderr, "capi_lifecycle_test: %d failures\n", g_failures), 1;
-    std::printf("capi_lifecycle_test: ok (3 named cases; N = %ld fallible calls, each failed once)\n", n_calls);
+    std::printf("capi_lifecycle_test: ok (3 named cases; N = %ld fallible calls, each failed once; %ld more under the minimal schedule)\n", n_calls, n_lazy);
     return 0;
 }

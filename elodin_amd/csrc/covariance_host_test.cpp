@@ -297,5 +297,6 @@ int main() {
     empty_group();
     refusals();
     failure_injection("covariance_host_test", kSwept, {true});
+    failure_injection("covariance_host_test", kSwept, {true}, hip_fake::kCopyFirst);
     return verdict("covariance_host_test");
 }

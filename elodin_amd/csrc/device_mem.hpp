@@ -73,11 +73,21 @@ class DeviceBuffer {
 // A host range this library page-locked.  A range that cannot be locked stays pageable (copies are then staged): no error.
 struct PinnedFree { void operator()(void* p) const { (void)hipHostUnregister(p); } };
 class PinnedRange : public Owner<void*, PinnedFree> {
+    size_t bytes_ = 0;   // of the range while it is locked
   public:
     bool lock(void* p, size_t bytes) {
         reset();
-        if (hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess) return *out() = p, true;
+        if (hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess) return *out() = p, bytes_ = bytes, true;
         return (void)hipGetLastError(), false;
+    }
+    // how [p, p + bytes) lies to the locked range
+    bool contains(const void* p, size_t bytes) const {
+        const char *lo = static_cast<const char*>(get()), *q = static_cast<const char*>(p);
+        return lo && lo <= q && q + bytes <= lo + bytes_;
+    }
+    bool intersects(const void* p, size_t bytes) const {
+        const char *lo = static_cast<const char*>(get()), *q = static_cast<const char*>(p);
+        return lo && lo < q + bytes && q < lo + bytes_;
     }
 };
 

@@ -172,5 +172,6 @@ int main() {
     two_readers_one_lane(true);
     stream_across_the_wrap();
     for (const SweptRead& swept : kSweptReads) failure_injection("envelope_host_test", swept, {true});
+    for (const SweptRead& swept : kSweptReads) failure_injection("envelope_host_test", swept, {true}, hip_fake::kCopyFirst);
     return verdict("envelope_host_test");
 }

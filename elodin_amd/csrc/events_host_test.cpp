@@ -505,6 +505,7 @@ int main() {
     more_captures_than_one_launch();
     force_segments(2);
     failure_injection("events_host_test", kSwept, {true, false, true});
+    failure_injection("events_host_test", kSwept, {true, false, true}, hip_fake::kComputeFirst);
     force_segments(0);
     return verdict("events_host_test");
 }

@@ -321,6 +321,7 @@ int main() {
     more_components_than_one_launch();
     force_segments(2);
     failure_injection("extremes_host_test", kSwept, {true, false, true});
+    failure_injection("extremes_host_test", kSwept, {true, false, true}, hip_fake::kComputeFirst);
     force_segments(0);
     return verdict("extremes_host_test");
 }

@@ -7,11 +7,31 @@
 // launches) returns hipErrorOutOfMemory when armed; frees and destroys always succeed.  The fake keeps the live
 // allocations, streams, events and page locks, and its launch stubs check that every table a launch is handed lies
 // inside a live allocation of sufficient size.
+//
+// The ordered mode (hip_fake::set_schedule, order_host_test.cpp) drops "everything completes at once": every stream is a FIFO of
+// deferred operations — copies, memsets, the launch stubs, event records and waits on events — with the arguments captured by value
+// and the checks made when the operation runs.  Nothing runs before a forcing point (a synchronisation, a synchronous copy, a
+// destruction).  What a forcing point runs, and in which order where the waits leave it free, is the schedule's choice:
+//     kMinimal        only what the forcing point itself is entitled to: the stream or event named, and what it waits on
+//     kComputeFirst   everything queued anywhere, the streams in order of their creation (a handle's compute stream runs ahead)
+//     kCopyFirst      everything queued anywhere, the youngest stream first (the copy lane runs ahead as far as its waits allow)
+// All three are orders a device may legally take.  The host destination of a queued device-to-host copy is filled with 0xFF bytes
+// (a NaN in f32 and f64) when it is enqueued, so a host read before completion is a value; device destinations are left alone.
+// hipFree of an allocation a queued operation names and hipHostUnregister of a range a queued copy touches are violations, and a
+// freed allocation's address is not handed out again while anything is queued, so a late operation cannot pass its check by luck.
+// An injected fault in a deferred operation surfaces at the forcing point that reaches it: that call fails, the operation stays
+// queued, and the next forcing point runs it — nothing is lost, as for a wait that was interrupted.  In every mode a page lock
+// keeps its extent: an overlapping registration is refused, and a copy whose host side straddles the edge of a lock is a violation.
+// What the fake still does not know: device page mappings (an access inside a live allocation's slack is invisible), other
+// processes, and the runtime's internal pools and staging buffers.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
+#include <functional>
 #include <map>
 #include <set>
 #include <string>
@@ -30,9 +50,36 @@
 namespace hip_fake {
 
 std::map<const char*, size_t> g_allocs;
-std::set<void*> g_streams, g_events, g_pins;
+std::set<void*> g_streams, g_events;
+std::map<const char*, size_t> g_pins;   // page locks: start -> bytes
 long g_calls = 0, g_fail_at = -1, g_violations = 0;
 bool g_fired = false;
+
+// ---- the ordered mode -------------------------------------------------------------------------------------------------
+enum { kAtOnce = 0, kMinimal = 1, kComputeFirst = 2, kCopyFirst = 3 };
+int g_schedule = kAtOnce;
+bool g_running = false;   // a deferred operation is being run: what it calls of the runtime happens at once
+struct Op {
+    std::string what;
+    std::function<hipError_t()> run;    // empty: an event record or a wait
+    std::vector<const void*> dev;       // the device pointers it names
+    const char* host = nullptr;         // the host side of a copy
+    size_t host_bytes = 0;
+    void* wait_stream = nullptr;        // a wait: that stream must have completed wait_pos operations
+    uint64_t wait_pos = 0;
+};
+struct Queue {
+    uint64_t order = 0;                 // of creation
+    bool non_blocking = false;
+    std::deque<Op> ops;
+    uint64_t done = 0;
+    uint64_t enqueued() const { return done + ops.size(); }
+};
+struct Record { void* stream = nullptr; uint64_t pos = 0; };
+std::map<void*, Queue> g_queues;        // by stream
+std::map<void*, Record> g_records;      // by event: its latest record
+std::vector<void*> g_quarantine;        // freed while something was queued: given back once every queue is empty
+uint64_t g_order = 0;
 
 void fail_after(long n) { g_fail_at = n < 0 ? -1 : g_calls + n, g_fired = false; }   // the n-th fallible call from now fails (once); < 0: none
 bool fired() { return g_fired; }
@@ -42,6 +89,21 @@ size_t live_allocations() { return g_allocs.size(); }
 size_t live_streams() { return g_streams.size(); }
 size_t live_events() { return g_events.size(); }
 size_t live_page_locks() { return g_pins.size(); }
+// whether any page lock intersects [p, p + bytes)
+bool lock_intersects(const void* p, size_t bytes) {
+    const char* lo = static_cast<const char*>(p);
+    for (auto& kv : g_pins)
+        if (kv.first < lo + bytes && lo < kv.first + kv.second) return true;
+    return false;
+}
+size_t queued() {
+    size_t n = 0;
+    for (auto& kv : g_queues) n += kv.second.ops.size();
+    return n;
+}
+const char* schedule_name(int schedule) {
+    return schedule == kAtOnce ? "at-once" : schedule == kMinimal ? "minimal" : schedule == kComputeFirst ? "compute-first" : "copy-first";
+}
 
 static hipError_t fallible() {
     if (g_calls++ != g_fail_at) return hipSuccess;
@@ -60,8 +122,77 @@ static bool need(bool ok, const char* what) {
     return ok;
 }
 static hipError_t launch(bool ok) {
-    if (hipError_t e = fallible(); e != hipSuccess) return e;
+    if (!g_running)   // a deferred operation was counted (and may have been failed) before it ran
+        if (hipError_t e = fallible(); e != hipSuccess) return e;
     return ok ? hipSuccess : hipErrorInvalidValue;
+}
+
+static void flush_quarantine() {
+    if (queued()) return;
+    for (void* p : g_quarantine) std::free(p);
+    g_quarantine.clear();
+}
+// Runs the operations of stream s until `upto` of them have completed, and before each wait what it waits on.  An injected fault
+// leaves its operation queued and ends the drain; an operation that fails its own checks is dropped, and reported once the drain is done.
+static hipError_t drain(void* s, uint64_t upto) {
+    auto it = g_queues.find(s);
+    if (it == g_queues.end()) return hipSuccess;   // destroyed, hence drained
+    Queue& q = it->second;
+    hipError_t first = hipSuccess;
+    while (q.done < upto && !q.ops.empty()) {
+        Op& op = q.ops.front();
+        if (op.wait_stream)
+            if (hipError_t e = drain(op.wait_stream, op.wait_pos); e != hipSuccess) return e;
+        if (op.run) {
+            if (hipError_t e = fallible(); e != hipSuccess) return e;
+            g_running = true;
+            const hipError_t e = op.run();
+            g_running = false;
+            if (e != hipSuccess && first == hipSuccess) first = e;
+        }
+        q.ops.pop_front();
+        q.done++;
+    }
+    return first;
+}
+static hipError_t drain_all(bool youngest_first, bool blocking_only = false) {
+    std::vector<std::pair<uint64_t, void*>> order;
+    for (auto& kv : g_queues)
+        if (!blocking_only || !kv.second.non_blocking) order.emplace_back(kv.second.order, kv.first);
+    std::sort(order.begin(), order.end());
+    if (youngest_first) std::reverse(order.begin(), order.end());
+    hipError_t first = hipSuccess;
+    for (auto& o : order) {
+        auto it = g_queues.find(o.second);
+        if (it == g_queues.end()) continue;
+        const hipError_t e = drain(o.second, it->second.enqueued());
+        if (e == hipErrorOutOfMemory) return e;
+        if (e != hipSuccess && first == hipSuccess) first = e;
+    }
+    return first;
+}
+// A forcing point: stream s has to complete `upto` operations (s null: every stream everything).
+static hipError_t force(void* s, uint64_t upto) {
+    hipError_t e;
+    if (g_schedule == kComputeFirst || g_schedule == kCopyFirst) e = drain_all(g_schedule == kCopyFirst);
+    else e = s ? drain(s, upto) : drain_all(false);
+    flush_quarantine();
+    return e;
+}
+static bool deferring() { return g_schedule != kAtOnce && !g_running; }
+static hipError_t defer(hipStream_t s, const char* what, std::vector<const void*> dev, std::function<hipError_t()> run, const void* host = nullptr, size_t host_bytes = 0) {
+    auto it = g_queues.find(s);
+    if (it == g_queues.end()) return need(false, (std::string(what) + " on a null or destroyed stream").c_str()), hipErrorInvalidHandle;
+    Op op;
+    op.what = what, op.run = std::move(run), op.dev = std::move(dev), op.host = static_cast<const char*>(host), op.host_bytes = host_bytes;
+    it->second.ops.push_back(std::move(op));
+    return hipSuccess;
+}
+// kAtOnce: everything completes at once (the default); otherwise one of the schedules above.  Whatever is queued runs first.
+void set_schedule(int schedule) {
+    (void)drain_all(false), (void)drain_all(false);   // twice: an armed fault may have ended the first pass
+    flush_quarantine();
+    g_schedule = schedule;
 }
 
 }  // namespace hip_fake
@@ -81,8 +212,21 @@ hipError_t hipMalloc(void** p, size_t bytes) {
 }
 hipError_t hipFree(void* p) {
     if (!p) return hipSuccess;
-    if (!g_allocs.erase(static_cast<const char*>(p))) std::fprintf(stderr, "hip_fake: hipFree of %p, which is not a live allocation\n", p), g_violations++;
-    std::free(p);   // a second free of the same pointer is AddressSanitizer's to report
+    auto it = g_allocs.find(static_cast<const char*>(p));
+    if (it == g_allocs.end()) {
+        std::fprintf(stderr, "hip_fake: hipFree of %p, which is not a live allocation\n", p), g_violations++;
+        std::free(p);   // a second free of the same pointer is AddressSanitizer's to report
+        return hipSuccess;
+    }
+    // the real hipFree synchronises; the host layer must not lean on that
+    for (auto& kv : g_queues)
+        for (const Op& op : kv.second.ops)
+            for (const void* d : op.dev)
+                if (d >= it->first && d < it->first + (it->second ? it->second : 1))
+                    std::fprintf(stderr, "hip_fake: hipFree of an allocation that a queued %s still names\n", op.what.c_str()), g_violations++;
+    g_allocs.erase(it);
+    if (queued()) g_quarantine.push_back(p);
+    else std::free(p);
     return hipSuccess;
 }
 static hipError_t create(std::set<void*>& live_set, void** out) {
@@ -96,18 +240,50 @@ static hipError_t destroy(std::set<void*>& live_set, void* p) {
     std::free(p);
     return hipSuccess;
 }
+static hipError_t create_stream(hipStream_t* s, unsigned flags) {
+    const hipError_t e = create(g_streams, reinterpret_cast<void**>(s));
+    if (e == hipSuccess) g_queues[*s].order = g_order++, g_queues[*s].non_blocking = (flags & hipStreamNonBlocking) != 0;
+    return e;
+}
 // a stream or event handed to record / wait / synchronise: null or destroyed is an error (the null stream is legal to query only)
 static hipError_t use(bool ok) {
     if (hipError_t e = fallible(); e != hipSuccess) return e;
     if (!ok) std::fprintf(stderr, "hip_fake: null or destroyed stream / event\n"), g_violations++;
     return ok ? hipSuccess : hipErrorInvalidHandle;
 }
-hipError_t hipStreamCreate(hipStream_t* s) { return create(g_streams, reinterpret_cast<void**>(s)); }
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return create(g_streams, reinterpret_cast<void**>(s)); }
-hipError_t hipStreamDestroy(hipStream_t s) { return destroy(g_streams, s); }
-hipError_t hipStreamSynchronize(hipStream_t s) { return use(g_streams.count(s)); }
-hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { return use(g_streams.count(s) && g_events.count(e)); }
+hipError_t hipStreamCreate(hipStream_t* s) { return create_stream(s, 0); }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags) { return create_stream(s, flags); }
+// destroying a stream or an event with work outstanding is legal: the work completes first
+hipError_t hipStreamDestroy(hipStream_t s) {
+    if (auto it = g_queues.find(s); it != g_queues.end()) {
+        (void)drain(s, it->second.enqueued());
+        g_queues.erase(s);
+        flush_quarantine();
+    }
+    return destroy(g_streams, s);
+}
+hipError_t hipStreamSynchronize(hipStream_t s) {
+    if (hipError_t e = use(g_streams.count(s)); e != hipSuccess) return e;
+    return force(s, g_queues[s].enqueued());
+}
+hipError_t hipDeviceSynchronize(void) {
+    if (hipError_t e = fallible(); e != hipSuccess) return e;
+    return force(nullptr, 0);
+}
+hipError_t hipStreamQuery(hipStream_t s) {
+    auto it = g_queues.find(s);
+    return it != g_queues.end() && !it->second.ops.empty() ? hipErrorNotReady : hipSuccess;
+}
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    if (hipError_t r = use(g_streams.count(s) && g_events.count(e)); r != hipSuccess) return r;
+    if (!deferring()) return hipSuccess;
+    auto rec = g_records.find(e);
+    if (rec == g_records.end()) return hipSuccess;   // never recorded: nothing to wait for
+    Op op;
+    op.what = "wait", op.wait_stream = rec->second.stream, op.wait_pos = rec->second.pos;
+    g_queues[s].ops.push_back(std::move(op));
+    return hipSuccess;
+}
 hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipErrorNotSupported; }
 hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { return *g = nullptr, hipErrorNotSupported; }
 hipError_t hipGraphInstantiate(hipGraphExec_t*, hipGraph_t, hipGraphNode_t*, char*, size_t) { return hipErrorNotSupported; }
@@ -117,27 +293,100 @@ hipError_t hipGraphUpload(hipGraphExec_t, hipStream_t) { return hipErrorNotSuppo
 hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipErrorNotSupported; }
 hipError_t hipEventCreate(hipEvent_t* e) { return create(g_events, reinterpret_cast<void**>(e)); }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return create(g_events, reinterpret_cast<void**>(e)); }
-hipError_t hipEventDestroy(hipEvent_t e) { return destroy(g_events, e); }
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { return use(g_events.count(e) && g_streams.count(s)); }
-hipError_t hipEventSynchronize(hipEvent_t e) { return use(g_events.count(e)); }
-hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) {
+    if (auto rec = g_records.find(e); rec != g_records.end()) {
+        (void)drain(rec->second.stream, rec->second.pos);
+        g_records.erase(rec);
+        flush_quarantine();
+    }
+    return destroy(g_events, e);
+}
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    if (hipError_t r = use(g_events.count(e) && g_streams.count(s)); r != hipSuccess) return r;
+    if (!deferring()) return g_records.erase(e), hipSuccess;
+    Op op;
+    op.what = "record";
+    Queue& q = g_queues[s];
+    q.ops.push_back(std::move(op));
+    g_records[e] = Record{s, q.enqueued()};
+    return hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e) {
+    if (hipError_t r = use(g_events.count(e)); r != hipSuccess) return r;
+    auto rec = g_records.find(e);
+    return rec == g_records.end() ? hipSuccess : force(rec->second.stream, rec->second.pos);
+}
+hipError_t hipEventQuery(hipEvent_t e) {
+    auto rec = g_records.find(e);
+    if (rec == g_records.end()) return hipSuccess;
+    auto q = g_queues.find(rec->second.stream);
+    return q != g_queues.end() && q->second.done < rec->second.pos ? hipErrorNotReady : hipSuccess;
+}
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { return *ms = 0.f, hipSuccess; }
-hipError_t hipHostRegister(void* p, size_t, unsigned) { return g_pins.insert(p).second ? hipSuccess : hipErrorHostMemoryAlreadyRegistered; }
-hipError_t hipHostUnregister(void* p) { return g_pins.erase(p) ? hipSuccess : hipErrorHostMemoryNotRegistered; }
+hipError_t hipHostRegister(void* p, size_t bytes, unsigned) {
+    if (!p || !bytes) return hipErrorInvalidValue;
+    if (lock_intersects(p, bytes)) return hipErrorHostMemoryAlreadyRegistered;
+    g_pins[static_cast<const char*>(p)] = bytes;
+    return hipSuccess;
+}
+hipError_t hipHostUnregister(void* p) {
+    auto it = g_pins.find(static_cast<const char*>(p));
+    if (it == g_pins.end()) return hipErrorHostMemoryNotRegistered;
+    for (auto& kv : g_queues)
+        for (const Op& op : kv.second.ops)
+            if (op.host && op.host < it->first + it->second && it->first < op.host + op.host_bytes)
+                std::fprintf(stderr, "hip_fake: hipHostUnregister of a range that a queued %s still touches\n", op.what.c_str()), g_violations++;
+    g_pins.erase(it);
+    return hipSuccess;
+}
+// the host side of a copy lies wholly inside a page lock or touches none: what the runtime does with a partly locked range is unspecified
+static void host_extent(const void* p, size_t bytes, const char* what) {
+    const char* lo = static_cast<const char*>(p);
+    for (auto& kv : g_pins)
+        if (kv.first < lo + bytes && lo < kv.first + kv.second && !(kv.first <= lo && lo + bytes <= kv.first + kv.second))
+            std::fprintf(stderr, "hip_fake: the host side of a %s of %zu bytes straddles the edge of a page lock of %zu bytes\n", what, bytes, kv.second), g_violations++;
+}
 // whichever side is device memory must be live; the other side is the caller's (AddressSanitizer watches the memcpy itself)
 static hipError_t copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    if (hipError_t e = fallible(); e != hipSuccess) return e;
+    if (!g_running)
+        if (hipError_t e = fallible(); e != hipSuccess) return e;
     const bool dst_dev = kind == hipMemcpyHostToDevice || kind == hipMemcpyDeviceToDevice, src_dev = kind == hipMemcpyDeviceToHost || kind == hipMemcpyDeviceToDevice;
     if (!need(!dst_dev || live(dst, bytes), "copy destination") || !need(!src_dev || live(src, bytes), "copy source")) return hipErrorInvalidValue;
     std::memcpy(dst, src, bytes);
     return hipSuccess;
 }
-hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { return copy(dst, src, bytes, kind); }
-hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
-    return need(g_streams.count(s), "copy on a null or destroyed stream") ? copy(dst, src, bytes, kind) : hipErrorInvalidHandle;
+static const char* copy_name(hipMemcpyKind kind) {
+    return kind == hipMemcpyDeviceToHost ? "device-to-host copy" : kind == hipMemcpyHostToDevice ? "host-to-device copy" : "device-to-device copy";
 }
-hipError_t hipMemsetAsync(void* dst, int v, size_t bytes, hipStream_t) {
-    if (hipError_t e = fallible(); e != hipSuccess) return e;
+static void copy_host_side(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (kind == hipMemcpyDeviceToHost) host_extent(dst, bytes, copy_name(kind));
+    if (kind == hipMemcpyHostToDevice) host_extent(src, bytes, copy_name(kind));
+}
+// the synchronous form waits for the null stream, and with it for every blocking stream; then it runs at once
+hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    copy_host_side(dst, src, bytes, kind);
+    if (deferring()) {
+        const hipError_t e = g_schedule == kMinimal ? drain_all(false, true) : force(nullptr, 0);
+        flush_quarantine();
+        if (e != hipSuccess) return e;
+    }
+    return copy(dst, src, bytes, kind);
+}
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    if (!need(g_streams.count(s), "copy on a null or destroyed stream")) return hipErrorInvalidHandle;
+    copy_host_side(dst, src, bytes, kind);
+    if (!deferring()) return copy(dst, src, bytes, kind);
+    std::vector<const void*> dev;
+    if (kind != hipMemcpyHostToDevice) dev.push_back(src);
+    if (kind != hipMemcpyDeviceToHost) dev.push_back(dst);
+    const void* host = kind == hipMemcpyDeviceToHost ? dst : kind == hipMemcpyHostToDevice ? src : nullptr;
+    if (kind == hipMemcpyDeviceToHost) std::memset(dst, 0xFF, bytes);   // poison: a NaN in either width until the copy has run
+    return defer(s, copy_name(kind), std::move(dev), [=] { return copy(dst, src, bytes, kind); }, host, host ? bytes : 0);
+}
+hipError_t hipMemsetAsync(void* dst, int v, size_t bytes, hipStream_t s) {
+    if (deferring()) return defer(s, "memset", {dst}, [=] { return hipMemsetAsync(dst, v, bytes, s); });
+    if (!g_running)
+        if (hipError_t e = fallible(); e != hipSuccess) return e;
     if (!need(live(dst, bytes), "memset destination")) return hipErrorInvalidValue;
     std::memset(dst, v, bytes);
     return hipSuccess;
@@ -190,7 +439,8 @@ static bool pair_ok(const PairParams& p) {
 StepKernel select_step(const StepParams&, int, int) { return {}; }
 // no arithmetic, but a recording launch leaves the (unchanged) Body columns in the ring slots of its ticks, as the kernel does:
 // what reads the ring (history_read, watch_read, history_envelope) then sees what was uploaded before the step
-hipError_t launch_step(const StepParams& p, int, int dtype, hipStream_t) {
+hipError_t launch_step(const StepParams& p, int integrator, int dtype, hipStream_t s) {
+    if (deferring()) return defer(s, "launch_step", {p.pos, p.vel, p.accel, p.force, p.hist_pos, p.hist_vel, p.hist_accel, p.hist_force}, [=] { return launch_step(p, integrator, dtype, s); });
     const bool ok = step_ok(p, dtype);
     if (ok && p.hist_ring && p.hist_pos) {
         const size_t es = dtype == 1 ? 4 : 8;
@@ -205,9 +455,16 @@ hipError_t launch_step(const StepParams& p, int, int dtype, hipStream_t) {
     return launch(ok);
 }
 uint32_t pair_splits_for(uint32_t) { return 1; }
-hipError_t launch_pair_ticks(const PairParams& p, int, uint32_t n_ticks, hipStream_t, uint64_t* launches) { return *launches += 1 + 2 * n_ticks, launch(pair_ok(p)); }
-hipError_t launch_pair_small(const PairParams& p, int, uint32_t, hipStream_t, uint64_t* launches) { return *launches += 1, launch(pair_ok(p)); }
-hipError_t launch_apollo(const ApolloParams&, hipStream_t) { return launch(true); }
+static hipError_t launch_pair(const PairParams& p, hipStream_t s) {
+    if (deferring()) return defer(s, "pair launch", {p.pos, p.vel, p.accel, p.force, p.pack, p.partial}, [=] { return launch(pair_ok(p)); });
+    return launch(pair_ok(p));
+}
+hipError_t launch_pair_ticks(const PairParams& p, int, uint32_t n_ticks, hipStream_t s, uint64_t* launches) { return *launches += 1 + 2 * n_ticks, launch_pair(p, s); }
+hipError_t launch_pair_small(const PairParams& p, int, uint32_t, hipStream_t s, uint64_t* launches) { return *launches += 1, launch_pair(p, s); }
+hipError_t launch_apollo(const ApolloParams&, hipStream_t s) {
+    if (deferring()) return defer(s, "launch_apollo", {}, [] { return launch(true); });
+    return launch(true);
+}
 
 static hipError_t move_rows(char* dst, const char* src, const uint32_t* rows, uint32_t m, size_t row, bool gather) {
     if (!need(live(rows, m * sizeof(uint32_t)), "join rows")) return launch(false);
@@ -219,15 +476,22 @@ static hipError_t move_rows(char* dst, const char* src, const uint32_t* rows, ui
     }
     return launch(true);
 }
-hipError_t launch_gather_rows(void* dst, const void* src, const uint32_t* rows, uint32_t m, uint32_t w, size_t elem, hipStream_t) {
+hipError_t launch_gather_rows(void* dst, const void* src, const uint32_t* rows, uint32_t m, uint32_t w, size_t elem, hipStream_t s) {
+    if (deferring()) return defer(s, "gather_rows", {dst, src, rows}, [=] { return launch_gather_rows(dst, src, rows, m, w, elem, s); });
     return move_rows(static_cast<char*>(dst), static_cast<const char*>(src), rows, m, w * elem, true);
 }
-hipError_t launch_scatter_rows(void* dst, const void* src, const uint32_t* rows, uint32_t m, uint32_t w, size_t elem, hipStream_t) {
+hipError_t launch_scatter_rows(void* dst, const void* src, const uint32_t* rows, uint32_t m, uint32_t w, size_t elem, hipStream_t s) {
+    if (deferring()) return defer(s, "scatter_rows", {dst, src, rows}, [=] { return launch_scatter_rows(dst, src, rows, m, w, elem, s); });
     return move_rows(static_cast<char*>(dst), static_cast<const char*>(src), rows, m, w * elem, false);
 }
 // the gather itself (join_kernels.hip), so that watch reads return what the ring holds
 hipError_t launch_history_gather(const HistoryGatherArgs& a, uint32_t n_components, void* out, const uint32_t* rows, uint64_t m, uint64_t n,
-                                 uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t) {
+                                 uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
+    if (deferring()) {
+        std::vector<const void*> dev{out, rows};
+        for (uint32_t c = 0; c < n_components; c++) dev.push_back(a.c[c].ring);
+        return defer(s, "history_gather", std::move(dev), [=] { return launch_history_gather(a, n_components, out, rows, m, n, first_tick, n_samples, every, ring, elem, s); });
+    }
     if (!need(live(rows, m * sizeof(uint32_t)), "watch rows")) return launch(false);
     for (uint32_t c = 0; c < n_components; c++) {
         const size_t row = a.c[c].w * elem;
@@ -266,7 +530,14 @@ static bool ring_bin_walk(const char* who, const RingBinArgs& a, uint32_t n_comp
 // the reduction itself (envelope_kernels.hip), serially: envelope_plan.hpp's arithmetic in the kernels' geometry and merge order
 hipError_t launch_history_envelope(const RingBinArgs& a, uint32_t n_components, double* out, void* partial, uint64_t partial_stride, uint64_t n,
                                    uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring,
-                                   size_t elem, hipStream_t) {
+                                   size_t elem, hipStream_t s) {
+    if (deferring()) {
+        std::vector<const void*> dev{out, partial};
+        for (uint32_t c = 0; c < n_components && c < kRingBinMaxComponents; c++) dev.push_back(a.c[c].ring);
+        return defer(s, "history_envelope", std::move(dev), [=] {
+            return launch_history_envelope(a, n_components, out, partial, partial_stride, n, period, first_tick, sample0, n_samples, every, ring, elem, s);
+        });
+    }
     if (!envelope_launch_ok(n_components, kRingBinMaxComponents, n_samples, period)) return launch(false);
     EnvelopePartial* part = static_cast<EnvelopePartial*>(partial);
     if (!need(live(part, n_samples * partial_stride * sizeof(EnvelopePartial)), "envelope partial records")) return launch(false);
@@ -356,7 +627,14 @@ static bool covariance_walk(const CovarianceArgs& a, double* out, double* part, 
     return true;
 }
 hipError_t launch_history_covariance(const CovarianceArgs& a, uint32_t k, double* out, void* partial, uint64_t partial_stride, uint64_t n, uint32_t period,
-                                     uint64_t first_tick, uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t) {
+                                     uint64_t first_tick, uint64_t sample0, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
+    if (deferring()) {
+        std::vector<const void*> dev{out, partial};
+        for (uint32_t c = 0; c < k && c < kCovarianceArgChannels; c++) dev.push_back(a.c[c].ring);
+        return defer(s, "history_covariance", std::move(dev), [=] {
+            return launch_history_covariance(a, k, out, partial, partial_stride, n, period, first_tick, sample0, n_samples, every, ring, elem, s);
+        });
+    }
     if (!covariance_launch_ok(k, n_samples, period)) return launch(false);
     double* part = static_cast<double*>(partial);
     if (!need(live(part, n_samples * partial_stride * sizeof(double)), "covariance partial records")) return launch(false);
@@ -410,6 +688,13 @@ static void quantiles_of_tick(const char* src, uint64_t n, uint32_t w, uint32_t 
 hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components, const QuantileRanks& ranks, double* out, void* hist, void* state,
                                     uint64_t slot_stride, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t sample0, uint64_t n_samples,
                                     uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
+    if (deferring()) {
+        std::vector<const void*> dev{out, hist, state};
+        for (uint32_t c = 0; c < n_components && c < kRingBinMaxComponents; c++) dev.push_back(a.c[c].ring);
+        return defer(s, "history_quantiles", std::move(dev), [=] {
+            return launch_history_quantiles(a, n_components, ranks, out, hist, state, slot_stride, n, period, first_tick, sample0, n_samples, every, ring, elem, s);
+        });
+    }
     if (!quantile_launch_ok(n_components, kRingBinMaxComponents, ranks, n, n_samples, period)) return launch(false);
     if (n_samples == 0 || n == 0) return launch(true);
     // the clears the real launcher enqueues between the passes: the first of them stands for all, fallible like them
@@ -452,7 +737,14 @@ static void extremes_of_component(const RingBinDesc& d, double* out, uint64_t* s
 }
 hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, double* out, void* scratch, uint64_t scratch_stride, uint32_t segments,
                                    bool merge_into, uint64_t n, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem,
-                                   hipStream_t) {
+                                   hipStream_t s) {
+    if (deferring()) {
+        std::vector<const void*> dev{out, scratch};
+        for (uint32_t c = 0; c < n_components && c < kRingBinMaxComponents; c++) dev.push_back(a.c[c].ring);
+        return defer(s, "history_extremes", std::move(dev), [=] {
+            return launch_history_extremes(a, n_components, out, scratch, scratch_stride, segments, merge_into, n, first_tick, n_samples, every, ring, elem, s);
+        });
+    }
     uint32_t widths[kRingBinMaxComponents] = {};
     for (uint32_t k = 0; k < n_components && k < kRingBinMaxComponents; k++) widths[k] = a.c[k].w;
     if (!extremes_launch_ok(n_components, kRingBinMaxComponents, widths, n, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
@@ -498,7 +790,14 @@ static void events_of_trigger(const EventsTrigger& t, uint32_t trig, uint32_t n_
     }
 }
 hipError_t launch_history_events(const EventsArgs& a, uint32_t n_triggers, void* rec, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n,
-                                 uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t) {
+                                 uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
+    if (deferring()) {
+        std::vector<const void*> dev{rec, out, scratch};
+        for (uint32_t c = 0; c < n_triggers && c < kEventsMaxTriggers; c++) dev.push_back(a.t[c].ring);
+        return defer(s, "history_events", std::move(dev), [=] {
+            return launch_history_events(a, n_triggers, rec, out, scratch, segments, merge_into, n, period, first_tick, n_samples, every, ring, elem, s);
+        });
+    }
     if (!events_launch_ok(a, n_triggers, n, period, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
     if (n == 0) return launch(true);
     const uint64_t units = n / period * n_triggers;
@@ -514,7 +813,14 @@ hipError_t launch_history_events(const EventsArgs& a, uint32_t n_triggers, void*
     return launch(true);
 }
 hipError_t launch_events_capture(const EventsArgs& a, uint32_t n_triggers, const RingBinArgs& c, uint32_t n_captures, const void* rec, double* out, bool merge_into,
-                                 uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t) {
+                                 uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
+    if (deferring()) {
+        std::vector<const void*> dev{rec, out};
+        for (uint32_t k = 0; k < n_captures && k < kRingBinMaxComponents; k++) dev.push_back(c.c[k].ring);
+        return defer(s, "events_capture", std::move(dev), [=] {
+            return launch_events_capture(a, n_triggers, c, n_captures, rec, out, merge_into, n, period, first_tick, n_samples, every, ring, elem, s);
+        });
+    }
     uint32_t widths[kRingBinMaxComponents] = {};
     for (uint32_t k = 0; k < n_captures && k < kRingBinMaxComponents; k++) widths[k] = c.c[k].w;
     if (!events_capture_ok(a, n_triggers, n_captures, kRingBinMaxComponents, widths, n, period, first_tick, n_samples, every) || ring == 0) return launch(false);
@@ -541,7 +847,8 @@ hipError_t launch_events_capture(const EventsArgs& a, uint32_t n_triggers, const
     }
     return launch(true);
 }
-hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags, unsigned long long* count, hipStream_t) {
+hipError_t launch_nonfinite(const void* pos, const void* vel, uint32_t n, size_t elem, uint8_t* flags, unsigned long long* count, hipStream_t s) {
+    if (deferring()) return defer(s, "count_nonfinite", {pos, vel, flags, count}, [=] { return launch_nonfinite(pos, vel, n, elem, flags, count, s); });
     return launch(need(live(pos, n * 7 * elem) && live(vel, n * 6 * elem) && live(count, 8) && (!flags || live(flags, n)), "count_nonfinite buffers"));
 }
 

@@ -201,5 +201,6 @@ int main() {
     two_readers_one_lane();
     long_range();
     failure_injection("quantile_host_test", kSwept, {true, false, true});
+    failure_injection("quantile_host_test", kSwept, {true, false, true}, hip_fake::kCopyFirst);
     return verdict("quantile_host_test");
 }

@@ -29,6 +29,13 @@ size_t live_allocations();
 size_t live_streams();
 size_t live_events();
 size_t live_page_locks();
+bool lock_intersects(const void* p, size_t bytes);   // whether any page lock intersects [p, p + bytes)
+// The ordered mode (hip_fake.cpp): kAtOnce is the default, everything completes at once; under the others every stream is a queue
+// that runs at forcing points only, in the order the schedule chooses where the host layer's waits leave it free.
+enum { kAtOnce = 0, kMinimal = 1, kComputeFirst = 2, kCopyFirst = 3 };
+void set_schedule(int schedule);
+const char* schedule_name(int schedule);
+size_t queued();                                      // operations enqueued and not yet run
 }  // namespace hip_fake
 
 namespace {
@@ -227,8 +234,11 @@ struct SweptRead {
 };
 
 // Each fallible runtime call of a blocking and of an asynchronous read is failed once: the status is returned with a message,
-// the call succeeds when repeated, its values are the fault-free run's, and nothing outlives the handle.
-void failure_injection(const char* program, const SweptRead& swept, RecordOptions o) {
+// the call succeeds when repeated, its values are the fault-free run's, and nothing outlives the handle.  Under a lazy `schedule`
+// a fault in a deferred operation is reported by the forcing point that reaches it, which may be a later step than the call
+// that enqueued it: still exactly one step reports it.
+void failure_injection(const char* program, const SweptRead& swept, RecordOptions o, int schedule = hip_fake::kAtOnce) {
+    hip_fake::set_schedule(schedule);
     const uint64_t comp[2] = {sixdof_component_id("world_pos"), sixdof_component_id("force")};
     std::vector<double> want[2];
     long n_calls = 0;
@@ -272,7 +282,9 @@ void failure_injection(const char* program, const SweptRead& swept, RecordOption
         }
         if (hip_fake::live_allocations() || hip_fake::live_streams() || hip_fake::live_events() || hip_fake::live_page_locks()) complain(run + ": something outlives sixdof_destroy");
     }
-    std::printf("%s: %ld fallible calls of a blocking and an asynchronous %s read, each failed once\n", program, n_calls, swept.name);
+    hip_fake::set_schedule(hip_fake::kAtOnce);
+    if (schedule == hip_fake::kAtOnce) std::printf("%s: %ld fallible calls of a blocking and an asynchronous %s read, each failed once\n", program, n_calls, swept.name);
+    else std::printf("%s: under the %s schedule: %ld fallible calls of the same %s reads, each failed once\n", program, hip_fake::schedule_name(schedule), n_calls, swept.name);
 }
 
 // The end of a program's main: the fake runtime's own findings, the verdict line, the exit status.

@@ -189,7 +189,7 @@ struct CopyLane {
     Stream stream;
     Event ev_snap, ev_copied;
     bool pending = false;
-    uint64_t stream_lo = 0, stream_hi = 0;   // ticks of the history run whose copy may still be in flight
+    uint64_t stream_lo = 1, stream_hi = 0;   // ticks of the history runs whose copies may still be in flight (hi < lo: none)
     std::vector<PinnedRange> pinned_user;    // caller's buffers page-locked by sixdof_history_stream / sixdof_watch_read, until sixdof_sync
     // Before `compute` overwrites a buffer the copies of an earlier read take their data from (snapshots, a staging buffer):
     // those copies must have drained it.  A device-side wait; the host goes on.
@@ -203,7 +203,8 @@ struct CopyLane {
     }
     // One D2H on the copy stream; [dst, dst + pin_bytes) is page-locked first (0: the caller's business).
     hipError_t copy(void* dst, const void* src, size_t bytes, size_t pin_bytes) {
-        if (pin_bytes) pin(dst, pin_bytes);
+        if (pin_bytes)
+            if (hipError_t e = pin(dst, pin_bytes); e != hipSuccess) return e;
         return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream.get());
     }
     // ev_copied is re-recorded behind whatever the copy stream already carried: one sixdof_download_wait covers every read
@@ -224,12 +225,29 @@ struct CopyLane {
         stream = std::move(s), ev_snap = std::move(a), ev_copied = std::move(b);
         return hipSuccess;
     }
-    // page-lock once; if the range cannot be locked the copy still works, staged
-    void pin(void* p, size_t bytes) {
-        for (const PinnedRange& r : pinned_user)
-            if (r.get() == p) return;
+    // Before [p, p + bytes) becomes the host side of a copy: a lock of ours either covers all of it (*covered) or does not touch
+    // it.  A lock that covers only a part — an earlier, shorter read into the same buffer — is dropped, once the copies that may
+    // still run under it have landed: what the runtime makes of a partly locked range is nowhere specified.
+    hipError_t settle(const void* p, size_t bytes, bool* covered = nullptr) {
+        bool partly = false, whole = false;
+        for (const PinnedRange& r : pinned_user) {
+            whole = whole || r.contains(p, bytes);   // locks are disjoint: then no other touches it
+            partly = partly || r.intersects(p, bytes);
+        }
+        if (covered) *covered = whole;
+        if (whole || !partly) return hipSuccess;
+        if (stream)
+            if (hipError_t e = hipStreamSynchronize(stream.get()); e != hipSuccess) return e;
+        pinned_user.erase(std::remove_if(pinned_user.begin(), pinned_user.end(), [&](const PinnedRange& r) { return r.intersects(p, bytes); }), pinned_user.end());
+        return hipSuccess;
+    }
+    // page-lock once, the whole range; if it cannot be locked the copy still works, staged
+    hipError_t pin(void* p, size_t bytes) {
+        bool covered = false;
+        if (hipError_t e = settle(p, bytes, &covered); e != hipSuccess || covered) return e;
         PinnedRange r;
         if (r.lock(p, bytes)) pinned_user.push_back(std::move(r));
+        return hipSuccess;
     }
 };
 
@@ -761,6 +779,7 @@ int sixdof_download_wait(sixdof_handle* h) try {
     HIP_TRY(h, hipSetDevice(h->device));
     const double t0 = now_ms();
     HIP_TRY(h, hipEventSynchronize(h->copy.ev_copied.get()));
+    h->copy.stream_lo = 1, h->copy.stream_hi = 0;   // every copy enqueued so far has landed: none reads the ring any more
     h->last.d2h_download_ms = now_ms() - t0;     // the part of the copy the host actually waited for
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
@@ -1144,7 +1163,10 @@ int sixdof_count_nonfinite(sixdof_handle* h, uint64_t* count, uint8_t* row_flags
     if (e == hipSuccess) e = hipMemcpyAsync(&host_count, d_count.get(), sizeof(host_count), hipMemcpyDeviceToHost, h->stream.get());
     if (e == hipSuccess && d_flags) e = hipMemcpyAsync(row_flags, d_flags.get(), n, hipMemcpyDeviceToHost, h->stream.get());
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream.get());
-    if (e != hipSuccess) return h->hip_fail(e, "count_nonfinite");
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream.get());   // what was enqueued names host_count and the two buffers: it must not outlive them
+        return h->hip_fail(e, "count_nonfinite");
+    }
     *count = host_count;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
@@ -1245,7 +1267,10 @@ int sixdof_set_fold_edges(sixdof_handle* h, uint32_t fold_index, const uint64_t*
     hipError_t e = hipMemcpyAsync(fresh.get(), blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream.get());
     // drains the batches that still read the old table, and the copy itself (its source is a local)
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream.get());
-    if (e != hipSuccess) return h->hip_fail(e, "set_fold_edges: upload");
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream.get());   // a copy that was enqueued names `blob` and `fresh`: it must not outlive them
+        return h->hip_fail(e, "set_fold_edges: upload");
+    }
     f.d_blob = std::move(fresh);
     const uint32_t* d_new = f.d_blob.get<uint32_t>();
     f.table.src_rows = d_new;
@@ -1293,6 +1318,11 @@ int sixdof_set_history(sixdof_handle* h, uint32_t ring_ticks) try {
     if (!h->bound) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, "set_history: bind Body columns first");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
+    // the copy stream may still read the ring (sixdof_history_stream) or a staging buffer that lives with it (the reductions, the scans)
+    if (h->copy.pending) {
+        HIP_TRY(h, hipStreamSynchronize(h->copy.stream.get()));
+        h->copy.stream_lo = 1, h->copy.stream_hi = 0;
+    }
     h->hist.reset();   // free first (rings can be gigabytes): from here to the end of a successful call there is no ring
     h->replay.drop();
     if (ring_ticks == 0) return SIXDOF_OK;
@@ -1346,7 +1376,10 @@ int sixdof_history_read(sixdof_handle* h, uint64_t component_id, uint64_t tick, 
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t block = static_cast<size_t>(h->desc.n_entities) * w * h->elem_size();
     const size_t slot = static_cast<size_t>(history_slot(tick, hs.ring));
-    if (block) HIP_TRY(h, hipMemcpyAsync(host_dst, static_cast<const char*>(ring_base) + slot * block, block, hipMemcpyDeviceToHost, h->stream.get()));
+    if (block) {
+        HIP_TRY(h, h->copy.settle(host_dst, block));   // a lock an asynchronous read left over a part of the buffer
+        HIP_TRY(h, hipMemcpyAsync(host_dst, static_cast<const char*>(ring_base) + slot * block, block, hipMemcpyDeviceToHost, h->stream.get()));
+    }
     HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
@@ -1375,9 +1408,11 @@ int sixdof_history_stream(sixdof_handle* h, uint64_t first_tick, uint64_t n_tick
         if (head < n_ticks) HIP_TRY(h, lane.copy(dst + head * block, ring, (n_ticks - head) * block, 0));
     }
     HIP_TRY(h, lane.end());
-    // the one reader whose copies read the RING from the copy stream: sixdof_step holds back a batch that would overwrite these ticks
-    lane.stream_lo = first_tick;
-    lane.stream_hi = first_tick + n_ticks - 1;
+    // the one reader whose copies read the RING from the copy stream: sixdof_step holds back a batch that would overwrite these ticks,
+    // and those of every earlier run that nothing has waited for yet (the hull of them all: a step held back needlessly is only late)
+    const bool earlier = lane.stream_hi >= lane.stream_lo;
+    lane.stream_lo = earlier ? std::min(lane.stream_lo, first_tick) : first_tick;
+    lane.stream_hi = earlier ? std::max(lane.stream_hi, first_tick + n_ticks - 1) : first_tick + n_ticks - 1;
     return SIXDOF_OK;
 } SIXDOF_ABI_CATCH(err_of(h))
 
@@ -1462,7 +1497,10 @@ struct StagedRead {
         const char* staged = stage->get<char>();
         if (!async) {
             for (const Part& p : parts)
-                if (p.bytes) HIP_TRY(h, hipMemcpyAsync(p.host, staged + p.offset, p.bytes, hipMemcpyDeviceToHost, h->stream.get()));
+                if (p.bytes) {
+                    HIP_TRY(h, lane.settle(p.host, p.bytes));   // a lock an asynchronous read left over a part of the buffer
+                    HIP_TRY(h, hipMemcpyAsync(p.host, staged + p.offset, p.bytes, hipMemcpyDeviceToHost, h->stream.get()));
+                }
             HIP_TRY(h, hipStreamSynchronize(h->stream.get()));
             return SIXDOF_OK;
         }

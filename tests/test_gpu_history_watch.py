@@ -309,6 +309,24 @@ def test_async_watch_read_alongside_a_history_stream_copy():
     hip.close()
 
 
+def test_a_longer_asynchronous_read_into_the_same_buffers_with_no_sync_between():
+    """Ticks 9 .. 10 streamed into the buffers, then — nothing waited for — ticks 5 .. 12 into the same buffers, then sync: the
+    second read's blocks, complete.  The page lock the first read took covers a quarter of what the second copies."""
+    n = 300
+    hip, _ = _exec(n, 4)
+    hip.enable_history(16)
+    hip.run(16)
+    want = {c: hip.history(c, 5, 12) for c in FIELDS}
+    blocks = {c: np.zeros((8, n, 7 if c == "world_pos" else 6)) for c in FIELDS}
+    ptrs = (C.c_void_p * 4)(*[blocks[c].ctypes.data for c in FIELDS])
+    assert hip._lib.sixdof_history_stream(hip._h, 9, 2, ptrs) == L.OK
+    assert hip._lib.sixdof_history_stream(hip._h, 5, 8, ptrs) == L.OK
+    hip.sync()
+    for c in FIELDS:
+        assert np.array_equal(blocks[c], want[c]), c
+    hip.close()
+
+
 def test_front_end_series_equal_the_history_rows():
     """The ball world with history=True, three ticks per telemetry commit: Exec.history_series at the commit ticks equals the rows
     of exec.history() from the second on — the first is the spawned state, tick 0, which is never in the ring."""
