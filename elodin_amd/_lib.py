@@ -36,6 +36,11 @@ EVENT_LEVEL, EVENT_CROSSING = 0, 1                    # sixdof_event_trigger.mod
 EVENTS_ASYNC, EVENTS_CONTINUE, EVENTS_HOLD = 1, 2, 4  # sixdof_history_events flags
 EVENTS_PLANES = 4         # tick, value, tick_before, value_before (SIXDOF_EVENTS_PLANES)
 EVENTS_MAX_TRIGGERS = 8   # triggers one call walks (SIXDOF_EVENTS_MAX_TRIGGERS)
+NORM_MINUS = 1            # sixdof_norm_probe.flags: the probe is |A - B|
+NORM_MAX_COUNT = 4        # elements of one probe (SIXDOF_NORM_MAX_COUNT: a quaternion)
+NORMS_ASYNC, NORMS_CONTINUE, NORMS_HOLD = 1, 2, 4     # sixdof_history_norms flags
+NORMS_PLANES = 6          # count, min_sq, tick_min, max_sq, tick_max, first_nonfinite (SIXDOF_NORMS_PLANES)
+NORMS_MAX_PROBES = 8      # probes one call walks (SIXDOF_NORMS_MAX_PROBES)
 COVARIANCE_ASYNC = 1      # sixdof_history_covariance flags
 COVARIANCE_MAX_CHANNELS = 6   # channels one call reduces jointly (SIXDOF_COVARIANCE_MAX_CHANNELS)
 COVARIANCE_MAX_PERIOD = 256   # groups one call keeps apart (csrc/covariance_plan.hpp: kCovarianceMaxPeriod)
@@ -82,6 +87,11 @@ class Timings(C.Structure):
 class EventTrigger(C.Structure):   # sixdof_event_trigger, 32 bytes
     _fields_ = [("component_id", C.c_uint64), ("element", C.c_uint32), ("group", C.c_uint32), ("op", C.c_uint32), ("mode", C.c_uint32),
                 ("level", C.c_double)]
+
+
+class NormProbe(C.Structure):   # sixdof_norm_probe, 40 bytes
+    _fields_ = [("component_id", C.c_uint64), ("minus_component_id", C.c_uint64), ("element", C.c_uint32), ("minus_element", C.c_uint32),
+                ("group", C.c_uint32), ("minus_group", C.c_uint32), ("count", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class CovChannel(C.Structure):   # sixdof_cov_channel, 16 bytes
@@ -170,6 +180,7 @@ SYMBOLS = {
                                           C.c_uint32]),
     "sixdof_history_events": (C.c_int, [_H, C.POINTER(EventTrigger), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64,
                                         C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]),
+    "sixdof_history_norms": (C.c_int, [_H, C.POINTER(NormProbe), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32]),
     "sixdof_history_covariance": (C.c_int, [_H, C.POINTER(CovChannel), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
                                             C.c_uint32]),
     "sixdof_set_model_apollo": (C.c_int, [_H, C.c_void_p]),

@@ -914,6 +914,24 @@ class Exec:
         out["t_cross"] = self._crossing_time(np.array([float(e.level) for e in evs]), out)
         return out
 
+    def history_norms(self, norms, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> Dict[str, Any]:
+        """Per-run extremes of a vector's length or of a separation: {"count", "argmin", "argmax", "first_nonfinite": int64 [P,
+        runs]; "min_sq", "max_sq", "min", "max", "t_min", "t_max", "t_first_nonfinite": f64 [P, runs]} for the P probes
+        (elodin_amd.Norm) over world ticks first_tick, first_tick + every, ... <= last_tick, reduced on the device out of the ring
+        (enable_history) — apogee and perigee (|r|), peak speed (|v|), the closest approach of two rows of a run and when.  A run
+        is `period` consecutive executor rows.  Tick fields are world ticks, the EARLIEST sampled tick that holds the extreme; 0
+        means none, and the matching t_* (seconds) is NaN.  min and max are the square roots of min_sq and max_sq."""
+        probes = [norms] if not isinstance(norms, (list, tuple)) else list(norms)
+        for comp in [c for p in probes for c in (p.component, p.minus) if c is not None]:
+            self._refuse_unrecorded("history_norms", comp, comp)
+        (first, last, step), _ = self._sampled_ticks("history_norms", first_tick, last_tick, every)
+        s = getattr(self, "_substeps", 1)
+        out: Dict[str, Any] = dict(self._hip.history_norms(probes, first, last, step, period))
+        for tick_field, seconds in (("argmin", "t_min"), ("argmax", "t_max"), ("first_nonfinite", "t_first_nonfinite")):
+            out[tick_field] = out[tick_field] // s          # exact: every sample is a multiple of the sub-step count
+            out[seconds] = np.where(out[tick_field] == 0, np.nan, out[tick_field].astype(np.float64) * self._dt)
+        return out
+
     @staticmethod
     def _crossing_time(levels, ev) -> np.ndarray:
         """[T, runs] seconds: where the line through (t_before, value_before) and (t, value) meets the event's level; t where

@@ -42,6 +42,7 @@
 #include "covariance_plan.hpp"
 #include "envelope_plan.hpp"
 #include "events_plan.hpp"
+#include "norms_plan.hpp"
 #include "extremes_plan.hpp"
 #include "history_plan.hpp"
 #include "kernels.hpp"
@@ -844,6 +845,57 @@ hipError_t launch_events_capture(const EventsArgs& a, uint32_t n_triggers, const
                     *o = __builtin_nan("");
                 }
             }
+    }
+    return launch(true);
+}
+// the walk and the merge themselves (norms_kernels.hip), serially: norms_plan.hpp's value and walk (norms_walk, the function the
+// kernel calls) and extremes_plan.hpp's rule in the kernels' segmentation — with more than one segment every (segment, probe, run) record goes through the launch's scratch, as on the device
+template <class E>
+static void norms_of_probe(const NormsProbe& p, uint32_t probe, uint32_t n_probes, double* out, uint64_t* scratch, uint32_t segments, bool merge_into, uint64_t n,
+                           uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
+    const uint64_t runs = n / period;
+    for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
+        const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
+        for (uint64_t run = 0; run < runs; run++) {
+            ExtremesRecord r = norms_walk<E>(extremes_empty(), p, run, n, period, lo, hi, first_tick, every, ring);
+            if (segments == 1) {
+                double* o = out + norms_out_index(probe, runs, run);
+                if (merge_into) r = extremes_merge(extremes_absorb<double>(o, runs), r);
+                extremes_emit<double>(r, o, runs);
+            } else {
+                extremes_store(r, scratch + norms_scratch_index(seg, n_probes, probe, runs, run), runs);
+            }
+        }
+    }
+    for (uint64_t run = 0; segments > 1 && run < runs; run++) {            // stage 2
+        double* o = out + norms_out_index(probe, runs, run);
+        ExtremesRecord r = merge_into ? extremes_absorb<double>(o, runs) : extremes_empty();
+        for (uint32_t s = 0; s < segments; s++) r = extremes_merge(r, extremes_load(scratch + norms_scratch_index(s, n_probes, probe, runs, run), runs));
+        extremes_emit<double>(r, o, runs);
+    }
+}
+hipError_t launch_history_norms(const NormsArgs& a, uint32_t n_probes, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n, uint32_t period,
+                                uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
+    if (deferring()) {
+        std::vector<const void*> dev{out, scratch};
+        for (uint32_t c = 0; c < n_probes && c < kNormsMaxProbes; c++) {
+            dev.push_back(a.p[c].ring_a);
+            if (a.p[c].flags & kNormMinus) dev.push_back(a.p[c].ring_b);
+        }
+        return defer(s, "history_norms", std::move(dev), [=] {
+            return launch_history_norms(a, n_probes, out, scratch, segments, merge_into, n, period, first_tick, n_samples, every, ring, elem, s);
+        });
+    }
+    if (!norms_launch_ok(a, n_probes, n, period, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
+    if (n == 0) return launch(true);
+    const uint64_t units = n / period * n_probes;
+    if (segments > 1 && !need(live(scratch, scan_scratch_bytes(segments, units, kNormsFields)), "norms scratch records")) return launch(false);
+    if (!need(live(out, units * kNormsPlanes * sizeof(double)), "norms staging")) return launch(false);
+    for (uint32_t k = 0; k < n_probes; k++) {
+        const NormsProbe& p = a.p[k];
+        if (!need(live(p.ring_a, ring * n * p.w_a * elem) && (!(p.flags & kNormMinus) || live(p.ring_b, ring * n * p.w_b * elem)), "ring of a probe")) return launch(false);
+        if (elem == 8) norms_of_probe<double>(p, k, n_probes, out, static_cast<uint64_t*>(scratch), segments, merge_into, n, period, first_tick, n_samples, every, ring);
+        else norms_of_probe<float>(p, k, n_probes, out, static_cast<uint64_t*>(scratch), segments, merge_into, n, period, first_tick, n_samples, every, ring);
     }
     return launch(true);
 }

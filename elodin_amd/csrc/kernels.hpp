@@ -221,6 +221,15 @@ hipError_t launch_events_capture(const EventsArgs& a, uint32_t n_triggers, const
                                  bool merge_into, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring,
                                  size_t elem, hipStream_t s);
 
+// ---- ring norms: per probe and run, the extremes of a squared vector length or separation over the sampled ticks (norms_kernels.hip) ---
+struct NormsArgs;   // norms_plan.hpp: the probes (ring bases, widths, elements, groups, count, flags) of one launch, at most 8
+// All n_samples samples of the range first_tick, first_tick + every, ... in `segments` time segments (norms_plan.hpp).  `out`: the
+// six planes, [n_probes][6][runs] doubles with runs = n / period, read first when merge_into (they then hold the samples before
+// this range, and the result covers both); with more than one segment `scratch` holds segments * n_probes * 6 * runs 64-bit words.
+// The caller has validated the range (sampled_range_ok, scan_ticks_ok) and the probes (norms_launch_ok).
+hipError_t launch_history_norms(const NormsArgs& a, uint32_t n_probes, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n,
+                                uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
+
 // ---- ring covariances: count, mean vector and co-moment matrix of k channels across the rows of every sampled tick (covariance_kernels.hip) ---
 constexpr uint32_t kCovarianceArgChannels = 6;   // covariance_plan.hpp: kCovarianceMaxChannels
 struct CovarianceChannel {

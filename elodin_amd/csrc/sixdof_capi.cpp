@@ -33,6 +33,7 @@
 #include "covariance_plan.hpp"
 #include "envelope_plan.hpp"
 #include "events_plan.hpp"
+#include "norms_plan.hpp"
 #include "extremes_plan.hpp"
 #include "quantile_plan.hpp"
 #include "history_plan.hpp"
@@ -163,7 +164,7 @@ struct History {
     DeviceBuffer quant_stage, quant_scratch;
     // sixdof_history_covariance: its staging and the stage-1 partial records of one launch; the same rules
     DeviceBuffer cov_stage, cov_partial;
-    // A scan over time (time_scan_read: sixdof_history_extremes, sixdof_history_events): its staging, which is also the accumulator
+    // A scan over time (time_scan_read: sixdof_history_extremes, sixdof_history_events, sixdof_history_norms): its staging, which is also the accumulator
     // a *_CONTINUE call merges into, the segment records of one launch and — the events only — the records its rule continues
     // from; the same rules.  `acc` says what the accumulator holds, if anything.
     struct ScanState {
@@ -177,7 +178,7 @@ struct History {
     struct TimeScan {
         DeviceBuffer stage, scratch, rec;
         ScanState acc;
-    } extremes, events;
+    } extremes, events, norms;
     void reset() { *this = History{}; }
 };
 
@@ -514,7 +515,7 @@ void sixdof_destroy(sixdof_handle* h) try {
 int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_cols) try {
     if (!h || (!cols && n_cols)) return SIXDOF_ERR_INVALID_ARGUMENT;
     h->bound = h->resident = false;   // until the end of this call: a failed bind leaves the handle unbound
-    h->hist.extremes.acc.valid = h->hist.events.acc.valid = false;   // the rows a scan's accumulator covers may be other rows from here on
+    h->hist.extremes.acc.valid = h->hist.events.acc.valid = h->hist.norms.acc.valid = false;   // the rows a scan's accumulator covers may be other rows from here on
     HIP_TRY(h, hipSetDevice(h->device));
     h->replay.drop();
     if (h->d_watch_rows) {      // a watch holds rows of the join this call replaces
@@ -1764,7 +1765,7 @@ int sixdof_history_covariance(sixdof_handle* h, const sixdof_cov_channel* channe
 
 }  // extern "C"
 
-// A scan of the ring over time: sixdof_history_extremes and sixdof_history_events.  Ordering, ring reads and the copy lane exactly
+// A scan of the ring over time: sixdof_history_extremes, sixdof_history_events and sixdof_history_norms.  Ordering, ring reads and the copy lane exactly
 // as for sixdof_watch_read above; not through ring_bin_read, whose output and chunk rule are per sample: here ALL samples of the
 // range go into one launch, cut into time segments (time_scan.hpp), and the output is per row or run.  The staging buffer is the
 // accumulator: a call with `continues` merges into what the previous call left there, a call with `holds` delivers nothing.
@@ -1970,6 +1971,76 @@ int sixdof_history_events(sixdof_handle* h, const sixdof_event_trigger* triggers
                 if (e != hipSuccess) return h->hip_fail(e, "history_events capture");
             }
             return SIXDOF_OK;
+        });
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// The extremes of a squared vector length or separation per probe and run.  One walk (and merge) launch covers all probes, a unit
+// is one (probe, run); the accumulator is the staging buffer, as for the extremes.
+int sixdof_history_norms(sixdof_handle* h, const sixdof_norm_probe* probes, size_t n_probes, uint32_t period, uint64_t first_tick, uint64_t n_samples,
+                         uint64_t every, double* host_dst, uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    History& hs = h->hist;
+    History::TimeScan& sc = hs.norms;
+    const TimeScanSpec spec{"history_norms", SIXDOF_NORMS_ASYNC, SIXDOF_NORMS_CONTINUE, SIXDOF_NORMS_HOLD, "SIXDOF_NORMS_CONTINUE",
+                            "probes, period, rows and rings", "SIXDOF_NORMS_SEGMENTS", norms_segments, kNormsFields, &sc};
+    const std::string who = spec.who;
+    const bool hold = (flags & SIXDOF_NORMS_HOLD) != 0;
+    const uint64_t n = h->desc.n_entities;
+    const uint32_t np = static_cast<uint32_t>(n_probes);
+    NormsArgs a{};
+    return time_scan_read(
+        h, spec, first_tick, n_samples, every, flags,
+        [&](bool&) -> int {
+            if (n_probes == 0 || n_probes > SIXDOF_NORMS_MAX_PROBES)
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(n_probes) + " probes, 1 to " + std::to_string(SIXDOF_NORMS_MAX_PROBES) + " can be asked for");
+            if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
+            if (n % period != 0)
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+            if (!probes || (!hold && !host_dst)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
+            for (size_t k = 0; k < n_probes; k++) {
+                const sixdof_norm_probe& p = probes[k];
+                const std::string which = who + ": probe " + std::to_string(k);
+                if (p.flags & ~SIXDOF_NORM_MINUS) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown flags " + std::to_string(p.flags));
+                if (p.count == 0 || p.count > SIXDOF_NORM_MAX_COUNT)
+                    return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": count " + std::to_string(p.count) + ", 1 to " + std::to_string(SIXDOF_NORM_MAX_COUNT) + " elements can be asked for");
+                const bool minus = (p.flags & SIXDOF_NORM_MINUS) != 0;
+                NormsProbe& d = a.p[k];
+                d.count = p.count, d.flags = p.flags;
+                for (int side = 0; side < (minus ? 2 : 1); side++) {
+                    const char* name = side ? " (minus)" : "";
+                    const uint32_t element = side ? p.minus_element : p.element, group = side ? p.minus_group : p.group;
+                    if (group >= period)
+                        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + name + ": group " + std::to_string(group) + " is not below period " + std::to_string(period));
+                    const void* ring = nullptr;
+                    size_t w = 0;
+                    if (!watch_lookup(h, side ? p.minus_component_id : p.component_id, &ring, &w) || !ring)
+                        return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, which + name + ": " + kOnlyRecorded);
+                    if (uint64_t(element) + p.count > w)
+                        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + name + ": elements " + std::to_string(element) + " .. " + std::to_string(uint64_t(element) + p.count - 1) +
+                                                                        " are not all below the component's width " + std::to_string(w));
+                    if (side) d.ring_b = ring, d.w_b = static_cast<uint32_t>(w), d.element_b = element, d.group_b = group;
+                    else d.ring_a = ring, d.w_a = static_cast<uint32_t>(w), d.element_a = element, d.group_a = group;
+                }
+            }
+            return SIXDOF_OK;
+        },
+        [&](StagedRead& rd, History::ScanState& next, std::vector<uint64_t>& units) -> int {
+            units.push_back(n / period * n_probes);
+            rd.add_block(hold ? nullptr : host_dst, static_cast<size_t>(units[0]) * kNormsPlanes * sizeof(double));
+            next.signature = {n_probes, period};
+            for (uint32_t k = 0; k < np; k++) {
+                const sixdof_norm_probe& p = probes[k];
+                const bool minus = (p.flags & SIXDOF_NORM_MINUS) != 0;
+                next.signature.insert(next.signature.end(), {p.component_id, p.minus_component_id, p.element, p.minus_element, p.group, p.minus_group, p.count, p.flags});
+                next.rings.push_back(a.p[k].ring_a), next.widths.push_back(a.p[k].w_a);
+                if (minus) next.rings.push_back(a.p[k].ring_b), next.widths.push_back(a.p[k].w_b);
+            }
+            return SIXDOF_OK;
+        },
+        [&](const StagedRead&, size_t, uint64_t, uint32_t segments, bool merge_into) -> int {
+            hipError_t e = launch_history_norms(a, np, sc.stage.get<double>(), sc.scratch.get(), segments, merge_into, n, period, first_tick, n_samples, every, hs.ring,
+                                                h->elem_size(), h->stream.get());
+            return e == hipSuccess ? int(SIXDOF_OK) : h->hip_fail(e, "history_norms");
         });
 } SIXDOF_ABI_CATCH(err_of(h))
 

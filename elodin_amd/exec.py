@@ -67,6 +67,21 @@ class Event:
     MODES = {"level": L.EVENT_LEVEL, "crossing": L.EVENT_CROSSING}
 
 
+@dataclass(frozen=True)
+class Norm:
+    """One probe of HipExec.history_norms: the Euclidean norm of elements element .. element + count - 1 of `component` in row
+    `group` of every run — |r|, |v|, |omega|, |q| — or, with `minus` (a component name, which may be the same), of their
+    difference to as many elements of `minus` from minus_element on in row minus_group: a separation, a miss distance, a
+    deviation from a commanded state.  minus_element and minus_group default to element and group."""
+    component: str
+    element: int
+    count: int
+    group: int = 0
+    minus: Optional[str] = None
+    minus_element: Optional[int] = None
+    minus_group: Optional[int] = None
+
+
 def dispersion_ellipse(cov2, prob: float = 0.99):
     """(semi_major, semi_minor, angle) of the ellipse that holds the share `prob` of a bivariate normal population with the
     2 x 2 covariance `cov2` — the landing footprint out of the x / y block of HipExec.history_covariance's "cov".  Closed-form
@@ -884,7 +899,7 @@ class HipExec:
         return wall, self._extremes_dict(names, raw)
 
     def _stream_accumulate(self, n_batches: int, ticks_per_batch: int, every: int, continue_flag: int, hold_flag: int, flags: int, read) -> float:
-        """The loop of stream_extremes / stream_events: every batch is stepped and its samples — ending on the batch's last tick —
+        """The loop of stream_extremes / stream_events / stream_norms: every batch is stepped and its samples — ending on the batch's last tick —
         are merged into an accumulator on the device by `read(first_tick, last, read_flags)`: held unless the batch is the last,
         continuing from the second batch on.  A ring one batch deep is enabled unless there is one at least that large.
         Whatever happens, the caller's flags are restored and the handle is drained.  Returns the wall time in seconds."""
@@ -980,6 +995,83 @@ class HipExec:
                                        lambda first, last, fl: self._events_read(triggers, comp, period, first, n_samples, every, raw if last else None,
                                                                                  ptrs if last else None, fl))
         return wall, self._events_dict(capture, raw, caps)
+
+    # ---- ring norms: per-run extremes of a vector's length or of a separation ---------------------------------------------
+    NORMS_FIELDS = ("count", "min_sq", "argmin", "max_sq", "argmax", "first_nonfinite")      # the six planes, in order
+
+    @staticmethod
+    def _norms_dict(raw) -> dict:
+        """A [P, 6, runs] block -> {"count", "argmin", "argmax", "first_nonfinite": int64 [P, runs]; "min_sq", "max_sq", "min",
+        "max": f64 [P, runs]}.  The integer planes arrive as doubles below 2^53: the conversion is exact.  min and max are the
+        square roots of the _sq fields, taken here on the host."""
+        out = {k: raw[:, i] if k.endswith("_sq") else raw[:, i].astype(np.int64) for i, k in enumerate(HipExec.NORMS_FIELDS)}
+        out["min"], out["max"] = np.sqrt(out["min_sq"]), np.sqrt(out["max_sq"])
+        return out
+
+    @staticmethod
+    def _norm_probes(norms):
+        """The ctypes array of sixdof_norm_probe for a list of Norm, or its ValueError."""
+        norms = [norms] if isinstance(norms, Norm) else list(norms)
+        if not 1 <= len(norms) <= L.NORMS_MAX_PROBES:
+            raise ValueError(f"history_norms: {len(norms)} norms, 1 to {L.NORMS_MAX_PROBES} can be asked for")
+        arr = (L.NormProbe * len(norms))()
+        for p, v in zip(arr, norms):
+            if not 1 <= int(v.count) <= L.NORM_MAX_COUNT:
+                raise ValueError(f"history_norms: {v!r}: count is 1 to {L.NORM_MAX_COUNT}")
+            if v.minus is None and (v.minus_element is not None or v.minus_group is not None):
+                raise ValueError(f"history_norms: {v!r}: minus_element and minus_group need minus, the component they index")
+            if min(int(v.element), int(v.group), int(v.element if v.minus_element is None else v.minus_element),
+                   int(v.group if v.minus_group is None else v.minus_group)) < 0:
+                raise ValueError(f"history_norms: {v!r}: a negative element or group")
+            p.component_id, p.element, p.group, p.count = L.component_id(v.component), int(v.element), int(v.group), int(v.count)
+            if v.minus is not None:
+                p.flags, p.minus_component_id = L.NORM_MINUS, L.component_id(v.minus)
+                p.minus_element = int(v.element if v.minus_element is None else v.minus_element)
+                p.minus_group = int(v.group if v.minus_group is None else v.minus_group)
+        return arr
+
+    def _norms_buffer(self, n_norms: int, period: int) -> np.ndarray:
+        """The [P, 6, runs] block, holding what a range without samples reduces to: count 0, NaN extremes, no ticks."""
+        raw = np.zeros((n_norms, L.NORMS_PLANES, self.n // max(period, 1)), dtype=np.float64)
+        raw[:, 1], raw[:, 3] = np.nan, np.nan
+        return raw
+
+    def _norms_read(self, probes, period: int, first_tick: int, n_samples: int, every: int, raw, flags: int) -> None:
+        rc = self._lib.sixdof_history_norms(self._h, probes, len(probes), period, first_tick, n_samples, every, None if raw is None else raw.ctypes.data, flags)
+        if rc != L.OK:
+            _raise(self._h, rc, "sixdof_history_norms")
+
+    def history_norms(self, norms, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> dict:
+        """{"count", "argmin", "argmax", "first_nonfinite": int64 [P, runs]; "min_sq", "max_sq", "min", "max": f64 [P, runs]}: per
+        Norm and run (period consecutive rows; runs = n // period), over the ticks first_tick, first_tick + every, ... <= last_tick,
+        the smallest and the largest squared norm with the EARLIEST sampled tick that holds each, the count of samples at which
+        the squared norm is finite and the earliest tick at which it is not — reduced on the device out of the ring.  The
+        squared norm is formed in f64, left to right, from the ring's elements widened to double; one that overflows counts as
+        non-finite.  0 in a tick field means none; count == 0 leaves the extremes NaN.  Stateless: no watch is involved."""
+        probes = self._norm_probes(norms)
+        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
+        raw = self._norms_buffer(len(probes), period)
+        self._norms_read(probes, max(period, 0), first_tick, self._sample_count(first_tick, last_tick, every), every, raw, 0)
+        return self._norms_dict(raw)
+
+    def stream_norms(self, norms, n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, flags: int = 0):
+        """history_norms over a run longer than the ring: n_batches batches of ticks_per_batch ticks are stepped, and after every
+        batch its samples — every `every`-th tick, ending on the batch's last — are merged into the accumulator on the device
+        (SIXDOF_NORMS_HOLD, SIXDOF_NORMS_CONTINUE from the second batch on).  Nothing crosses the link until the last batch's call
+        delivers.  The ring is read on the compute stream, so a ring one batch deep is enough (enabled here unless enable_history
+        already made one at least that large).  Returns (wall time in seconds, the dict of history_norms); whatever happens, the
+        caller's flags are restored and the handle is drained."""
+        probes = self._norm_probes(norms)
+        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
+        n_samples = self._stream_shape("stream_norms", ticks_per_batch, every)
+        if n_batches < 1:
+            raise ValueError("stream_norms: at least one batch")
+        if period < 1:
+            raise ValueError("stream_norms: period must be at least 1")
+        raw = self._norms_buffer(len(probes), period)
+        wall = self._stream_accumulate(n_batches, ticks_per_batch, every, L.NORMS_CONTINUE, L.NORMS_HOLD, flags,
+                                       lambda first, last, fl: self._norms_read(probes, period, first, n_samples, every, raw if last else None, fl))
+        return wall, self._norms_dict(raw)
 
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))

@@ -351,6 +351,13 @@ class Campaign:
         out["capture"] = {comp: v.reshape(v.shape[0], self.n_runs, self.entities_per_run, v.shape[-1]) for comp, v in out["capture"].items()}
         return out
 
+    def norms(self, norms, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
+        """Per-run extremes of a vector's length or of a separation, out of the device ring (self.exec.enable_history): the dict of
+        Exec.history_norms with a run = entities_per_run consecutive rows — "count", "argmin", "argmax", "first_nonfinite",
+        "min_sq", "max_sq", "min", "max", "t_min", "t_max", "t_first_nonfinite": [probe, run].  A Norm's `group` (and minus_group) is
+        the entity of the run it reads: apogee, peak speed, the closest approach of two entities of a run and when."""
+        return self.exec.history_norms(norms, first_tick, last_tick, every, period=self.entities_per_run)
+
     def result_table(self, names: Sequence[str]) -> np.ndarray:
         """The runs' `el.monte_carlo.result(...)` records as [n_runs, len(names)] (NaN where a run reported nothing)."""
         out = np.full((self.n_runs, len(names)), np.nan)

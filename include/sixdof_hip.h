@@ -587,6 +587,65 @@ int sixdof_history_events(sixdof_handle* h, const sixdof_event_trigger* triggers
                           size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                           double* event_dst, double* const capture_dst[], uint32_t flags);
 
+/* ---- ring norms: per-run extremes of a vector's length or of a separation -------------------------------------------------
+ * Apogee and perigee are extremes of |r|, peak speed of |v|, peak tumble rate of |omega|, the drift of a quaternion from unit
+ * length of |q|, the miss distance of chaser and target the smallest |r_a - r_b| and when: extremes over time of a scalar derived
+ * from several elements, possibly of two rows of a run.  sixdof_history_extremes looks at one element of one row; this reader
+ * forms the scalar on the device before the same rule sees it.
+ *
+ * A run is `period` consecutive rows (n_entities % period == 0; runs = n_entities / period).  Probe A reads elements element ..
+ * element + count - 1 of component `component_id` in row run * period + group of every run; with SIXDOF_NORM_MINUS, B reads
+ * elements minus_element .. minus_element + count - 1 of `minus_component_id` (which may equal component_id) in row run * period +
+ * minus_group, otherwise the three minus_ fields are not read.  For each probe, run and sampled tick the value is the SQUARED
+ * Euclidean norm s, in f64, in this fixed order: d_e = a_e (or a_e - b_e with SIXDOF_NORM_MINUS), s = d_0 * d_0, then s = s + d_e *
+ * d_e for e = 1 .. count - 1.  Every ring element is widened to double first (exact for an f32 handle), and the code is compiled
+ * without FMA contraction, so the library, its host twin and a plain restatement round alike, bit for bit.  A sample is finite
+ * exactly when s is finite: any non-finite input gives a non-finite s (squares are non-negative, nothing cancels), and an s that
+ * OVERFLOWS from finite inputs counts as non-finite too.  s then goes through the rule of sixdof_history_extremes unchanged.
+ *
+ * Samples are the ticks first_tick, first_tick + every, ... (n_samples of them), all in the ring.  host_dst is
+ * [n_probes][SIXDOF_NORMS_PLANES][runs] doubles, plane-major:
+ *   plane 0  count             samples at which s is finite
+ *   plane 1  min_sq            the smallest finite s
+ *   plane 2  tick_min          the EARLIEST sampled tick that holds it
+ *   plane 3  max_sq            the largest finite s
+ *   plane 4  tick_max          the EARLIEST sampled tick that holds it
+ *   plane 5  first_nonfinite   the earliest sampled tick at which s is not finite; 0: none
+ * count = 0: min_sq and max_sq are NaN, their ticks 0.  Ticks are exact in doubles: a range whose last sampled tick is 2^53 or
+ * more is refused.  The rule is exact and associative in time order and there are no atomics, so every output is bit-identical
+ * however the range is cut into time segments (SIXDOF_NORMS_SEGMENTS in the environment forces a count; 0 or unset: the
+ * library's choice), launches or calls.  The square root is left to the caller.
+ * SIXDOF_NORMS_HOLD: reduce and keep the result in the device accumulator (the call's staging buffer, freed with the ring);
+ * nothing is delivered, host_dst is ignored.  SIXDOF_NORMS_CONTINUE: merge into the accumulator the previous successful call left
+ * instead of starting afresh.  Accepted only if the previous call succeeded with the same probes field for field and the same
+ * period, ring bases, widths and row count are unchanged, no sixdof_set_history or sixdof_bind_columns came since, and first_tick
+ * is above the last tick accumulated; otherwise SIXDOF_ERR_INVALID_ARGUMENT and the accumulator stays as it was.
+ * SIXDOF_NORMS_ASYNC: the rules of SIXDOF_WATCH_ASYNC.  Either way the ring is read on the compute stream: a later sixdof_step
+ * may overwrite the slots at once, and a ring one batch deep is enough.
+ * n_samples = 0 is a no-op that leaves the accumulator alone.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied and the
+ * accumulator as it was: no ring, every = 0, a sampled tick that is not (or no longer) in the ring or is 2^53 or more, unknown
+ * flags, a null probes, a null host_dst without SIXDOF_NORMS_HOLD, n_probes = 0 or above SIXDOF_NORMS_MAX_PROBES, count = 0 or
+ * above SIXDOF_NORM_MAX_COUNT, element + count (with SIXDOF_NORM_MINUS also minus_element + count) above the component's width,
+ * group (minus_group) >= period, unknown probe flags, period = 0 or not dividing n_entities.  A component the ring does not
+ * record: SIXDOF_ERR_COMPONENT_NOT_FOUND.  A call that fails in the runtime leaves the ring as it was and the accumulator
+ * invalid, as for sixdof_history_extremes. */
+typedef struct sixdof_norm_probe {     /* 40 bytes */
+    uint64_t component_id;             /* A: elements element .. element+count-1 of row run*period+group */
+    uint64_t minus_component_id;       /* B, read only with SIXDOF_NORM_MINUS; may equal component_id */
+    uint32_t element, minus_element, group, minus_group;
+    uint32_t count;                    /* 1 .. SIXDOF_NORM_MAX_COUNT (4: a quaternion) */
+    uint32_t flags;                    /* 0 or SIXDOF_NORM_MINUS */
+} sixdof_norm_probe;
+#define SIXDOF_NORM_MINUS 1u
+#define SIXDOF_NORM_MAX_COUNT 4
+#define SIXDOF_NORMS_ASYNC 1u
+#define SIXDOF_NORMS_CONTINUE 2u
+#define SIXDOF_NORMS_HOLD 4u
+#define SIXDOF_NORMS_PLANES 6
+#define SIXDOF_NORMS_MAX_PROBES 8
+int sixdof_history_norms(sixdof_handle* h, const sixdof_norm_probe* probes, size_t n_probes, uint32_t period,
+                         uint64_t first_tick, uint64_t n_samples, uint64_t every, double* host_dst, uint32_t flags);
+
 /* ---- ring covariances: how quantities vary TOGETHER across the rows, over time ---------------------------------------------
  * The landing footprint ellipse, the 6 x 6 position / velocity dispersion, whether touchdown speed goes with lateral miss: joint
  * moments.  The envelope's mean and m2 are the diagonal of this matrix; the off-diagonals cannot be recovered from them.
