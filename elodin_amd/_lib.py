@@ -41,6 +41,9 @@ NORM_MAX_COUNT = 4        # elements of one probe (SIXDOF_NORM_MAX_COUNT: a quat
 NORMS_ASYNC, NORMS_CONTINUE, NORMS_HOLD = 1, 2, 4     # sixdof_history_norms flags
 NORMS_PLANES = 6          # count, min_sq, tick_min, max_sq, tick_max, first_nonfinite (SIXDOF_NORMS_PLANES)
 NORMS_MAX_PROBES = 8      # probes one call walks (SIXDOF_NORMS_MAX_PROBES)
+NORM_EVENTS_ASYNC, NORM_EVENTS_CONTINUE, NORM_EVENTS_HOLD = 1, 2, 4   # sixdof_history_norm_events flags
+NORM_EVENTS_PLANES = 4    # tick, value_sq, tick_before, value_before_sq (SIXDOF_NORM_EVENTS_PLANES)
+NORM_EVENTS_MAX_TRIGGERS = 8   # triggers one call walks (SIXDOF_NORM_EVENTS_MAX_TRIGGERS)
 COVARIANCE_ASYNC = 1      # sixdof_history_covariance flags
 COVARIANCE_MAX_CHANNELS = 6   # channels one call reduces jointly (SIXDOF_COVARIANCE_MAX_CHANNELS)
 COVARIANCE_MAX_PERIOD = 256   # groups one call keeps apart (csrc/covariance_plan.hpp: kCovarianceMaxPeriod)
@@ -92,6 +95,10 @@ class EventTrigger(C.Structure):   # sixdof_event_trigger, 32 bytes
 class NormProbe(C.Structure):   # sixdof_norm_probe, 40 bytes
     _fields_ = [("component_id", C.c_uint64), ("minus_component_id", C.c_uint64), ("element", C.c_uint32), ("minus_element", C.c_uint32),
                 ("group", C.c_uint32), ("minus_group", C.c_uint32), ("count", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class NormTrigger(C.Structure):   # sixdof_norm_trigger, 56 bytes
+    _fields_ = [("probe", NormProbe), ("level_sq", C.c_double), ("op", C.c_uint32), ("mode", C.c_uint32)]
 
 
 class CovChannel(C.Structure):   # sixdof_cov_channel, 16 bytes
@@ -181,6 +188,8 @@ SYMBOLS = {
     "sixdof_history_events": (C.c_int, [_H, C.POINTER(EventTrigger), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64,
                                         C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_history_norms": (C.c_int, [_H, C.POINTER(NormProbe), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "sixdof_history_norm_events": (C.c_int, [_H, C.POINTER(NormTrigger), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64,
+                                             C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_history_covariance": (C.c_int, [_H, C.POINTER(CovChannel), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
                                             C.c_uint32]),
     "sixdof_set_model_apollo": (C.c_int, [_H, C.c_void_p]),

@@ -932,6 +932,29 @@ class Exec:
             out[seconds] = np.where(out[tick_field] == 0, np.nan, out[tick_field].astype(np.float64) * self._dt)
         return out
 
+    def history_norm_events(self, events, capture, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> Dict[str, Any]:
+        """At what tick did a vector's length or a separation first pass a level, and what was the run's state there: {"tick",
+        "tick_before": int64 [T, runs]; "value_sq", "value_before_sq", "value", "value_before", "t", "t_before", "t_cross": f64 [T,
+        runs]; "capture": {component: f64 [T, rows, w]}} for the T events (elodin_amd.NormEvent) over world ticks first_tick,
+        first_tick + every, ... <= last_tick, found on the device out of the ring (enable_history) — touchdown on a sphere (|r| <=
+        R + h), leaving a sphere of influence, a keep-out distance between two rows of a run, a speed limit.  A run is `period`
+        consecutive executor rows.  tick is the first sampled world tick at which the event's norm meets its level (0: never;
+        the values, t and the run's captured rows are then NaN), tick_before the finite sample before it (0: none).  value and
+        value_before are norms (square roots taken on the host), t and t_before seconds.  t_cross is the time at which the
+        straight line from (t_before, value_before) to (t, value) passes the event's level, as for history_events."""
+        evs = [events] if not isinstance(events, (list, tuple)) else list(events)
+        caps = [capture] if isinstance(capture, str) else list(capture)
+        for comp in [c for e in evs for c in (e.norm.component, e.norm.minus) if c is not None] + caps:
+            self._refuse_unrecorded("history_norm_events", comp, comp)
+        (first, last, step), _ = self._sampled_ticks("history_norm_events", first_tick, last_tick, every)
+        s = getattr(self, "_substeps", 1)
+        out: Dict[str, Any] = dict(self._hip.history_norm_events(evs, caps, first, last, step, period))
+        for tick_field, seconds in (("tick", "t"), ("tick_before", "t_before")):
+            out[tick_field] = out[tick_field] // s          # exact: every sample is a multiple of the sub-step count
+            out[seconds] = np.where(out[tick_field] == 0, np.nan, out[tick_field].astype(np.float64) * self._dt)
+        out["t_cross"] = self._crossing_time(np.array([float(e.level) for e in evs]), out)
+        return out
+
     @staticmethod
     def _crossing_time(levels, ev) -> np.ndarray:
         """[T, runs] seconds: where the line through (t_before, value_before) and (t, value) meets the event's level; t where

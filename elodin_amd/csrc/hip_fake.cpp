@@ -43,6 +43,7 @@
 #include "envelope_plan.hpp"
 #include "events_plan.hpp"
 #include "norms_plan.hpp"
+#include "norm_events_plan.hpp"
 #include "extremes_plan.hpp"
 #include "history_plan.hpp"
 #include "kernels.hpp"
@@ -896,6 +897,60 @@ hipError_t launch_history_norms(const NormsArgs& a, uint32_t n_probes, double* o
         if (!need(live(p.ring_a, ring * n * p.w_a * elem) && (!(p.flags & kNormMinus) || live(p.ring_b, ring * n * p.w_b * elem)), "ring of a probe")) return launch(false);
         if (elem == 8) norms_of_probe<double>(p, k, n_probes, out, static_cast<uint64_t*>(scratch), segments, merge_into, n, period, first_tick, n_samples, every, ring);
         else norms_of_probe<float>(p, k, n_probes, out, static_cast<uint64_t*>(scratch), segments, merge_into, n, period, first_tick, n_samples, every, ring);
+    }
+    return launch(true);
+}
+// the walk and the merge themselves (norm_events_kernels.hip), serially: norm_events_plan.hpp's walk (norm_events_walk, the function
+// the kernel calls) and events_plan.hpp's rule in the kernels' segmentation — with more than one segment every (segment, trigger, run) record goes through the launch's scratch, as on the device
+template <class E>
+static void norm_events_of_trigger(const NormEventsTrigger& t, uint32_t trig, uint32_t n_triggers, uint64_t* rec, double* out, uint64_t* scratch, uint32_t segments,
+                                   bool merge_into, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
+    const uint64_t runs = n / period;
+    for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
+        const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
+        for (uint64_t run = 0; run < runs; run++) {
+            uint64_t* mine = rec + norm_events_record_index(trig, runs, run);
+            const EventsRecord r = norm_events_walk<E>(segments == 1 && merge_into ? events_load(mine, runs) : events_empty(), t, run, n, period, lo, hi, first_tick, every, ring);
+            if (segments == 1) {
+                events_store(r, mine, runs);
+                events_emit<double>(r, t.mode, out + norm_events_out_index(trig, runs, run), runs);
+            } else {
+                events_store(r, scratch + norm_events_scratch_index(seg, n_triggers, trig, runs, run), runs);
+            }
+        }
+    }
+    for (uint64_t run = 0; segments > 1 && run < runs; run++) {            // stage 2
+        uint64_t* mine = rec + norm_events_record_index(trig, runs, run);
+        EventsRecord r = merge_into ? events_load(mine, runs) : events_empty();
+        for (uint32_t s = 0; s < segments; s++) r = events_merge(r, events_load(scratch + norm_events_scratch_index(s, n_triggers, trig, runs, run), runs));
+        events_store(r, mine, runs);
+        events_emit<double>(r, t.mode, out + norm_events_out_index(trig, runs, run), runs);
+    }
+}
+hipError_t launch_history_norm_events(const NormEventsArgs& a, uint32_t n_triggers, void* rec, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n,
+                                      uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
+    if (deferring()) {
+        std::vector<const void*> dev{rec, out, scratch};
+        for (uint32_t c = 0; c < n_triggers && c < kNormEventsMaxTriggers; c++) {
+            dev.push_back(a.t[c].probe.ring_a);
+            if (a.t[c].probe.flags & kNormMinus) dev.push_back(a.t[c].probe.ring_b);
+        }
+        return defer(s, "history_norm_events", std::move(dev), [=] {
+            return launch_history_norm_events(a, n_triggers, rec, out, scratch, segments, merge_into, n, period, first_tick, n_samples, every, ring, elem, s);
+        });
+    }
+    if (!norm_events_launch_ok(a, n_triggers, n, period, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
+    if (n == 0) return launch(true);
+    const uint64_t units = n / period * n_triggers;
+    if (segments > 1 && !need(live(scratch, scan_scratch_bytes(segments, units, kNormEventsFields)), "norm events scratch records")) return launch(false);
+    if (!need(live(rec, events_record_bytes(units)) && live(out, units * kNormEventsPlanes * sizeof(double)), "norm events records or staging")) return launch(false);
+    for (uint32_t k = 0; k < n_triggers; k++) {
+        const NormEventsTrigger& t = a.t[k];
+        const NormsProbe& p = t.probe;
+        if (!need(live(p.ring_a, ring * n * p.w_a * elem) && (!(p.flags & kNormMinus) || live(p.ring_b, ring * n * p.w_b * elem)), "ring of a trigger's probe")) return launch(false);
+        uint64_t *r = static_cast<uint64_t*>(rec), *sc = static_cast<uint64_t*>(scratch);
+        if (elem == 8) norm_events_of_trigger<double>(t, k, n_triggers, r, out, sc, segments, merge_into, n, period, first_tick, n_samples, every, ring);
+        else norm_events_of_trigger<float>(t, k, n_triggers, r, out, sc, segments, merge_into, n, period, first_tick, n_samples, every, ring);
     }
     return launch(true);
 }

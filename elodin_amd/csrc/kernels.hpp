@@ -230,6 +230,16 @@ struct NormsArgs;   // norms_plan.hpp: the probes (ring bases, widths, elements,
 hipError_t launch_history_norms(const NormsArgs& a, uint32_t n_probes, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n,
                                 uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
 
+// ---- ring norm events: per trigger and run, the first crossing of a squared vector length or separation and the state there (norm_events_kernels.hip) ---
+struct NormEventsArgs;   // norm_events_plan.hpp: the triggers (a norms probe, level_sq, op, mode) of one launch, at most 8
+// All n_samples samples of the range first_tick, first_tick + every, ... in `segments` time segments (norm_events_plan.hpp).  `rec`,
+// `out` and `scratch` as for launch_history_events — the records have the events' layout, so launch_events_capture follows on the
+// same stream with norm_events_capture_args.  The caller has validated the range (sampled_range_ok, scan_ticks_ok) and the
+// triggers (norm_events_launch_ok).
+hipError_t launch_history_norm_events(const NormEventsArgs& a, uint32_t n_triggers, void* rec, double* out, void* scratch, uint32_t segments, bool merge_into,
+                                      uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem,
+                                      hipStream_t s);
+
 // ---- ring covariances: count, mean vector and co-moment matrix of k channels across the rows of every sampled tick (covariance_kernels.hip) ---
 constexpr uint32_t kCovarianceArgChannels = 6;   // covariance_plan.hpp: kCovarianceMaxChannels
 struct CovarianceChannel {

@@ -79,18 +79,25 @@ SIXDOF_HOST_DEVICE constexpr uint32_t norms_depth(uint32_t count, bool minus) {
     return d > kScanLoads ? kScanLoads : d < 2 ? 2 : d;
 }
 
+// The rule of this reader as norms_walk_as takes it (scan_walk's shape: sample + settled): every sample counts, so no walk ends early.
+struct NormsRule {
+    SIXDOF_HOST_DEVICE void sample(ExtremesRecord& rec, double s, uint64_t tick) const { norms_sample(rec, s, tick); }
+    SIXDOF_HOST_DEVICE bool settled(const ExtremesRecord&) const { return false; }
+};
+
 // The record `r` after samples [lo, hi) of the range, in time order: sample j is the COUNT elements from a + slot(j) * stride_a
 // (minus those from b + slot(j) * stride_b) at tick first_tick + j * every.  scan_walk's shape: the loads of norms_depth samples
-// are issued before the first value is formed, the slot advances by an add and a compare, the record travels by value.  Every
-// sample counts, so no walk ends early.
-template <class E, uint32_t COUNT, bool MINUS>
-SIXDOF_HOST_DEVICE inline ExtremesRecord norms_walk_as(ExtremesRecord r, const E* __restrict__ a, const E* __restrict__ b, uint64_t stride_a,
-                                                       uint64_t stride_b, uint64_t lo, uint64_t hi, uint64_t first_tick, uint64_t every, uint64_t ring) {
+// are issued before the first value is formed, the slot advances by an add and a compare, record and rule travel by value.
+// rule.sample(r, s, tick) applies one squared norm; once rule.settled(r) says that no later sample can change what the reader
+// reports, the walk stops loading (the norms never do; the norm events do: norm_events_plan.hpp).
+template <class E, uint32_t COUNT, bool MINUS, class Record, class Rule>
+SIXDOF_HOST_DEVICE inline Record norms_walk_as(Record r, const Rule rule, const E* __restrict__ a, const E* __restrict__ b, uint64_t stride_a, uint64_t stride_b,
+                                               uint64_t lo, uint64_t hi, uint64_t first_tick, uint64_t every, uint64_t ring) {
     constexpr uint32_t kDepth = norms_depth(COUNT, MINUS);
     const uint64_t step = every % ring;
     uint64_t slot = sample_slot(first_tick, lo, every, ring), tick = first_tick + lo * every;
     uint64_t j = lo;
-    for (; j + kDepth <= hi; j += kDepth) {
+    for (; j + kDepth <= hi && !rule.settled(r); j += kDepth) {
         E xa[kDepth][COUNT], xb[kDepth][COUNT];
 #pragma unroll
         for (uint32_t q = 0; q < kDepth; q++) {
@@ -105,11 +112,11 @@ SIXDOF_HOST_DEVICE inline ExtremesRecord norms_walk_as(ExtremesRecord r, const E
         }
 #pragma unroll
         for (uint32_t q = 0; q < kDepth; q++) {
-            norms_sample(r, norms_value<E, COUNT, MINUS>(xa[q], xb[q]), tick);
+            rule.sample(r, norms_value<E, COUNT, MINUS>(xa[q], xb[q]), tick);
             tick += every;
         }
     }
-    for (; j < hi; j++) {
+    for (; j < hi && !rule.settled(r); j++) {
         E xa[COUNT], xb[COUNT];
         const E* __restrict__ pa = a + slot * stride_a;
         const E* __restrict__ pb = b + slot * stride_b;
@@ -118,32 +125,38 @@ SIXDOF_HOST_DEVICE inline ExtremesRecord norms_walk_as(ExtremesRecord r, const E
             xa[e] = pa[e];
             xb[e] = MINUS ? pb[e] : E(0);
         }
-        norms_sample(r, norms_value<E, COUNT, MINUS>(xa, xb), tick);
+        rule.sample(r, norms_value<E, COUNT, MINUS>(xa, xb), tick);
         slot = next_sample_slot(slot, step, ring);
         tick += every;
     }
     return r;
 }
-// The walk of probe `p` for run `run` of a world of n rows: what the kernel and the host twin both call.  A probe's shape is the
-// same for every thread of a block (blockIdx.z names it), so the switch does not diverge.  norms_launch_ok has been asked.
-template <class E>
-SIXDOF_HOST_DEVICE inline ExtremesRecord norms_walk(ExtremesRecord r, const NormsProbe& p, uint64_t run, uint64_t n, uint32_t period, uint64_t lo, uint64_t hi,
-                                                    uint64_t first_tick, uint64_t every, uint64_t ring) {
+// The walk of probe `p` for run `run` of a world of n rows under `rule`.  A probe's shape is the same for every thread of a block
+// (blockIdx.z names it), so the switch does not diverge.  norms_launch_ok has been asked.
+template <class E, class Record, class Rule>
+SIXDOF_HOST_DEVICE inline Record norms_walk_with(Record r, const Rule rule, const NormsProbe& p, uint64_t run, uint64_t n, uint32_t period, uint64_t lo, uint64_t hi,
+                                                 uint64_t first_tick, uint64_t every, uint64_t ring) {
     const bool minus = (p.flags & kNormMinus) != 0;
     const E* a = static_cast<const E*>(p.ring_a) + (run * period + p.group_a) * p.w_a + p.element_a;
     const E* b = minus ? static_cast<const E*>(p.ring_b) + (run * period + p.group_b) * p.w_b + p.element_b : a;
     const uint64_t sa = n * p.w_a, sb = minus ? n * p.w_b : sa;
     switch (p.count * 2 + (minus ? 1u : 0u)) {
-    case 2: return norms_walk_as<E, 1, false>(r, a, b, sa, sb, lo, hi, first_tick, every, ring);
-    case 3: return norms_walk_as<E, 1, true>(r, a, b, sa, sb, lo, hi, first_tick, every, ring);
-    case 4: return norms_walk_as<E, 2, false>(r, a, b, sa, sb, lo, hi, first_tick, every, ring);
-    case 5: return norms_walk_as<E, 2, true>(r, a, b, sa, sb, lo, hi, first_tick, every, ring);
-    case 6: return norms_walk_as<E, 3, false>(r, a, b, sa, sb, lo, hi, first_tick, every, ring);
-    case 7: return norms_walk_as<E, 3, true>(r, a, b, sa, sb, lo, hi, first_tick, every, ring);
-    case 8: return norms_walk_as<E, 4, false>(r, a, b, sa, sb, lo, hi, first_tick, every, ring);
-    case 9: return norms_walk_as<E, 4, true>(r, a, b, sa, sb, lo, hi, first_tick, every, ring);
+    case 2: return norms_walk_as<E, 1, false>(r, rule, a, b, sa, sb, lo, hi, first_tick, every, ring);
+    case 3: return norms_walk_as<E, 1, true>(r, rule, a, b, sa, sb, lo, hi, first_tick, every, ring);
+    case 4: return norms_walk_as<E, 2, false>(r, rule, a, b, sa, sb, lo, hi, first_tick, every, ring);
+    case 5: return norms_walk_as<E, 2, true>(r, rule, a, b, sa, sb, lo, hi, first_tick, every, ring);
+    case 6: return norms_walk_as<E, 3, false>(r, rule, a, b, sa, sb, lo, hi, first_tick, every, ring);
+    case 7: return norms_walk_as<E, 3, true>(r, rule, a, b, sa, sb, lo, hi, first_tick, every, ring);
+    case 8: return norms_walk_as<E, 4, false>(r, rule, a, b, sa, sb, lo, hi, first_tick, every, ring);
+    case 9: return norms_walk_as<E, 4, true>(r, rule, a, b, sa, sb, lo, hi, first_tick, every, ring);
     default: return r;   // norms_launch_ok refuses such a probe
     }
+}
+// The norms' own walk: what norms_walk_kernel and the host twin both call.
+template <class E>
+SIXDOF_HOST_DEVICE inline ExtremesRecord norms_walk(ExtremesRecord r, const NormsProbe& p, uint64_t run, uint64_t n, uint32_t period, uint64_t lo, uint64_t hi,
+                                                    uint64_t first_tick, uint64_t every, uint64_t ring) {
+    return norms_walk_with<E>(r, NormsRule{}, p, run, n, period, lo, hi, first_tick, every, ring);
 }
 
 // Where the record of (segment, probe, run) sits in scratch: field f at base[f * runs], so that consecutive lanes store

@@ -34,6 +34,7 @@
 #include "envelope_plan.hpp"
 #include "events_plan.hpp"
 #include "norms_plan.hpp"
+#include "norm_events_plan.hpp"
 #include "extremes_plan.hpp"
 #include "quantile_plan.hpp"
 #include "history_plan.hpp"
@@ -164,8 +165,8 @@ struct History {
     DeviceBuffer quant_stage, quant_scratch;
     // sixdof_history_covariance: its staging and the stage-1 partial records of one launch; the same rules
     DeviceBuffer cov_stage, cov_partial;
-    // A scan over time (time_scan_read: sixdof_history_extremes, sixdof_history_events, sixdof_history_norms): its staging, which is also the accumulator
-    // a *_CONTINUE call merges into, the segment records of one launch and — the events only — the records its rule continues
+    // A scan over time (time_scan_read: sixdof_history_extremes, sixdof_history_events, sixdof_history_norms, sixdof_history_norm_events): its staging, which is also the accumulator
+    // a *_CONTINUE call merges into, the segment records of one launch and — the two event readers only — the records its rule continues
     // from; the same rules.  `acc` says what the accumulator holds, if anything.
     struct ScanState {
         bool valid = false;                  // the previous call succeeded and nothing has replaced what it read since
@@ -178,7 +179,7 @@ struct History {
     struct TimeScan {
         DeviceBuffer stage, scratch, rec;
         ScanState acc;
-    } extremes, events, norms;
+    } extremes, events, norms, norm_events;
     void reset() { *this = History{}; }
 };
 
@@ -515,7 +516,7 @@ void sixdof_destroy(sixdof_handle* h) try {
 int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_cols) try {
     if (!h || (!cols && n_cols)) return SIXDOF_ERR_INVALID_ARGUMENT;
     h->bound = h->resident = false;   // until the end of this call: a failed bind leaves the handle unbound
-    h->hist.extremes.acc.valid = h->hist.events.acc.valid = h->hist.norms.acc.valid = false;   // the rows a scan's accumulator covers may be other rows from here on
+    h->hist.extremes.acc.valid = h->hist.events.acc.valid = h->hist.norms.acc.valid = h->hist.norm_events.acc.valid = false;   // the rows a scan's accumulator covers may be other rows from here on
     HIP_TRY(h, hipSetDevice(h->device));
     h->replay.drop();
     if (h->d_watch_rows) {      // a watch holds rows of the join this call replaces
@@ -1765,7 +1766,7 @@ int sixdof_history_covariance(sixdof_handle* h, const sixdof_cov_channel* channe
 
 }  // extern "C"
 
-// A scan of the ring over time: sixdof_history_extremes, sixdof_history_events and sixdof_history_norms.  Ordering, ring reads and the copy lane exactly
+// A scan of the ring over time: sixdof_history_extremes, sixdof_history_events, sixdof_history_norms and sixdof_history_norm_events.  Ordering, ring reads and the copy lane exactly
 // as for sixdof_watch_read above; not through ring_bin_read, whose output and chunk rule are per sample: here ALL samples of the
 // range go into one launch, cut into time segments (time_scan.hpp), and the output is per row or run.  The staging buffer is the
 // accumulator: a call with `continues` merges into what the previous call left there, a call with `holds` delivers nothing.
@@ -1840,6 +1841,32 @@ static int time_scan_read(sixdof_handle* h, const TimeScanSpec& spec, uint64_t f
 }
 
 static const char* const kOnlyRecorded = "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded";
+
+// One probe of sixdof_history_norms or sixdof_history_norm_events, checked against the ring and resolved into what the kernels
+// see; `which` names it in the messages.
+static int norm_probe_resolve(sixdof_handle* h, const std::string& which, const sixdof_norm_probe& p, uint32_t period, NormsProbe& d) {
+    if (p.flags & ~SIXDOF_NORM_MINUS) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown flags " + std::to_string(p.flags));
+    if (p.count == 0 || p.count > SIXDOF_NORM_MAX_COUNT)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": count " + std::to_string(p.count) + ", 1 to " + std::to_string(SIXDOF_NORM_MAX_COUNT) + " elements can be asked for");
+    const bool minus = (p.flags & SIXDOF_NORM_MINUS) != 0;
+    d.count = p.count, d.flags = p.flags;
+    for (int side = 0; side < (minus ? 2 : 1); side++) {
+        const char* name = side ? " (minus)" : "";
+        const uint32_t element = side ? p.minus_element : p.element, group = side ? p.minus_group : p.group;
+        if (group >= period)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + name + ": group " + std::to_string(group) + " is not below period " + std::to_string(period));
+        const void* ring = nullptr;
+        size_t w = 0;
+        if (!watch_lookup(h, side ? p.minus_component_id : p.component_id, &ring, &w) || !ring)
+            return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, which + name + ": " + kOnlyRecorded);
+        if (uint64_t(element) + p.count > w)
+            return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + name + ": elements " + std::to_string(element) + " .. " + std::to_string(uint64_t(element) + p.count - 1) +
+                                                            " are not all below the component's width " + std::to_string(w));
+        if (side) d.ring_b = ring, d.w_b = static_cast<uint32_t>(w), d.element_b = element, d.group_b = group;
+        else d.ring_a = ring, d.w_a = static_cast<uint32_t>(w), d.element_a = element, d.group_a = group;
+    }
+    return SIXDOF_OK;
+}
 
 extern "C" {
 
@@ -2000,27 +2027,7 @@ int sixdof_history_norms(sixdof_handle* h, const sixdof_norm_probe* probes, size
             for (size_t k = 0; k < n_probes; k++) {
                 const sixdof_norm_probe& p = probes[k];
                 const std::string which = who + ": probe " + std::to_string(k);
-                if (p.flags & ~SIXDOF_NORM_MINUS) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown flags " + std::to_string(p.flags));
-                if (p.count == 0 || p.count > SIXDOF_NORM_MAX_COUNT)
-                    return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": count " + std::to_string(p.count) + ", 1 to " + std::to_string(SIXDOF_NORM_MAX_COUNT) + " elements can be asked for");
-                const bool minus = (p.flags & SIXDOF_NORM_MINUS) != 0;
-                NormsProbe& d = a.p[k];
-                d.count = p.count, d.flags = p.flags;
-                for (int side = 0; side < (minus ? 2 : 1); side++) {
-                    const char* name = side ? " (minus)" : "";
-                    const uint32_t element = side ? p.minus_element : p.element, group = side ? p.minus_group : p.group;
-                    if (group >= period)
-                        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + name + ": group " + std::to_string(group) + " is not below period " + std::to_string(period));
-                    const void* ring = nullptr;
-                    size_t w = 0;
-                    if (!watch_lookup(h, side ? p.minus_component_id : p.component_id, &ring, &w) || !ring)
-                        return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, which + name + ": " + kOnlyRecorded);
-                    if (uint64_t(element) + p.count > w)
-                        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + name + ": elements " + std::to_string(element) + " .. " + std::to_string(uint64_t(element) + p.count - 1) +
-                                                                        " are not all below the component's width " + std::to_string(w));
-                    if (side) d.ring_b = ring, d.w_b = static_cast<uint32_t>(w), d.element_b = element, d.group_b = group;
-                    else d.ring_a = ring, d.w_a = static_cast<uint32_t>(w), d.element_a = element, d.group_a = group;
-                }
+                if (int rc = norm_probe_resolve(h, which, p, period, a.p[k]); rc != SIXDOF_OK) return rc;
             }
             return SIXDOF_OK;
         },
@@ -2041,6 +2048,90 @@ int sixdof_history_norms(sixdof_handle* h, const sixdof_norm_probe* probes, size
             hipError_t e = launch_history_norms(a, np, sc.stage.get<double>(), sc.scratch.get(), segments, merge_into, n, period, first_tick, n_samples, every, hs.ring,
                                                 h->elem_size(), h->stream.get());
             return e == hipSuccess ? int(SIXDOF_OK) : h->hip_fail(e, "history_norms");
+        });
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// The first event of every run per trigger on a squared vector length or separation, and the rows of the captured components at
+// it: sixdof_history_events' shape with the probes of sixdof_history_norms.  One walk (and merge) launch covers all triggers, a unit
+// is one (trigger, run); the capture launches are the events' own, handed the triggers' modes (norm_events_capture_args).  The
+// accumulator is the record buffer together with the staging buffer, as for the events.
+int sixdof_history_norm_events(sixdof_handle* h, const sixdof_norm_trigger* triggers, size_t n_triggers, const uint64_t* capture_ids,
+                               size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
+                               double* event_dst, double* const capture_dst[], uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    History& hs = h->hist;
+    History::TimeScan& sc = hs.norm_events;
+    const TimeScanSpec spec{"history_norm_events", SIXDOF_NORM_EVENTS_ASYNC, SIXDOF_NORM_EVENTS_CONTINUE, SIXDOF_NORM_EVENTS_HOLD, "SIXDOF_NORM_EVENTS_CONTINUE",
+                            "triggers, captures, period, rows and rings", "SIXDOF_NORM_EVENTS_SEGMENTS", norm_events_segments, kNormEventsFields, &sc};
+    const std::string who = spec.who;
+    const bool hold = (flags & SIXDOF_NORM_EVENTS_HOLD) != 0;
+    const uint64_t n = h->desc.n_entities;
+    const uint32_t nt = static_cast<uint32_t>(n_triggers);
+    NormEventsArgs a{};
+    return time_scan_read(
+        h, spec, first_tick, n_samples, every, flags,
+        [&](bool&) -> int {
+            if (n_triggers == 0 || n_triggers > SIXDOF_NORM_EVENTS_MAX_TRIGGERS)
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(n_triggers) + " triggers, 1 to " + std::to_string(SIXDOF_NORM_EVENTS_MAX_TRIGGERS) + " can be asked for");
+            if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
+            if (n % period != 0)
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+            if (!triggers || (n_captures && !capture_ids) || (!hold && (!event_dst || (n_captures && !capture_dst))))
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
+            for (size_t k = 0; k < n_triggers; k++) {
+                const sixdof_norm_trigger& t = triggers[k];
+                const std::string which = who + ": trigger " + std::to_string(k);
+                if (t.op > SIXDOF_EVENT_GE) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown op " + std::to_string(t.op));
+                if (t.mode > SIXDOF_EVENT_CROSSING) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown mode " + std::to_string(t.mode));
+                if (!std::isfinite(t.level_sq) || t.level_sq < 0.0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": the squared level is not finite or is below 0");
+                if (int rc = norm_probe_resolve(h, which, t.probe, period, a.t[k].probe); rc != SIXDOF_OK) return rc;
+                a.t[k].level_sq = t.level_sq, a.t[k].op = t.op, a.t[k].mode = t.mode;
+            }
+            return SIXDOF_OK;
+        },
+        [&](StagedRead& rd, History::ScanState& next, std::vector<uint64_t>& units) -> int {
+            units.push_back(n / period * n_triggers);
+            rd.add_block(hold ? nullptr : event_dst, static_cast<size_t>(units[0]) * kNormEventsPlanes * sizeof(double));
+            next.signature = {n_triggers, period, n_captures};
+            for (uint32_t k = 0; k < nt; k++) {
+                const sixdof_norm_trigger& t = triggers[k];
+                const sixdof_norm_probe& p = t.probe;
+                uint64_t level;
+                std::memcpy(&level, &t.level_sq, sizeof(level));
+                next.signature.insert(next.signature.end(), {p.component_id, p.minus_component_id, p.element, p.minus_element, p.group, p.minus_group, p.count, p.flags,
+                                                             level, t.op, t.mode});
+                next.rings.push_back(a.t[k].probe.ring_a), next.widths.push_back(a.t[k].probe.w_a);
+                if (p.flags & SIXDOF_NORM_MINUS) next.rings.push_back(a.t[k].probe.ring_b), next.widths.push_back(a.t[k].probe.w_b);
+            }
+            for (size_t k = 0; k < n_captures; k++) {
+                const int rc = rd.add(capture_ids[k], hold ? nullptr : capture_dst[k], static_cast<size_t>(n) * n_triggers, sizeof(double), kOnlyRecorded, !hold);
+                if (rc != SIXDOF_OK) return rc;
+                next.signature.push_back(capture_ids[k]);
+                next.rings.push_back(rd.parts[1 + k].ring), next.widths.push_back(rd.parts[1 + k].w);
+            }
+            return SIXDOF_OK;
+        },
+        [&](const StagedRead& rd, size_t, uint64_t units, uint32_t segments, bool merge_into) -> int {
+            if (events_record_bytes(units) > sc.rec.bytes()) {   // never for a continuing call: its records are as large as the accumulator's
+                HIP_TRY(h, hipStreamSynchronize(h->stream.get()));   // an earlier call's launches may still use the old buffer
+                HIP_TRY(h, sc.rec.alloc(static_cast<size_t>(events_record_bytes(units))));
+            }
+            hipError_t e = launch_history_norm_events(a, nt, sc.rec.get(), sc.stage.get<double>(), sc.scratch.get(), segments, merge_into, n, period, first_tick,
+                                                      n_samples, every, hs.ring, h->elem_size(), h->stream.get());
+            if (e != hipSuccess) return h->hip_fail(e, "history_norm_events");
+            const EventsArgs modes = norm_events_capture_args(a, nt);
+            for (size_t k0 = 0; k0 < n_captures; k0 += kRingBinMaxComponents) {
+                const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_captures - k0));
+                RingBinArgs c{};
+                for (uint32_t k = 0; k < cnt; k++) {
+                    const StagedRead::Part& p = rd.parts[1 + k0 + k];
+                    c.c[k].ring = p.ring, c.c[k].out_offset = p.offset / sizeof(double), c.c[k].w = static_cast<uint32_t>(p.w);
+                }
+                e = launch_events_capture(modes, nt, c, cnt, sc.rec.get(), sc.stage.get<double>(), merge_into, n, period, first_tick, n_samples, every, hs.ring,
+                                          h->elem_size(), h->stream.get());
+                if (e != hipSuccess) return h->hip_fail(e, "history_norm_events capture");
+            }
+            return SIXDOF_OK;
         });
 } SIXDOF_ABI_CATCH(err_of(h))
 

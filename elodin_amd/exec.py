@@ -10,6 +10,7 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Callable, Optional, Sequence
 
+import math
 import os
 from pathlib import Path
 
@@ -80,6 +81,17 @@ class Norm:
     minus: Optional[str] = None
     minus_element: Optional[int] = None
     minus_group: Optional[int] = None
+
+
+@dataclass(frozen=True)
+class NormEvent:
+    """One trigger of HipExec.history_norm_events: the Euclidean norm `norm` (a Norm: |r|, |v|, a separation) meets `op level`, with
+    `level` in the norm's own units — finite, not negative, its square finite.  The device compares squared norm and squared
+    level; modes as for Event."""
+    norm: Norm
+    op: str                 # "<", "<=", ">" or ">="
+    level: float
+    mode: str = "crossing"
 
 
 def dispersion_ellipse(cov2, prob: float = 0.99):
@@ -899,7 +911,7 @@ class HipExec:
         return wall, self._extremes_dict(names, raw)
 
     def _stream_accumulate(self, n_batches: int, ticks_per_batch: int, every: int, continue_flag: int, hold_flag: int, flags: int, read) -> float:
-        """The loop of stream_extremes / stream_events / stream_norms: every batch is stepped and its samples — ending on the batch's last tick —
+        """The loop of stream_extremes / stream_events / stream_norms / stream_norm_events: every batch is stepped and its samples — ending on the batch's last tick —
         are merged into an accumulator on the device by `read(first_tick, last, read_flags)`: held unless the batch is the last,
         continuing from the second batch on.  A ring one batch deep is enabled unless there is one at least that large.
         Whatever happens, the caller's flags are restored and the handle is drained.  Returns the wall time in seconds."""
@@ -1016,19 +1028,24 @@ class HipExec:
             raise ValueError(f"history_norms: {len(norms)} norms, 1 to {L.NORMS_MAX_PROBES} can be asked for")
         arr = (L.NormProbe * len(norms))()
         for p, v in zip(arr, norms):
-            if not 1 <= int(v.count) <= L.NORM_MAX_COUNT:
-                raise ValueError(f"history_norms: {v!r}: count is 1 to {L.NORM_MAX_COUNT}")
-            if v.minus is None and (v.minus_element is not None or v.minus_group is not None):
-                raise ValueError(f"history_norms: {v!r}: minus_element and minus_group need minus, the component they index")
-            if min(int(v.element), int(v.group), int(v.element if v.minus_element is None else v.minus_element),
-                   int(v.group if v.minus_group is None else v.minus_group)) < 0:
-                raise ValueError(f"history_norms: {v!r}: a negative element or group")
-            p.component_id, p.element, p.group, p.count = L.component_id(v.component), int(v.element), int(v.group), int(v.count)
-            if v.minus is not None:
-                p.flags, p.minus_component_id = L.NORM_MINUS, L.component_id(v.minus)
-                p.minus_element = int(v.element if v.minus_element is None else v.minus_element)
-                p.minus_group = int(v.group if v.minus_group is None else v.minus_group)
+            HipExec._norm_probe_fill(p, v, "history_norms")
         return arr
+
+    @staticmethod
+    def _norm_probe_fill(p, v, who: str) -> None:
+        """Fills the sixdof_norm_probe `p` from the Norm `v`, or raises its ValueError in the name of `who`."""
+        if not 1 <= int(v.count) <= L.NORM_MAX_COUNT:
+            raise ValueError(f"{who}: {v!r}: count is 1 to {L.NORM_MAX_COUNT}")
+        if v.minus is None and (v.minus_element is not None or v.minus_group is not None):
+            raise ValueError(f"{who}: {v!r}: minus_element and minus_group need minus, the component they index")
+        if min(int(v.element), int(v.group), int(v.element if v.minus_element is None else v.minus_element),
+               int(v.group if v.minus_group is None else v.minus_group)) < 0:
+            raise ValueError(f"{who}: {v!r}: a negative element or group")
+        p.component_id, p.element, p.group, p.count = L.component_id(v.component), int(v.element), int(v.group), int(v.count)
+        if v.minus is not None:
+            p.flags, p.minus_component_id = L.NORM_MINUS, L.component_id(v.minus)
+            p.minus_element = int(v.element if v.minus_element is None else v.minus_element)
+            p.minus_group = int(v.group if v.minus_group is None else v.minus_group)
 
     def _norms_buffer(self, n_norms: int, period: int) -> np.ndarray:
         """The [P, 6, runs] block, holding what a range without samples reduces to: count 0, NaN extremes, no ticks."""
@@ -1072,6 +1089,81 @@ class HipExec:
         wall = self._stream_accumulate(n_batches, ticks_per_batch, every, L.NORMS_CONTINUE, L.NORMS_HOLD, flags,
                                        lambda first, last, fl: self._norms_read(probes, period, first, n_samples, every, raw if last else None, fl))
         return wall, self._norms_dict(raw)
+
+    # ---- ring norm events: the first crossing of a vector's length or of a separation per run, and the state there ------------
+    NORM_EVENTS_FIELDS = ("tick", "value_sq", "tick_before", "value_before_sq")      # the four planes, in order
+
+    @staticmethod
+    def _norm_events_dict(capture_names, raw_events, raw_captures) -> dict:
+        """A [T, 4, runs] block and one [T, n, w] block per captured name -> {"tick", "tick_before": int64 [T, runs]; "value_sq",
+        "value_before_sq", "value", "value_before": f64 [T, runs]; "capture": {name: f64 [T, n, w]}}.  The tick planes arrive as
+        doubles below 2^53: the conversion is exact.  value and value_before are the square roots of the _sq fields, taken here on
+        the host: NaN stays NaN, +0.0 stays +0.0."""
+        out = {k: raw_events[:, i] if k.endswith("_sq") else raw_events[:, i].astype(np.int64) for i, k in enumerate(HipExec.NORM_EVENTS_FIELDS)}
+        out["value"], out["value_before"] = np.sqrt(out["value_sq"]), np.sqrt(out["value_before_sq"])
+        out["capture"] = dict(zip(capture_names, raw_captures))
+        return out
+
+    @staticmethod
+    def _norm_triggers(events):
+        """The ctypes array of sixdof_norm_trigger for a list of NormEvent — level_sq is level * level — or its ValueError."""
+        events = [events] if isinstance(events, NormEvent) else list(events)
+        if not 1 <= len(events) <= L.NORM_EVENTS_MAX_TRIGGERS:
+            raise ValueError(f"history_norm_events: {len(events)} events, 1 to {L.NORM_EVENTS_MAX_TRIGGERS} can be asked for")
+        arr = (L.NormTrigger * len(events))()
+        for t, e in zip(arr, events):
+            if e.op not in Event.OPS or e.mode not in Event.MODES:
+                raise ValueError(f"history_norm_events: {e!r}: op is one of {list(Event.OPS)}, mode one of {list(Event.MODES)}")
+            level = float(e.level)
+            if not (math.isfinite(level) and level >= 0.0 and math.isfinite(level * level)):
+                raise ValueError(f"history_norm_events: {e!r}: level is finite, not negative, and its square is finite")
+            HipExec._norm_probe_fill(t.probe, e.norm, "history_norm_events")
+            t.level_sq, t.op, t.mode = level * level, Event.OPS[e.op], Event.MODES[e.mode]
+        return arr
+
+    def _norm_events_read(self, triggers, comp, period: int, first_tick: int, n_samples: int, every: int, raw, ptrs, flags: int) -> None:
+        rc = self._lib.sixdof_history_norm_events(self._h, triggers, len(triggers), comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), period,
+                                                  first_tick, n_samples, every, None if raw is None else raw.ctypes.data, ptrs, flags)
+        if rc != L.OK:
+            _raise(self._h, rc, "sixdof_history_norm_events")
+
+    def history_norm_events(self, events, capture: Sequence[str], first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> dict:
+        """{"tick", "tick_before": int64 [T, runs]; "value_sq", "value_before_sq", "value", "value_before": f64 [T, runs]; "capture":
+        {name: f64 [T, n, w]}}: per NormEvent and run (period consecutive rows; runs = n // period), over the ticks first_tick,
+        first_tick + every, ... <= last_tick, the first sampled tick at which the event's norm meets its level, the squared norm
+        there, and tick and squared norm of the finite sample before — found on the device out of the ring.  The squared norm is
+        history_norms' (f64, left to right); one that is not finite, an overflowing one included, is skipped.  capture[name][e, r]
+        is row r of `name` at the event tick of r's run for event e.  tick 0 means no event: the values and the run's captured rows
+        are then NaN; tick_before 0 means no sample before it.  Stateless: no watch is involved."""
+        triggers = self._norm_triggers(events)
+        capture = [capture] if isinstance(capture, str) else list(capture)
+        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
+        raw, caps, ptrs = self._events_buffers(len(triggers), capture, period)
+        comp = np.array([L.component_id(n) for n in capture], dtype=np.uint64)
+        self._norm_events_read(triggers, comp, max(period, 0), first_tick, self._sample_count(first_tick, last_tick, every), every, raw, ptrs, 0)
+        return self._norm_events_dict(capture, raw, caps)
+
+    def stream_norm_events(self, events, capture: Sequence[str], n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, flags: int = 0):
+        """history_norm_events over a run longer than the ring: n_batches batches of ticks_per_batch ticks are stepped, and after
+        every batch its samples — every `every`-th tick, ending on the batch's last — are merged into the accumulator on the
+        device (SIXDOF_NORM_EVENTS_HOLD, SIXDOF_NORM_EVENTS_CONTINUE from the second batch on); a run's rows are captured in the
+        batch that sees its event.  Nothing crosses the link until the last batch's call delivers.  A ring one batch deep is
+        enough (enabled here unless enable_history already made one at least that large).  Returns (wall time in seconds, the
+        dict of history_norm_events); whatever happens, the caller's flags are restored and the handle is drained."""
+        triggers = self._norm_triggers(events)
+        capture = [capture] if isinstance(capture, str) else list(capture)
+        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
+        n_samples = self._stream_shape("stream_norm_events", ticks_per_batch, every)
+        if n_batches < 1:
+            raise ValueError("stream_norm_events: at least one batch")
+        if period < 1:
+            raise ValueError("stream_norm_events: period must be at least 1")
+        raw, caps, ptrs = self._events_buffers(len(triggers), capture, period)
+        comp = np.array([L.component_id(n) for n in capture], dtype=np.uint64)
+        wall = self._stream_accumulate(n_batches, ticks_per_batch, every, L.NORM_EVENTS_CONTINUE, L.NORM_EVENTS_HOLD, flags,
+                                       lambda first, last, fl: self._norm_events_read(triggers, comp, period, first, n_samples, every, raw if last else None,
+                                                                                      ptrs if last else None, fl))
+        return wall, self._norm_events_dict(capture, raw, caps)
 
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))

@@ -358,6 +358,16 @@ class Campaign:
         the entity of the run it reads: apogee, peak speed, the closest approach of two entities of a run and when."""
         return self.exec.history_norms(norms, first_tick, last_tick, every, period=self.entities_per_run)
 
+    def norm_events(self, events, capture, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
+        """When a vector's length or a separation of each run first passed a level and the run's state there, out of the device
+        ring (self.exec.enable_history): the dict of Exec.history_norm_events with a run = entities_per_run consecutive rows —
+        "tick", "tick_before", "value_sq", "value_before_sq", "value", "value_before", "t", "t_before", "t_cross": [event, run];
+        "capture": {component: [event, run, entity-of-run, w]}, every entity of a run taken at that run's own event tick (NaN where
+        the run has none).  A Norm's `group` (and minus_group) is the entity of the run it reads."""
+        out = self.exec.history_norm_events(events, capture, first_tick, last_tick, every, period=self.entities_per_run)
+        out["capture"] = {comp: v.reshape(v.shape[0], self.n_runs, self.entities_per_run, v.shape[-1]) for comp, v in out["capture"].items()}
+        return out
+
     def result_table(self, names: Sequence[str]) -> np.ndarray:
         """The runs' `el.monte_carlo.result(...)` records as [n_runs, len(names)] (NaN where a run reported nothing)."""
         out = np.full((self.n_runs, len(names)), np.nan)

@@ -646,6 +646,51 @@ typedef struct sixdof_norm_probe {     /* 40 bytes */
 int sixdof_history_norms(sixdof_handle* h, const sixdof_norm_probe* probes, size_t n_probes, uint32_t period,
                          uint64_t first_tick, uint64_t n_samples, uint64_t every, double* host_dst, uint32_t flags);
 
+/* ---- ring norm events: the first crossing of a vector's length or of a separation per run, and the state there -------------
+ * On a spherical or orbital world the conditions are lengths: touchdown or entry interface is |r| <= R + h, leaving a sphere of
+ * influence |r| >= r_soi, a keep-out sphere or conjunction |r_chaser - r_target| < d, a speed or tumble-rate limit |v| > v_max or
+ * |omega| > omega_max, loss of quaternion normalisation |q| > 1 + eps.  sixdof_history_events reads one element;
+ * sixdof_history_norms keeps only the extremes of a norm.  This reader puts the norms' value under the events' rule.
+ *
+ * A run is `period` consecutive rows (n_entities % period == 0; runs = n_entities / period).  For each trigger, run and sampled
+ * tick the value is s, exactly the SQUARED norm sixdof_history_norms forms of `probe` (every ring element widened to double, f64,
+ * left to right, no FMA contraction).  A sample is finite exactly when s is: an s that overflows from finite inputs is non-finite
+ * and therefore SKIPPED as the events skip a non-finite sample — it neither holds nor fails and is never a "before" sample.  The
+ * predicate is the IEEE compare s op level_sq against the SQUARED level: no square root and no other arithmetic on the device.
+ * SIXDOF_EVENT_LEVEL and SIXDOF_EVENT_CROSSING as for sixdof_history_events.
+ *
+ * Samples are the ticks first_tick, first_tick + every, ... (n_samples of them), all in the ring.  event_dst is
+ * [n_triggers][SIXDOF_NORM_EVENTS_PLANES][runs] doubles, plane-major: the event tick (0: none), s at it (NaN: none), the tick of
+ * the finite sample before it (0: none — also where a LEVEL event fell on the first finite sample) and s at that sample (NaN:
+ * none).  capture_dst[k] is [n_triggers][n_entities][w_k] doubles: every row of component capture_ids[k] at the event tick of
+ * the row's run for that trigger, NaN where the run has no event; n_captures = 0 reports the events only.  Ticks are exact in
+ * doubles: a range whose last sampled tick is 2^53 or more is refused.  The rule is exact and associative in time order and there
+ * are no atomics, so every output is bit-identical however the range is cut into time segments (SIXDOF_NORM_EVENTS_SEGMENTS in
+ * the environment forces a count; 0 or unset: the library's choice), launches or calls.  The square roots are left to the caller.
+ * SIXDOF_NORM_EVENTS_HOLD, SIXDOF_NORM_EVENTS_CONTINUE and SIXDOF_NORM_EVENTS_ASYNC behave as SIXDOF_EVENTS_HOLD, _CONTINUE and
+ * _ASYNC: a continuing call rewrites only the captures of the runs whose event it saw, and is accepted only if the previous call
+ * succeeded with the same triggers field for field (level_sq compared by its bits), the same capture ids in the same order and
+ * the same period, ring bases, widths and row count are unchanged, no sixdof_set_history or sixdof_bind_columns came since, and
+ * first_tick is above the last tick accumulated; otherwise SIXDOF_ERR_INVALID_ARGUMENT and the accumulator stays as it was.
+ * n_samples = 0 is a no-op that leaves the accumulator alone.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied and the
+ * accumulator as it was: everything sixdof_history_events refuses for range, flags, buffers, n_triggers, period, op and mode,
+ * everything sixdof_history_norms refuses for a probe, and a level_sq that is not finite or is below 0.  A probe or capture
+ * component the ring does not record: SIXDOF_ERR_COMPONENT_NOT_FOUND.  A call that fails in the runtime leaves the ring as it was
+ * and the accumulator invalid, as for sixdof_history_extremes. */
+typedef struct sixdof_norm_trigger {   /* 56 bytes */
+    sixdof_norm_probe probe;           /* as for sixdof_history_norms */
+    double level_sq;                   /* finite, >= 0: the SQUARED level */
+    uint32_t op, mode;                 /* SIXDOF_EVENT_LT .. SIXDOF_EVENT_GE; SIXDOF_EVENT_LEVEL or SIXDOF_EVENT_CROSSING */
+} sixdof_norm_trigger;
+#define SIXDOF_NORM_EVENTS_ASYNC    1u
+#define SIXDOF_NORM_EVENTS_CONTINUE 2u
+#define SIXDOF_NORM_EVENTS_HOLD     4u
+#define SIXDOF_NORM_EVENTS_PLANES   4
+#define SIXDOF_NORM_EVENTS_MAX_TRIGGERS 8
+int sixdof_history_norm_events(sixdof_handle* h, const sixdof_norm_trigger* triggers, size_t n_triggers, const uint64_t* capture_ids,
+                               size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
+                               double* event_dst, double* const capture_dst[], uint32_t flags);
+
 /* ---- ring covariances: how quantities vary TOGETHER across the rows, over time ---------------------------------------------
  * The landing footprint ellipse, the 6 x 6 position / velocity dispersion, whether touchdown speed goes with lateral miss: joint
  * moments.  The envelope's mean and m2 are the diagonal of this matrix; the off-diagonals cannot be recovered from them.

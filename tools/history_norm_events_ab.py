@@ -1,0 +1,343 @@
+#!/usr/bin/env python3
+"""Ring norm events against ring norms and against whole-block reads plus numpy, on one GPU, f64, at 65,536 runs and at 1,024
+(profiles/history_norm_events.md).  A run is two rows (period 2); ring of 1,024 ticks.  Two probes, each read alone: |v| of a run's
+row 0 (3 loads per sample) and the separation |r_0 - r_1| of its two rows (6 loads per sample).
+
+  read-back   one HipExec.history_norm_events over the 1,024 ticks, reduced only (SIXDOF_NORM_EVENTS_HOLD, then a synchronise), with a
+              trigger that NEVER fires — every thread loads every sample, as the norms walk does — beside history_norms of the same
+              probe, the yardstick (same loads, a 6-field record against 10 fields here), and beside the same trigger at a level
+              the runs pass at about mid-range, where a settled thread stops loading; all IN THE SAME CHILD, windows alternating.
+              The never-firing read is timed twice, as two rows of identical code: their spread is the margin of the comparison.
+              Then the delivered read with two captures, and the host route for the same answer, HipExec.history of the blocks +
+              numpy, timed on 32 ticks and scaled to 1,024.
+  segments    the never-firing |v| read under the plan's own time segments and under 1 .. 32 forced ones
+              (SIXDOF_NORM_EVENTS_SEGMENTS, read at every call: the settings alternate inside one child).  What
+              norm_events_plan.hpp's kNormEventsFillThreads is confirmed or replaced from.
+  streaming   entity-steps/s of the stepper at 65,536 runs while both mid-range triggers accumulate on the device with two captures:
+              stream_norm_events in 64-tick batches at every 1 and 8, against recording only.
+
+Every leg runs in a child process of its own, under its own time limit, several windows per child after a warm-up; a window is
+`reps` calls behind one another, each ending in a stream synchronise.  The legs alternate over `--rounds` rounds and a failed
+child ends the run.
+
+    python tools/history_norm_events_ab.py [--out profiles/history_norm_events.md]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+RUNS = (65536, 1024)
+PERIOD = 2
+READ_TICKS = 1024
+HOST_TICKS = 32                          # the host route is timed on this many ticks and scaled
+BATCH = 64
+SEGMENTS = ("0", "1", "2", "4", "8", "16", "32")     # 0: the plan's choice
+REPS = {65536: 10, 1024: 100}            # calls per window
+PROBES = ("speed", "separation")
+CAPTURE = ["world_pos", "world_vel"]
+NEVER = 1e150                            # a level no norm of this world reaches; its square is finite
+
+
+def _norm(which):
+    import elodin_amd as ea
+    return ea.Norm("world_vel", 3, 3) if which == "speed" else ea.Norm("world_pos", 4, 3, group=0, minus="world_pos", minus_group=1)
+
+
+def _never(which):
+    """A crossing that never fires: the walk goes to the end of every run."""
+    import elodin_amd as ea
+    return ea.NormEvent(_norm(which), ">", NEVER)
+
+
+def _mid_level(ex, which):
+    """A level the runs pass at about mid-range: the median over the runs of the norm at tick READ_TICKS / 2."""
+    import numpy as np
+    mid = READ_TICKS // 2
+    if which == "speed":
+        d = ex.history("world_vel", mid, mid)[0, 0::PERIOD, 3:6]
+    else:
+        pos = ex.history("world_pos", mid, mid)[0]
+        d = pos[0::PERIOD, 4:7] - pos[1::PERIOD, 4:7]
+    return float(np.median(np.sqrt((d * d).sum(axis=1))))
+
+
+def _exec(runs, ticks_per_launch):
+    import elodin_amd as ea
+    from elodin_amd import workloads
+    w = workloads.independent_bodies(runs * PERIOD)
+    eff = workloads.gravity_torque_effectors(w["body_torque"])
+    return ea.HipExec(w["world_pos"], w["world_vel"], w["inertia"], entity_ids=w["entity_ids"], simulation_time_step=workloads.DT_120HZ,
+                      effectors=eff, ticks_per_launch=ticks_per_launch)
+
+
+def _recorded(runs):
+    ex = _exec(runs, BATCH)
+    ex.enable_history(READ_TICKS)
+    ex.invoke_batch(READ_TICKS)
+    return ex
+
+
+def _windows(windows, reps, call):
+    for _ in range(2):
+        call()
+    out = []
+    for _ in range(windows):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            call()
+        out.append((time.perf_counter() - t0) / reps)
+    return out
+
+
+def _held_norms(ex, which):
+    """One reduce-only read of the whole ring: nothing is delivered, the call is waited for."""
+    from elodin_amd import _lib as L
+    probes = ex._norm_probes(_norm(which))
+
+    def call():
+        ex._norms_read(probes, PERIOD, 1, READ_TICKS, 1, None, L.NORMS_HOLD)
+        ex.sync()
+    return call
+
+
+def _held_norm_events(ex, event):
+    import numpy as np
+    from elodin_amd import _lib as L
+    trig = ex._norm_triggers(event)
+    comp = np.array([], dtype=np.uint64)
+
+    def call():
+        ex._norm_events_read(trig, comp, PERIOD, 1, READ_TICKS, 1, None, None, L.NORM_EVENTS_HOLD)
+        ex.sync()
+    return call
+
+
+def leg_read(windows, runs):
+    import numpy as np
+    import elodin_amd as ea
+    ex = _recorded(runs)
+    calls, fired = {}, {}
+    for which in PROBES:
+        mid = ea.NormEvent(_norm(which), ">=", _mid_level(ex, which))
+        assert (ex.history_norm_events(_never(which), [], 1, READ_TICKS, period=PERIOD)["tick"] == 0).all()
+        got = ex.history_norm_events(mid, CAPTURE, 1, READ_TICKS, period=PERIOD)
+        hit = got["tick"][0] > 0
+        fired[which] = {"share": float(hit.mean()), "median_tick": float(np.median(got["tick"][0][hit])) if hit.any() else 0.0}
+        calls[which + "_never"] = _held_norm_events(ex, _never(which))
+        calls[which + "_norms"] = _held_norms(ex, which)
+        calls[which + "_never_again"] = _held_norm_events(ex, _never(which))
+        calls[which + "_mid"] = _held_norm_events(ex, mid)
+        calls[which + "_delivered"] = lambda mid=mid: ex.history_norm_events(mid, CAPTURE, 1, READ_TICKS, period=PERIOD)
+    out = {k: [] for k in calls}
+    for k, call in calls.items():                        # every path once before anything is timed
+        call()
+    for _ in range(windows):                             # the paths alternate inside the child
+        for k, call in calls.items():
+            out[k] += _windows(1, REPS[runs], call)
+    return {"series": out, "fired": fired, "bytes_delivered": (4 * runs + runs * PERIOD * (7 + 6)) * 8}
+
+
+def leg_read_blocks(windows, runs):
+    import numpy as np
+    ex = _exec(runs, BATCH)
+    ex.enable_history(BATCH)
+    ex.invoke_batch(BATCH)
+    ex.history("world_pos", 1, 8)
+    out = {"speed": [], "separation": [], "speed_numpy": [], "separation_numpy": []}
+    scale = READ_TICKS / HOST_TICKS
+    rows = np.arange(runs)
+    for _ in range(windows):
+        for which in PROBES:
+            t0 = time.perf_counter()
+            vel = ex.history("world_vel", 1, HOST_TICKS)                               # a synchronise per tick inside
+            pos = ex.history("world_pos", 1, HOST_TICKS)                               # the captured state needs both blocks either way
+            d = vel[:, 0::PERIOD, 3:6] if which == "speed" else pos[:, 0::PERIOD, 4:7] - pos[:, 1::PERIOD, 4:7]
+            t1 = time.perf_counter()
+            s = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
+            holds = s >= np.median(s[HOST_TICKS // 2])                                 # every element is finite here
+            cross = holds[1:] & ~holds[:-1]
+            at = np.where(cross.any(axis=0), cross.argmax(axis=0) + 1, 0)
+            res = (at + 1, s[at, rows], s[np.maximum(at - 1, 0), rows], pos[at, rows * PERIOD], vel[at, rows * PERIOD])
+            spent = time.perf_counter() - t1
+            del d, s, res, pos, vel
+            out[which].append((time.perf_counter() - t0) * scale)
+            out[which + "_numpy"].append(spent * scale)
+    return {"series": out, "bytes": runs * PERIOD * READ_TICKS * (6 + 7) * 8}
+
+
+def leg_segments(windows, runs):
+    ex = _recorded(runs)
+    call = _held_norm_events(ex, _never("speed"))
+    out = {s: [] for s in SEGMENTS}
+    for s in SEGMENTS:                                   # every setting once before anything is timed
+        os.environ["SIXDOF_NORM_EVENTS_SEGMENTS"] = s
+        call()
+    for _ in range(windows):
+        for s in SEGMENTS:
+            os.environ["SIXDOF_NORM_EVENTS_SEGMENTS"] = s
+            out[s] += _windows(1, REPS[runs], call)
+    return {"series": out}
+
+
+def _rate(n, wall, batches):
+    return n * BATCH * batches / wall
+
+
+def leg_stream(windows, batches, every):
+    import elodin_amd as ea
+    runs = RUNS[0]
+    ex = _exec(runs, BATCH)
+    events = [ea.NormEvent(_norm("speed"), ">=", 40.0), ea.NormEvent(_norm("separation"), ">=", 1000.0)]
+    ex.stream_norm_events(events, CAPTURE, 4, BATCH, every=every, period=PERIOD)
+    return {"series": {"entity_steps_per_s": [_rate(runs * PERIOD, ex.stream_norm_events(events, CAPTURE, batches, BATCH, every=every, period=PERIOD)[0], batches)
+                                              for _ in range(windows)]},
+            "bytes_at_the_end": 2 * (4 * runs + runs * PERIOD * (7 + 6)) * 8}
+
+
+def leg_record_only(windows, batches):
+    from elodin_amd import _lib as L
+    runs = RUNS[0]
+    ex = _exec(runs, BATCH)
+    ex.enable_history(BATCH)
+    ex.invoke_batch(4 * BATCH)
+    out = []
+    for _ in range(windows):
+        ex.sync()
+        ex.set_flags(L.FLAG_ASYNC_STEP)
+        t0 = time.perf_counter()
+        for _ in range(batches):
+            ex.invoke_batch(BATCH)
+        ex.sync()
+        out.append(_rate(runs * PERIOD, time.perf_counter() - t0, batches))
+        ex.set_flags(0)
+    return {"series": {"entity_steps_per_s": out}, "bytes_at_the_end": 0}
+
+
+LEGS = {}       # name: (function, extra arguments, time limit of one child in seconds)
+for _runs in RUNS:
+    LEGS[f"read runs={_runs}: norm events and norms"] = (leg_read, (_runs,), 300)
+    LEGS[f"read runs={_runs}: history + numpy"] = (leg_read_blocks, (_runs,), 300)
+    LEGS[f"read runs={_runs}: segments"] = (leg_segments, (_runs,), 300)
+LEGS.update({
+    "stream: stream_norm_events every=1": (leg_stream, (1,), 240),
+    "stream: stream_norm_events every=8": (leg_stream, (8,), 240),
+    "stream: record only": (leg_record_only, (), 240),
+})
+
+
+def run_leg(name, windows, batches):
+    fn, extra, _ = LEGS[name]
+    res = fn(windows, *extra) if name.startswith("read") else fn(windows, batches, *extra)
+    print("LEG_RESULT " + json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--leg", help="(internal) run one leg in this process")
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--windows", type=int, default=3, help="timed windows per child")
+    ap.add_argument("--batches", type=int, default=64, help="64-tick batches per streaming window")
+    ap.add_argument("--box", default="one MI355X", help="how the note names the machine")
+    ap.add_argument("--registers", default="", help="the kernels' register counts, as the compiler reports them, for the note")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "history_norm_events.md"))
+    a = ap.parse_args()
+    if a.leg:
+        run_leg(a.leg, a.windows, a.batches)
+        return
+    pooled = {name: {} for name in LEGS}       # name -> series -> values
+    meta = {}
+    for rnd in range(a.rounds):
+        for name, (_, _, limit) in LEGS.items():
+            windows = 1 if "numpy" in name else a.windows
+            cmd = [sys.executable, str(Path(__file__).resolve()), "--leg", name, "--windows", str(windows), "--batches", str(a.batches)]
+            env = dict(os.environ)
+            for var in ("SIXDOF_NORM_EVENTS_SEGMENTS", "SIXDOF_NORMS_SEGMENTS"):
+                env.pop(var, None)
+            try:
+                p = subprocess.run(cmd, capture_output=True, text=True, timeout=limit, env=env)
+            except subprocess.TimeoutExpired:
+                sys.exit(f"{name}: no result within {limit} s; nothing more is started")
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("LEG_RESULT ")]
+            if p.returncode != 0 or not line:
+                sys.exit(f"{name}: child failed (status {p.returncode}); nothing more is started\n{p.stdout[-1500:]}\n{p.stderr[-3000:]}")
+            res = json.loads(line[-1][len("LEG_RESULT "):])
+            for key, v in res["series"].items():
+                pooled[name].setdefault(key, []).extend(v)
+            meta[name] = {k: v for k, v in res.items() if k != "series"}
+            print(f"round {rnd} {name}: " + json.dumps(res["series"]), flush=True)
+    med = lambda name, key: statistics.median(pooled[name][key])
+
+    def ms(name, key):
+        v = pooled[name][key]
+        return f"{statistics.median(v) * 1e3:,.3f} ms [{min(v) * 1e3:,.3f} .. {max(v) * 1e3:,.3f}]"
+    rows = ["# Ring norm events against ring norms and whole-block reads",
+            "",
+            f"{a.box[0].upper() + a.box[1:]}, f64, RK4, {BATCH} ticks per launch, ring of {READ_TICKS:,} ticks, runs of {PERIOD} rows.  Two probes, each read alone: the speed |v| of",
+            "a run's row 0 (3 loads per sample) and the separation |r_0 - r_1| of its two rows (6 loads per sample).  The yardstick is",
+            "history_norms of the same probe: the same loads, a 6-field record against the 10 fields here.  A trigger that never fires loads",
+            "every sample, as the norms walk does; the same trigger at the median norm of tick 512 lets settled threads stop loading.",
+            f"tools/history_norm_events_ab.py: every leg in a child process of its own, {a.rounds} rounds of alternating legs, a warm-up and then",
+            f"{a.windows} timed windows per child, a window being {REPS[RUNS[0]]} calls behind one another at 65,536 runs and {REPS[RUNS[1]]} at 1,024, each ending in a",
+            "stream synchronise; the paths alternate inside one child.  Per call: median, and [min .. max], over all windows.  The",
+            "never-firing read appears twice: two rows of identical code, whose spread is the margin of every ratio below.",
+            "Nothing here is a gate.",
+            ""]
+    if a.registers:
+        rows += [f"Registers, as the compiler reports them for gfx950 (no spills, no scratch): {a.registers}.", ""]
+    for runs in RUNS:
+        both, blocks, seg = f"read runs={runs}: norm events and norms", f"read runs={runs}: history + numpy", f"read runs={runs}: segments"
+        rows += [f"## Read-back at {runs:,} runs ({runs * PERIOD:,} rows): {READ_TICKS:,} ticks",
+                 "",
+                 "| path | bytes to the host | time per call |",
+                 "|---|---|---|"]
+        for which in PROBES:
+            f = meta[both]["fired"][which]
+            rows += [f"| history_norm_events {which}, never firing, reduced only (HOLD, synchronise) | 0 | {ms(both, which + '_never')} |",
+                     f"| the same again (identical code) | 0 | {ms(both, which + '_never_again')} |",
+                     f"| history_norms {which}, reduced only | 0 | {ms(both, which + '_norms')} |",
+                     f"| history_norm_events {which}, {f['share']:.0%} of the runs firing, median tick {f['median_tick']:,.0f}, reduced only | 0 | {ms(both, which + '_mid')} |",
+                     f"| the same, delivered with two captures | {meta[both]['bytes_delivered'] / 1e6:,.2f} MB | {ms(both, which + '_delivered')} |",
+                     f"| history + numpy {which} (timed on {HOST_TICKS} ticks, scaled by {READ_TICKS // HOST_TICKS}) | {meta[blocks]['bytes'] / 1e6:,.0f} MB | {ms(blocks, which)} |"]
+        rows += [""]
+        for which in PROBES:
+            never, again = med(both, which + "_never"), med(both, which + "_never_again")
+            rows += [f"{which}: never firing {never / med(both, which + '_norms'):,.3f} of the time of the norms walk (identical rows differ by "
+                     f"{abs(never - again) / min(never, again):.1%}); firing {med(both, which + '_mid') / never:,.2f} of never firing; delivered "
+                     f"{med(blocks, which) / med(both, which + '_delivered'):,.0f} times faster than the host route, of which {med(blocks, which + '_numpy'):,.2f} s is numpy."]
+        rows += ["",
+                 f"### Time segments at {runs:,} runs (|v|, never firing, reduced only)",
+                 "",
+                 "| SIXDOF_NORM_EVENTS_SEGMENTS | time per call |",
+                 "|---|---|"]
+        for s in SEGMENTS:
+            rows.append(f"| {'0 (the plan)' if s == '0' else s} | {ms(seg, s)} |")
+        rows.append("")
+    rows += [f"## Streaming at {RUNS[0]:,} runs ({RUNS[0] * PERIOD:,} rows), both triggers and two captures: {a.batches:,} batches of {BATCH} ticks per window",
+             "",
+             "| path | bytes to the host at the end | entity-steps/s (wall time of the window) |",
+             "|---|---|---|"]
+    for name in LEGS:
+        if name.startswith("stream"):
+            v = pooled[name]["entity_steps_per_s"]
+            rows.append(f"| {name[8:]} | {meta[name]['bytes_at_the_end'] / 1e6:,.2f} MB | {statistics.median(v):.3e} [{min(v):.3e} .. {max(v):.3e}] |")
+    rec = med("stream: record only", "entity_steps_per_s")
+    rel = lambda name: med(name, "entity_steps_per_s") / rec
+    rows += ["",
+             f"Relative to recording with nothing read back: stream_norm_events every=1 {rel('stream: stream_norm_events every=1'):.2f}, every=8 "
+             f"{rel('stream: stream_norm_events every=8'):.2f}.",
+             ""]
+    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.out).write_text("\n".join(rows))
+    print("\n".join(rows))
+
+
+if __name__ == "__main__":
+    main()
