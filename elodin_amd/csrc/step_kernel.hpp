@@ -15,7 +15,10 @@
 // `global_load_lds_dwordx4` (LDS-DMA: 16 B per lane, 1 KiB per wave instruction, no VGPR round
 // trip, all of a wave's ~10 KiB in flight at once); each lane then reads its own row from LDS
 // (56-B rows with ds_read_b64 are bank-conflict free: lane*14 mod 64 permutes the even banks of a
-// 32-lane group).  Results go rows -> LDS -> 16-B-per-lane coalesced stores.  The strided row
+// 32-lane group).  Results go rows -> LDS -> 16-B-per-lane coalesced stores.  The step kernels address a slab
+// once per column on the way in (scalar column base, lane * 16, the column's LDS base in M0; the 1-KiB chunks are
+// the DMA's immediate offsets, the lanes of the partial last chunk are masked once), and the RK4 kernels do the
+// same on the way out (see "slab movement" below).  The strided row
 // accesses therefore never reach the memory system, and PMC traffic equals the algorithmic bytes
 // (profiles/).  Single-wave workgroups need no cross-wave barrier and let 8+ independent waves per
 // CU overlap their load / compute / store phases.
@@ -36,6 +39,7 @@
 // (0 * NaN = NaN poisons that tick like the reference's); later ticks' a_in is already folded into v0.
 #pragma once
 #include <type_traits>
+#include <utility>
 
 #include "effectors.hpp"
 #include "kernels.hpp"
@@ -59,7 +63,8 @@ constexpr int kPolPlain = 0, kPolNtStores = 1, kPolSc1Stores = 2, kPolNt = 9;
 constexpr int pol_ld(int pol) { return pol / 8; }
 constexpr int pol_st(int pol) { return pol % 8; }
 
-// Whole-wave slab of BYTES bytes (multiple of 16), global -> LDS by LDS-DMA.
+// Whole-wave slab of BYTES bytes (multiple of 16), global -> LDS by LDS-DMA, one column at a time with an address per chunk:
+// pair_kernel.hpp.  The step kernels move their three input columns with slabs_dma_in below.
 template <int BYTES, int POL>
 __device__ __forceinline__ void slab_dma_in(const char* __restrict__ g, char* l, uint32_t lane) {
     constexpr int kFull = BYTES / 1024, kRem = (BYTES % 1024) / 16;
@@ -73,7 +78,9 @@ __device__ __forceinline__ void slab_dma_in(const char* __restrict__ g, char* l,
                                          0, kAux);
 }
 
-// Whole-wave slab, LDS -> global: read every chunk first, then issue the stores back to back.
+// Whole-wave slab, LDS -> global: read every chunk first, then issue the stores back to back.  pair_kernel.hpp, and the step
+// kernels that are not RK4: the semi-implicit ones are short and sit at the edge of an occupancy step, and slab_flush below
+// costs the f32 gravity | body_torque kernel 6 VGPRs and that step (78 -> 84, profiles/step_slab_issue_ab.md).
 typedef float vfloat4 __attribute__((ext_vector_type(4)));
 template <int POL>
 __device__ __forceinline__ void store16(char* g, vfloat4 v) {
@@ -94,6 +101,95 @@ __device__ __forceinline__ void slab_out(const char* l, char* __restrict__ g, ui
 #pragma unroll
     for (int i = 0; i < kFull; i++) store16<NT>(g + i * 1024 + lane * 16, tmp[i]);
     if (kRem && lane < (uint32_t)kRem) store16<NT>(g + kFull * 1024 + lane * 16, tmp[kFull]);
+}
+
+// Whole-wave slabs, global -> LDS by LDS-DMA.  A slab of BYTES bytes (multiple of 16) is BYTES / 1024 chunks that all 64 lanes
+// move, 16 bytes each, and a remainder chunk that the first (BYTES % 1024) / 16 lanes move.  Every chunk of a column has the
+// same two addresses, the lane's source (column base + lane * 16) and the column's LDS base (M0): chunk i is the
+// instruction's immediate offset i * 1024, which the hardware adds to both.  So a column costs one address and one M0 write,
+// however many chunks it has, and ceil(BYTES / 1024) instructions.
+typedef __attribute__((address_space(3))) char* lds_bytes;
+// Instruction selection works one basic block at a time: `uniform base + lane offset` becomes the scalar-base form of a global
+// instruction (no 64-bit vector add) only where the sum is formed in the block that uses it.  Inside a masked region the lane
+// offset goes through this, so that the sum is formed there and not taken over, as a 64-bit vector address, from the block in
+// front of it.  An empty asm statement only steers this compiler, it promises nothing: what guards the shape (here and at the
+// statement that keeps slab_flush's remainder read in front of the stores) is tests/test_step_kernel_slab_issue.py, which
+// reads the built library; after a toolchain update that fails it, rework these.
+__device__ __forceinline__ uint32_t same_in_this_block(uint32_t v) {
+    asm("" : "+v"(v));
+    return v;
+}
+template <int AUX, int... I>
+__device__ __forceinline__ void dma_chunks(global_cptr g, lds_ptr l, std::integer_sequence<int, I...>) {
+    (__builtin_amdgcn_global_load_lds(g, l, 16, I * 1024, AUX), ...);
+}
+template <int BYTES, int POL>
+struct SlabIn {
+    static constexpr int kFull = BYTES / 1024, kRem = BYTES % 1024;
+    static constexpr int kAux = pol_ld(POL) == 1 ? 2 : 0;
+    const char* base;   // the column's slab, wave-uniform
+    lds_ptr l;          // its LDS image, wave-uniform: taken from the __shared__ array itself, so the cast checks nothing
+    uint32_t lane16;
+    __device__ __forceinline__ SlabIn(const void* g, lds_bytes lds, uint32_t lane16_)
+        : base(static_cast<const char*>(g)), l((lds_ptr)lds), lane16(lane16_) {}
+    __device__ __forceinline__ void full() const {
+        dma_chunks<kAux>((global_cptr)(base + lane16), l, std::make_integer_sequence<int, kFull>{});
+    }
+    // the remainder chunk: lanes below kRem / 16 only, from inside their masked region
+    __device__ __forceinline__ void rem(uint32_t r16) const {
+        dma_chunks<kAux>((global_cptr)(base + r16), l, std::integer_sequence<int, kFull>{});
+    }
+};
+// The three input columns of a step: [ROWS,7] at l, [ROWS,6] behind it, [ROWS,7] behind that.  Every full chunk first, then
+// the remainder chunks together in ONE exec region (the 6-wide remainder, where there is one, is the narrower and nests in
+// it): interleaved per column, the compiler joins the two 7-wide regions by copying the loads between them per lane class.
+template <class T, int ROWS, int POL>
+__device__ __forceinline__ void slabs_dma_in(const T* g7a, const T* g6, const T* g7b, lds_bytes l, uint32_t lane16) {
+    constexpr int kB7 = ROWS * 7 * sizeof(T), kB6 = ROWS * 6 * sizeof(T);
+    const SlabIn<kB7, POL> a(g7a, l, lane16), c(g7b, l + kB7 + kB6, lane16);
+    const SlabIn<kB6, POL> b(g6, l + kB7, lane16);
+    static_assert(b.kRem <= a.kRem, "the 6-wide remainder nests inside the 7-wide one");
+    a.full();
+    b.full();
+    c.full();
+    if (a.kRem && lane16 < (uint32_t)a.kRem) {
+        const uint32_t r16 = same_in_this_block(lane16);
+        c.rem(r16);
+        a.rem(r16);
+        if (b.kRem && lane16 < (uint32_t)b.kRem) b.rem(same_in_this_block(lane16));
+    }
+}
+
+// Whole-wave slab, LDS -> global: read every chunk first, then issue the stores back to back, again with one address per side
+// (the lane's: base + lane * 16) and the chunk as the immediate offset.
+template <int POL, int OFF>
+__device__ __forceinline__ void store16_at(char* g, vfloat4 v) {   // to g + OFF
+    constexpr int ST = pol_st(POL);
+    if constexpr (ST == 1) __builtin_nontemporal_store(v, reinterpret_cast<vfloat4*>(g + OFF));
+    else if constexpr (ST == 2) asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1" ::"v"(g), "v"(v), "n"(OFF) : "memory");
+    else if constexpr (ST == 3) asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc0 sc1" ::"v"(g), "v"(v), "n"(OFF) : "memory");
+    else if constexpr (ST == 4) asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1 nt" ::"v"(g), "v"(v), "n"(OFF) : "memory");
+    else *reinterpret_cast<vfloat4*>(g + OFF) = v;
+}
+template <int POL, int... I>
+__device__ __forceinline__ void store_chunks(char* g, const vfloat4* v, std::integer_sequence<int, I...>) {
+    (store16_at<POL, I * 1024>(g, v[I]), ...);
+}
+// PAST: the LDS array reaches at least ceil(BYTES / 1024) KiB behind l, so all 64 lanes read the remainder chunk (what the
+// lanes behind the column's end read is never stored) and only its store is masked: one exec region per flush, not two, and
+// ceil(BYTES / 1024) store instructions.
+template <int BYTES, int POL, bool PAST = false>
+__device__ __forceinline__ void slab_flush(const char* l, char* __restrict__ g, uint32_t lane) {
+    constexpr int kFull = BYTES / 1024, kRem = BYTES % 1024;
+    const uint32_t lane16 = lane * 16;
+    const char* const ll = l + lane16;
+    vfloat4 tmp[kFull + 1];
+#pragma unroll
+    for (int i = 0; i < kFull; i++) tmp[i] = *reinterpret_cast<const vfloat4*>(ll + i * 1024);
+    if (kRem && (PAST || lane16 < (uint32_t)kRem)) tmp[kFull] = *reinterpret_cast<const vfloat4*>(ll + kFull * 1024);
+    if constexpr (kRem && PAST) asm volatile("" : "+v"(tmp[kFull]));   // read here, with the others: not inside the masked region
+    store_chunks<POL>(g + lane16, tmp, std::make_integer_sequence<int, kFull>{});
+    if (kRem && lane16 < (uint32_t)kRem) store16_at<POL, kFull * 1024>(g + same_in_this_block(lane16), tmp[kFull]);
 }
 
 // Ragged last wave (rows < 64): element-wise.
@@ -213,6 +309,9 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
     const uint32_t rows = min((uint32_t)ROWS, P.n - row0);
     const uint32_t t = threadIdx.x;
     const bool full = rows == ROWS;  // wave-uniform
+    // The chunk-addressed flush (slab_flush) and the ragged wave's late flush: RK4 only, see slab_out above.  The generated
+    // systems-only kernels (kNone) keep the one-column movers too.
+    constexpr bool kNewMovers = INTEGRATOR == kRk4;
 
     T* const g_pos = static_cast<T*>(P.pos) + (size_t)row0 * 7;
     T* const g_vel = static_cast<T*>(P.vel) + (size_t)row0 * 6;
@@ -234,10 +333,8 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
     // systems only and none of them touches a Body column (NoModel::kBodyDead): the Body slabs stay where they are
     constexpr bool kDead = INTEGRATOR == kNone && PIPE::kBodyDead;
     if constexpr (!kDead) {
-        if (full) {
-            slab_dma_in<ROWS * 7 * sizeof(T), POL>(reinterpret_cast<const char*>(g_pos), reinterpret_cast<char*>(l_pos), t);
-            slab_dma_in<ROWS * 6 * sizeof(T), POL>(reinterpret_cast<const char*>(g_vel), reinterpret_cast<char*>(l_vel), t);
-            slab_dma_in<ROWS * 7 * sizeof(T), POL>(reinterpret_cast<const char*>(g_inertia), reinterpret_cast<char*>(l_c), t);
+        if (__builtin_expect(full, 1)) {
+            slabs_dma_in<T, ROWS, POL>(g_pos, g_vel, g_inertia, (lds_bytes)reinterpret_cast<char*>(lds), t * 16);
         } else {
             slab_in_tail(g_pos, l_pos, rows * 7, t);
             slab_in_tail(g_vel, l_vel, rows * 6, t);
@@ -339,6 +436,33 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
         if (full) slab_out<ROWS * 6 * sizeof(T), decltype(pol)::value>(reinterpret_cast<const char*>(l), reinterpret_cast<char*>(o), t);
         else slab_out_tail(l, o, rows * 6, t);
     };
+    // RK4 (kNewMovers).  A flush reads whole KiB chunks (slab_flush's PAST): behind every column but the last lies the next
+    // one; `force`, the last, reads past its end only where it has no partial chunk.  `early` (compile time): a store of the
+    // early path below.  There only full waves store; the ragged wave's columns leave in the late flush at the end of the
+    // kernel, so the last-tick body holds no element-wise mover and a full wave pays one untaken test per column for the one
+    // ragged wave a launch may have.
+    constexpr int kB7 = ROWS * 7 * sizeof(T), kB6 = ROWS * 6 * sizeof(T);
+    constexpr bool kPastForce = (kB6 + 1023) / 1024 * 1024 == kB6;
+    constexpr auto whole_chunks_fit = [](int first_elem, int bytes) {
+        return first_elem * (int)sizeof(T) + (bytes + 1023) / 1024 * 1024 <= (int)sizeof(lds);
+    };
+    static_assert(whole_chunks_fit(0, kB7) && whole_chunks_fit(ROWS * 7, kB6) && whole_chunks_fit(ROWS * 13, kB6) &&
+                      (!kPastForce || whole_chunks_fit(ROWS * 19, kB6)),
+                  "a PAST flush reads outside the LDS array: l_pos, l_vel, l_c, l_force");
+    auto flush_pos = [&](T* o, auto pol, auto early) {
+        if (__builtin_expect(full, 1)) slab_flush<kB7, decltype(pol)::value, true>(reinterpret_cast<const char*>(l_pos), reinterpret_cast<char*>(o), t);
+        else if constexpr (!decltype(early)::value) slab_out_tail(l_pos, o, rows * 7, t);
+    };
+    auto flush6_chunks_as = [&](const T* l, T* o, auto pol, auto early, auto past) {
+        if (__builtin_expect(full, 1)) slab_flush<kB6, decltype(pol)::value, decltype(past)::value>(reinterpret_cast<const char*>(l), reinterpret_cast<char*>(o), t);
+        else if constexpr (!decltype(early)::value) slab_out_tail(l, o, rows * 6, t);
+    };
+    auto flush6_chunks = [&](const T* l, T* o, auto pol, auto early) {   // l_vel, l_c (asserted above), not l_force
+        flush6_chunks_as(l, o, pol, early, std::true_type{});
+    };
+    auto flush_force = [&](T* o, auto pol, auto early) { flush6_chunks_as(l_force, o, pol, early, std::bool_constant<kPastForce>{}); };
+    constexpr std::true_type kEarly{};
+    constexpr std::false_type kLate{};
     constexpr std::integral_constant<int, POL> kLive{};   // cache policy of the live columns
     constexpr std::integral_constant<int, 1> kRing{};     // history ring slots are write-once: non-temporal stores
 
@@ -446,7 +570,7 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
             if constexpr (early) {
                 stage_pos(q_new, p_new);
                 __syncthreads();
-                flush7(l_pos, g_pos, kLive);
+                flush_pos(g_pos, kLive, kEarly);
             }
             F = zero_wrench<T>();
             PIPE::apply(P, aux, regs, b, F);
@@ -454,7 +578,7 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
                 if (!state_only) {
                     stage6(l_force, world_wrench<PIPE>(b.q, F));
                     __syncthreads();
-                    flush6(l_force, g_force, kLive);
+                    flush_force(g_force, kLive, kEarly);
                 }
             }
             A = calc_accel<PIPE>(b.q, F, inv_I, inv_m + taint, taint);
@@ -462,7 +586,7 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
                 if (!state_only) {
                     stage6(l_c, A);
                     __syncthreads();
-                    flush6(l_c, g_accel, kLive);
+                    flush6_chunks(l_c, g_accel, kLive, kEarly);
                 }
             }
             sa = sa + A;
@@ -474,8 +598,7 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
             if constexpr (early) {
                 stage6(l_vel, v0);
                 __syncthreads();
-                flush6(l_vel, g_vel, kLive);
-                flushed = true;
+                flush6_chunks(l_vel, g_vel, kLive, kEarly);
             }
         } else if constexpr (INTEGRATOR == kNone) {
             // systems only (`World.build(system)` without six_dof): the pre / post hooks are the whole tick
@@ -532,10 +655,17 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
                 stage6(l_force, F_out);
                 __syncthreads();
                 const size_t r7 = (slot * P.n + row0) * 7, r6 = (slot * P.n + row0) * 6;
-                flush7(l_pos, static_cast<T*>(P.hist_pos) + r7, kRing);
-                flush6(l_vel, static_cast<T*>(P.hist_vel) + r6, kRing);
-                flush6(l_c, static_cast<T*>(P.hist_accel) + r6, kRing);
-                flush6(l_force, static_cast<T*>(P.hist_force) + r6, kRing);
+                if constexpr (kNewMovers) {
+                    flush_pos(static_cast<T*>(P.hist_pos) + r7, kRing, kLate);
+                    flush6_chunks(l_vel, static_cast<T*>(P.hist_vel) + r6, kRing, kLate);
+                    flush6_chunks(l_c, static_cast<T*>(P.hist_accel) + r6, kRing, kLate);
+                    flush_force(static_cast<T*>(P.hist_force) + r6, kRing, kLate);
+                } else {
+                    flush7(l_pos, static_cast<T*>(P.hist_pos) + r7, kRing);
+                    flush6(l_vel, static_cast<T*>(P.hist_vel) + r6, kRing);
+                    flush6(l_c, static_cast<T*>(P.hist_accel) + r6, kRing);
+                    flush6(l_force, static_cast<T*>(P.hist_force) + r6, kRing);
+                }
             }
             if constexpr (PIPE::kHasModel)
                 if (active) PIPE::record(P, slot, row0 + t, regs);   // component columns of a generated program
@@ -553,8 +683,11 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
                 if (P.accel_in_check && P.n_ticks) one_tick(no, yes, tick++);   // once per upload: late flush, speed is no concern
             for (; tick + 1 < P.n_ticks; tick++) one_tick(no, no, tick);
             if (tick < P.n_ticks) {
-                if (early_ok) one_tick(yes, no, tick);
-                else one_tick(no, no, tick);
+                if (early_ok) {
+                    one_tick(yes, no, tick);
+                    if constexpr (kNewMovers)
+                        if (full) return;   // every live column has left; the ragged wave's leave in the late flush
+                } else one_tick(no, no, tick);
             }
         }
     }
@@ -576,11 +709,19 @@ __global__ __launch_bounds__(kWave) void sixdof_step_kernel(const StepParams P) 
         stage6(l_force, F_out);
     }
     __syncthreads();
-    flush7(l_pos, g_pos, kLive);
-    flush6(l_vel, g_vel, kLive);
-    if (state_only) return;
-    flush6(l_c, g_accel, kLive);
-    flush6(l_force, g_force, kLive);
+    if constexpr (kNewMovers) {
+        flush_pos(g_pos, kLive, kLate);
+        flush6_chunks(l_vel, g_vel, kLive, kLate);
+        if (state_only) return;
+        flush6_chunks(l_c, g_accel, kLive, kLate);
+        flush_force(g_force, kLive, kLate);
+    } else {
+        flush7(l_pos, g_pos, kLive);
+        flush6(l_vel, g_vel, kLive);
+        if (state_only) return;
+        flush6(l_c, g_accel, kLive);
+        flush6(l_force, g_force, kLive);
+    }
 }
 
 // ---- kernel selection ----------------------------------------------------------------------------------------
