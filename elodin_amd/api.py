@@ -906,13 +906,7 @@ class Exec:
         for comp in [e.component for e in evs] + caps:
             self._refuse_unrecorded("history_events", comp, comp)
         (first, last, step), _ = self._sampled_ticks("history_events", first_tick, last_tick, every)
-        s = getattr(self, "_substeps", 1)
-        out: Dict[str, Any] = dict(self._hip.history_events(evs, caps, first, last, step, period))
-        for tick_field, seconds in (("tick", "t"), ("tick_before", "t_before")):
-            out[tick_field] = out[tick_field] // s          # exact: every sample is a multiple of the sub-step count
-            out[seconds] = np.where(out[tick_field] == 0, np.nan, out[tick_field].astype(np.float64) * self._dt)
-        out["t_cross"] = self._crossing_time(np.array([float(e.level) for e in evs]), out)
-        return out
+        return self._event_times(evs, dict(self._hip.history_events(evs, caps, first, last, step, period)))
 
     def history_norms(self, norms, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> Dict[str, Any]:
         """Per-run extremes of a vector's length or of a separation: {"count", "argmin", "argmax", "first_nonfinite": int64 [P,
@@ -925,12 +919,8 @@ class Exec:
         for comp in [c for p in probes for c in (p.component, p.minus) if c is not None]:
             self._refuse_unrecorded("history_norms", comp, comp)
         (first, last, step), _ = self._sampled_ticks("history_norms", first_tick, last_tick, every)
-        s = getattr(self, "_substeps", 1)
         out: Dict[str, Any] = dict(self._hip.history_norms(probes, first, last, step, period))
-        for tick_field, seconds in (("argmin", "t_min"), ("argmax", "t_max"), ("first_nonfinite", "t_first_nonfinite")):
-            out[tick_field] = out[tick_field] // s          # exact: every sample is a multiple of the sub-step count
-            out[seconds] = np.where(out[tick_field] == 0, np.nan, out[tick_field].astype(np.float64) * self._dt)
-        return out
+        return self._world_ticks(out, (("argmin", "t_min"), ("argmax", "t_max"), ("first_nonfinite", "t_first_nonfinite")))
 
     def history_norm_events(self, events, capture, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> Dict[str, Any]:
         """At what tick did a vector's length or a separation first pass a level, and what was the run's state there: {"tick",
@@ -947,11 +937,20 @@ class Exec:
         for comp in [c for e in evs for c in (e.norm.component, e.norm.minus) if c is not None] + caps:
             self._refuse_unrecorded("history_norm_events", comp, comp)
         (first, last, step), _ = self._sampled_ticks("history_norm_events", first_tick, last_tick, every)
+        return self._event_times(evs, dict(self._hip.history_norm_events(evs, caps, first, last, step, period)))
+
+    def _world_ticks(self, out: Dict[str, Any], fields) -> Dict[str, Any]:
+        """`out` with every (tick field, seconds field) pair of `fields` filled in: the executor's ticks as world ticks, and their
+        time in seconds, NaN where the tick is 0 (none)."""
         s = getattr(self, "_substeps", 1)
-        out: Dict[str, Any] = dict(self._hip.history_norm_events(evs, caps, first, last, step, period))
-        for tick_field, seconds in (("tick", "t"), ("tick_before", "t_before")):
+        for tick_field, seconds in fields:
             out[tick_field] = out[tick_field] // s          # exact: every sample is a multiple of the sub-step count
             out[seconds] = np.where(out[tick_field] == 0, np.nan, out[tick_field].astype(np.float64) * self._dt)
+        return out
+
+    def _event_times(self, evs, out: Dict[str, Any]) -> Dict[str, Any]:
+        """What history_events and history_norm_events add to the executor's dict: world ticks, seconds, and t_cross."""
+        self._world_ticks(out, (("tick", "t"), ("tick_before", "t_before")))
         out["t_cross"] = self._crossing_time(np.array([float(e.level) for e in evs]), out)
         return out
 

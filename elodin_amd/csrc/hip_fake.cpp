@@ -711,42 +711,96 @@ hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components,
         else quantiles_of_tick<float>(src, n, d.w, period, ranks, h, st, to);
     }));
 }
-// the walk and the merge themselves (extremes_kernels.hip), serially: extremes_plan.hpp's rule in the kernels' segmentation and the
-// kernels' own loop (time_scan.hpp: scan_walk) — with more than one segment every (segment, element) record goes through the launch's scratch, as on the device
-template <class E>
-static void extremes_of_component(const RingBinDesc& d, double* out, uint64_t* scratch, uint64_t stride, uint32_t segments, bool merge_into, uint64_t n,
-                                  uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
-    const uint64_t total = n * d.w;
+// ---- the scans over time: the walk and the merge themselves (extremes_, events_, norms_ and norm_events_kernels.hip), serially ----
+// The two stages of a scan launch in the kernels' segmentation (time_scan.hpp) for `units` units: walk(unit, lo, hi, start) -> record
+// is the kernel's own walk over the samples [lo, hi); slot(segment, unit) is the unit's record in scratch, its fields `stride`
+// apart — with more than one segment every (segment, unit) record goes through the launch's scratch, as on the device.  Record,
+// rule and accumulator come with `acc`, one of the two below.
+template <class Acc, class Walk, class Slot>
+static void scan_stages(const Acc& acc, uint64_t units, uint64_t stride, uint32_t segments, bool merge_into, uint64_t n_samples, Walk walk, Slot slot) {
+    using Record = typename Acc::Record;
+    const bool resume = segments == 1 && merge_into;
     for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
         const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
-        for (uint64_t i = 0; i < total; i++) {
-            ExtremesRecord r = scan_walk(extremes_empty(), ExtremesRule{}, static_cast<const E*>(d.ring) + i, total, lo, hi, first_tick, every, ring);
-            double* o = out + d.out_offset + i;
-            if (segments == 1) {
-                if (merge_into) r = extremes_merge(extremes_absorb<E>(o, total), r);
-                extremes_emit<E>(r, o, total);
-            } else {
-                extremes_store(r, scratch + uint64_t(seg) * kExtremesFields * stride + d.scratch_offset + i, stride);
+        for (uint64_t u = 0; u < units; u++) {
+            Record r = walk(u, lo, hi, resume && Acc::kWalksOn ? acc.held(u) : Acc::empty());
+            if (segments > 1) {
+                Acc::store(r, slot(seg, u), stride);
+                continue;
             }
+            if (resume && !Acc::kWalksOn) r = Acc::merge(acc.held(u), r);
+            acc.emit(r, u);
         }
     }
-    for (uint64_t i = 0; segments > 1 && i < total; i++) {                 // stage 2
-        double* o = out + d.out_offset + i;
-        ExtremesRecord r = merge_into ? extremes_absorb<E>(o, total) : extremes_empty();
-        for (uint32_t s = 0; s < segments; s++) r = extremes_merge(r, extremes_load(scratch + uint64_t(s) * kExtremesFields * stride + d.scratch_offset + i, stride));
-        extremes_emit<E>(r, o, total);
+    for (uint64_t u = 0; segments > 1 && u < units; u++) {                 // stage 2
+        Record r = merge_into ? acc.held(u) : Acc::empty();
+        for (uint32_t s = 0; s < segments; s++) r = Acc::merge(r, Acc::load(slot(s, u), stride));
+        acc.emit(r, u);
     }
 }
+// The accumulator in the output planes, under extremes_plan.hpp's rule (the extremes, the norms): at(unit) is the unit's first
+// plane, the planes of E `stride` apart.  A continuing one-segment walk starts empty and is merged behind what the planes hold.
+template <class E, class At>
+struct PlanesAcc {
+    using Record = ExtremesRecord;
+    static constexpr bool kWalksOn = false;
+    uint64_t stride;
+    At at;
+    static Record empty() { return extremes_empty(); }
+    static Record merge(const Record& earlier, const Record& later) { return extremes_merge(earlier, later); }
+    static void store(const Record& r, uint64_t* base, uint64_t s) { extremes_store(r, base, s); }
+    static Record load(const uint64_t* base, uint64_t s) { return extremes_load(base, s); }
+    Record held(uint64_t u) const { return extremes_absorb<E>(at(u), stride); }
+    void emit(const Record& r, uint64_t u) const { extremes_emit<E>(r, at(u), stride); }
+};
+template <class E, class At>
+static PlanesAcc<E, At> planes_acc(uint64_t stride, At at) { return {stride, at}; }
+// The accumulator in a record buffer, under events_plan.hpp's rule (the events, the norm events): mine(unit) is the unit's record,
+// at(unit) its first output plane of E, both `runs` apart.  A continuing one-segment walk starts FROM the record, as the kernels do.
+template <class E, class Mine, class At>
+struct RecordsAcc {
+    using Record = EventsRecord;
+    static constexpr bool kWalksOn = true;
+    uint64_t runs;
+    uint32_t mode;
+    Mine mine;
+    At at;
+    static Record empty() { return events_empty(); }
+    static Record merge(const Record& earlier, const Record& later) { return events_merge(earlier, later); }
+    static void store(const Record& r, uint64_t* base, uint64_t s) { events_store(r, base, s); }
+    static Record load(const uint64_t* base, uint64_t s) { return events_load(base, s); }
+    Record held(uint64_t u) const { return events_load(mine(u), runs); }
+    void emit(const Record& r, uint64_t u) const { events_store(r, mine(u), runs), events_emit<E>(r, mode, at(u), runs); }
+};
+template <class E, class Mine, class At>
+static RecordsAcc<E, Mine, At> records_acc(uint64_t runs, uint32_t mode, Mine mine, At at) { return {runs, mode, mine, at}; }
+// f(E{}) for the ring's element type
+template <class F>
+static void with_elem(size_t elem, F f) {
+    if (elem == 8) f(double{});
+    else f(float{});
+}
+// The deferred form of a scan launch: `dev` and what rings(item, dev) adds for each of its items is the device memory it names.
+template <class Rings, class Run>
+static hipError_t defer_scan(hipStream_t s, const char* what, std::vector<const void*> dev, uint32_t items, uint32_t max_items, Rings rings, Run run) {
+    for (uint32_t c = 0; c < items && c < max_items; c++) rings(c, dev);
+    return defer(s, what, std::move(dev), run);
+}
+static void probe_rings(const NormsProbe& p, std::vector<const void*>& dev) {
+    dev.push_back(p.ring_a);
+    if (p.flags & kNormMinus) dev.push_back(p.ring_b);
+}
+static bool probe_live(const NormsProbe& p, uint64_t ring, uint64_t n, size_t elem) {
+    return live(p.ring_a, ring * n * p.w_a * elem) && (!(p.flags & kNormMinus) || live(p.ring_b, ring * n * p.w_b * elem));
+}
+// extremes_plan.hpp's rule over the kernels' own loop (time_scan.hpp: scan_walk); a unit is one element of a row
 hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, double* out, void* scratch, uint64_t scratch_stride, uint32_t segments,
                                    bool merge_into, uint64_t n, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem,
                                    hipStream_t s) {
-    if (deferring()) {
-        std::vector<const void*> dev{out, scratch};
-        for (uint32_t c = 0; c < n_components && c < kRingBinMaxComponents; c++) dev.push_back(a.c[c].ring);
-        return defer(s, "history_extremes", std::move(dev), [=] {
+    if (deferring())
+        return defer_scan(s, "history_extremes", {out, scratch}, n_components, kRingBinMaxComponents, [&](uint32_t c, auto& dev) { dev.push_back(a.c[c].ring); }, [=] {
             return launch_history_extremes(a, n_components, out, scratch, scratch_stride, segments, merge_into, n, first_tick, n_samples, every, ring, elem, s);
         });
-    }
     uint32_t widths[kRingBinMaxComponents] = {};
     for (uint32_t k = 0; k < n_components && k < kRingBinMaxComponents; k++) widths[k] = a.c[k].w;
     if (!extremes_launch_ok(n_components, kRingBinMaxComponents, widths, n, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
@@ -758,59 +812,43 @@ hipError_t launch_history_extremes(const RingBinArgs& a, uint32_t n_components, 
         if (!need(segments == 1 || d.scratch_offset + total <= scratch_stride, "extremes scratch of one segment")) return launch(false);
         if (!need(live(d.ring, ring * total * elem) && live(out + d.out_offset, kExtremesPlanes * total * sizeof(double)), "ring or extremes staging"))
             return launch(false);
-        if (elem == 8) extremes_of_component<double>(d, out, static_cast<uint64_t*>(scratch), scratch_stride, segments, merge_into, n, first_tick, n_samples, every, ring);
-        else extremes_of_component<float>(d, out, static_cast<uint64_t*>(scratch), scratch_stride, segments, merge_into, n, first_tick, n_samples, every, ring);
+        with_elem(elem, [&](auto e) {
+            using E = decltype(e);
+            scan_stages(planes_acc<E>(total, [&](uint64_t i) { return out + d.out_offset + i; }), total, scratch_stride, segments, merge_into, n_samples,
+                        [&](uint64_t i, uint64_t lo, uint64_t hi, const ExtremesRecord& start) {
+                            return scan_walk(start, ExtremesRule{}, static_cast<const E*>(d.ring) + i, total, lo, hi, first_tick, every, ring);
+                        },
+                        [&](uint32_t seg, uint64_t i) { return static_cast<uint64_t*>(scratch) + uint64_t(seg) * kExtremesFields * scratch_stride + d.scratch_offset + i; });
+        });
     }
     return launch(true);
 }
-// the walk, the merge and the capture themselves (events_kernels.hip), serially: events_plan.hpp's rule in the kernels' segmentation
-// and scan_walk, whose loop the kernel writes out — with more than one segment every (segment, trigger, run) record goes through the launch's scratch, as on the device
-template <class E>
-static void events_of_trigger(const EventsTrigger& t, uint32_t trig, uint32_t n_triggers, uint64_t* rec, double* out, uint64_t* scratch, uint32_t segments,
-                              bool merge_into, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
-    const uint64_t runs = n / period;
-    for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
-        const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
-        for (uint64_t run = 0; run < runs; run++) {
-            uint64_t* mine = rec + uint64_t(trig) * kEventsFields * runs + run;
-            EventsRecord r = scan_walk(segments == 1 && merge_into ? events_load(mine, runs) : events_empty(), EventsRule{t.level, t.op, t.mode},
-                                       static_cast<const E*>(t.ring) + (run * period + t.group) * t.w + t.element, n * t.w, lo, hi, first_tick, every, ring);
-            if (segments == 1) {
-                events_store(r, mine, runs);
-                events_emit<E>(r, t.mode, out + uint64_t(trig) * kEventsPlanes * runs + run, runs);
-            } else {
-                events_store(r, scratch + (uint64_t(seg) * n_triggers + trig) * kEventsFields * runs + run, runs);
-            }
-        }
-    }
-    for (uint64_t run = 0; segments > 1 && run < runs; run++) {            // stage 2
-        uint64_t* mine = rec + uint64_t(trig) * kEventsFields * runs + run;
-        EventsRecord r = merge_into ? events_load(mine, runs) : events_empty();
-        for (uint32_t s = 0; s < segments; s++) r = events_merge(r, events_load(scratch + (uint64_t(s) * n_triggers + trig) * kEventsFields * runs + run, runs));
-        events_store(r, mine, runs);
-        events_emit<E>(r, t.mode, out + uint64_t(trig) * kEventsPlanes * runs + run, runs);
-    }
-}
+// events_plan.hpp's rule over scan_walk, whose loop the kernel writes out; a unit is one run of a trigger.  The capture follows.
 hipError_t launch_history_events(const EventsArgs& a, uint32_t n_triggers, void* rec, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n,
                                  uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
-    if (deferring()) {
-        std::vector<const void*> dev{rec, out, scratch};
-        for (uint32_t c = 0; c < n_triggers && c < kEventsMaxTriggers; c++) dev.push_back(a.t[c].ring);
-        return defer(s, "history_events", std::move(dev), [=] {
+    if (deferring())
+        return defer_scan(s, "history_events", {rec, out, scratch}, n_triggers, kEventsMaxTriggers, [&](uint32_t c, auto& dev) { dev.push_back(a.t[c].ring); }, [=] {
             return launch_history_events(a, n_triggers, rec, out, scratch, segments, merge_into, n, period, first_tick, n_samples, every, ring, elem, s);
         });
-    }
     if (!events_launch_ok(a, n_triggers, n, period, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
     if (n == 0) return launch(true);
-    const uint64_t units = n / period * n_triggers;
+    const uint64_t runs = n / period, units = runs * n_triggers;
     if (segments > 1 && !need(live(scratch, scan_scratch_bytes(segments, units, kEventsFields)), "events scratch records")) return launch(false);
     if (!need(live(rec, events_record_bytes(units)) && live(out, units * kEventsPlanes * sizeof(double)), "events records or staging")) return launch(false);
     for (uint32_t k = 0; k < n_triggers; k++) {
         const EventsTrigger& t = a.t[k];
         if (!need(live(t.ring, ring * n * t.w * elem), "ring of a trigger")) return launch(false);
-        uint64_t *r = static_cast<uint64_t*>(rec), *sc = static_cast<uint64_t*>(scratch);
-        if (elem == 8) events_of_trigger<double>(t, k, n_triggers, r, out, sc, segments, merge_into, n, period, first_tick, n_samples, every, ring);
-        else events_of_trigger<float>(t, k, n_triggers, r, out, sc, segments, merge_into, n, period, first_tick, n_samples, every, ring);
+        with_elem(elem, [&](auto e) {
+            using E = decltype(e);
+            scan_stages(records_acc<E>(runs, t.mode, [&](uint64_t run) { return static_cast<uint64_t*>(rec) + uint64_t(k) * kEventsFields * runs + run; },
+                                       [&](uint64_t run) { return out + uint64_t(k) * kEventsPlanes * runs + run; }),
+                        runs, runs, segments, merge_into, n_samples,
+                        [&](uint64_t run, uint64_t lo, uint64_t hi, const EventsRecord& start) {
+                            return scan_walk(start, EventsRule{t.level, t.op, t.mode}, static_cast<const E*>(t.ring) + (run * period + t.group) * t.w + t.element, n * t.w,
+                                             lo, hi, first_tick, every, ring);
+                        },
+                        [&](uint32_t seg, uint64_t run) { return static_cast<uint64_t*>(scratch) + (uint64_t(seg) * n_triggers + k) * kEventsFields * runs + run; });
+        });
     }
     return launch(true);
 }
@@ -849,108 +887,53 @@ hipError_t launch_events_capture(const EventsArgs& a, uint32_t n_triggers, const
     }
     return launch(true);
 }
-// the walk and the merge themselves (norms_kernels.hip), serially: norms_plan.hpp's value and walk (norms_walk, the function the
-// kernel calls) and extremes_plan.hpp's rule in the kernels' segmentation — with more than one segment every (segment, probe, run) record goes through the launch's scratch, as on the device
-template <class E>
-static void norms_of_probe(const NormsProbe& p, uint32_t probe, uint32_t n_probes, double* out, uint64_t* scratch, uint32_t segments, bool merge_into, uint64_t n,
-                           uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
-    const uint64_t runs = n / period;
-    for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
-        const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
-        for (uint64_t run = 0; run < runs; run++) {
-            ExtremesRecord r = norms_walk<E>(extremes_empty(), p, run, n, period, lo, hi, first_tick, every, ring);
-            if (segments == 1) {
-                double* o = out + norms_out_index(probe, runs, run);
-                if (merge_into) r = extremes_merge(extremes_absorb<double>(o, runs), r);
-                extremes_emit<double>(r, o, runs);
-            } else {
-                extremes_store(r, scratch + norms_scratch_index(seg, n_probes, probe, runs, run), runs);
-            }
-        }
-    }
-    for (uint64_t run = 0; segments > 1 && run < runs; run++) {            // stage 2
-        double* o = out + norms_out_index(probe, runs, run);
-        ExtremesRecord r = merge_into ? extremes_absorb<double>(o, runs) : extremes_empty();
-        for (uint32_t s = 0; s < segments; s++) r = extremes_merge(r, extremes_load(scratch + norms_scratch_index(s, n_probes, probe, runs, run), runs));
-        extremes_emit<double>(r, o, runs);
-    }
-}
+// norms_plan.hpp's value and walk (norms_walk, the function the kernel calls) under extremes_plan.hpp's rule; a unit is one run of a probe
 hipError_t launch_history_norms(const NormsArgs& a, uint32_t n_probes, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n, uint32_t period,
                                 uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
-    if (deferring()) {
-        std::vector<const void*> dev{out, scratch};
-        for (uint32_t c = 0; c < n_probes && c < kNormsMaxProbes; c++) {
-            dev.push_back(a.p[c].ring_a);
-            if (a.p[c].flags & kNormMinus) dev.push_back(a.p[c].ring_b);
-        }
-        return defer(s, "history_norms", std::move(dev), [=] {
+    if (deferring())
+        return defer_scan(s, "history_norms", {out, scratch}, n_probes, kNormsMaxProbes, [&](uint32_t c, auto& dev) { probe_rings(a.p[c], dev); }, [=] {
             return launch_history_norms(a, n_probes, out, scratch, segments, merge_into, n, period, first_tick, n_samples, every, ring, elem, s);
         });
-    }
     if (!norms_launch_ok(a, n_probes, n, period, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
     if (n == 0) return launch(true);
-    const uint64_t units = n / period * n_probes;
+    const uint64_t runs = n / period, units = runs * n_probes;
     if (segments > 1 && !need(live(scratch, scan_scratch_bytes(segments, units, kNormsFields)), "norms scratch records")) return launch(false);
     if (!need(live(out, units * kNormsPlanes * sizeof(double)), "norms staging")) return launch(false);
     for (uint32_t k = 0; k < n_probes; k++) {
         const NormsProbe& p = a.p[k];
-        if (!need(live(p.ring_a, ring * n * p.w_a * elem) && (!(p.flags & kNormMinus) || live(p.ring_b, ring * n * p.w_b * elem)), "ring of a probe")) return launch(false);
-        if (elem == 8) norms_of_probe<double>(p, k, n_probes, out, static_cast<uint64_t*>(scratch), segments, merge_into, n, period, first_tick, n_samples, every, ring);
-        else norms_of_probe<float>(p, k, n_probes, out, static_cast<uint64_t*>(scratch), segments, merge_into, n, period, first_tick, n_samples, every, ring);
+        if (!need(probe_live(p, ring, n, elem), "ring of a probe")) return launch(false);
+        with_elem(elem, [&](auto e) {
+            using E = decltype(e);
+            scan_stages(planes_acc<double>(runs, [&](uint64_t run) { return out + norms_out_index(k, runs, run); }), runs, runs, segments, merge_into, n_samples,
+                        [&](uint64_t run, uint64_t lo, uint64_t hi, const ExtremesRecord& start) { return norms_walk<E>(start, p, run, n, period, lo, hi, first_tick, every, ring); },
+                        [&](uint32_t seg, uint64_t run) { return static_cast<uint64_t*>(scratch) + norms_scratch_index(seg, n_probes, k, runs, run); });
+        });
     }
     return launch(true);
 }
-// the walk and the merge themselves (norm_events_kernels.hip), serially: norm_events_plan.hpp's walk (norm_events_walk, the function
-// the kernel calls) and events_plan.hpp's rule in the kernels' segmentation — with more than one segment every (segment, trigger, run) record goes through the launch's scratch, as on the device
-template <class E>
-static void norm_events_of_trigger(const NormEventsTrigger& t, uint32_t trig, uint32_t n_triggers, uint64_t* rec, double* out, uint64_t* scratch, uint32_t segments,
-                                   bool merge_into, uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring) {
-    const uint64_t runs = n / period;
-    for (uint32_t seg = 0; seg < segments; seg++) {                        // stage 1
-        const uint64_t lo = scan_segment_start(n_samples, segments, seg), hi = scan_segment_start(n_samples, segments, seg + 1);
-        for (uint64_t run = 0; run < runs; run++) {
-            uint64_t* mine = rec + norm_events_record_index(trig, runs, run);
-            const EventsRecord r = norm_events_walk<E>(segments == 1 && merge_into ? events_load(mine, runs) : events_empty(), t, run, n, period, lo, hi, first_tick, every, ring);
-            if (segments == 1) {
-                events_store(r, mine, runs);
-                events_emit<double>(r, t.mode, out + norm_events_out_index(trig, runs, run), runs);
-            } else {
-                events_store(r, scratch + norm_events_scratch_index(seg, n_triggers, trig, runs, run), runs);
-            }
-        }
-    }
-    for (uint64_t run = 0; segments > 1 && run < runs; run++) {            // stage 2
-        uint64_t* mine = rec + norm_events_record_index(trig, runs, run);
-        EventsRecord r = merge_into ? events_load(mine, runs) : events_empty();
-        for (uint32_t s = 0; s < segments; s++) r = events_merge(r, events_load(scratch + norm_events_scratch_index(s, n_triggers, trig, runs, run), runs));
-        events_store(r, mine, runs);
-        events_emit<double>(r, t.mode, out + norm_events_out_index(trig, runs, run), runs);
-    }
-}
+// norm_events_plan.hpp's walk (norm_events_walk, the function the kernel calls) under events_plan.hpp's rule; a unit is one run of a trigger
 hipError_t launch_history_norm_events(const NormEventsArgs& a, uint32_t n_triggers, void* rec, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n,
                                       uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
-    if (deferring()) {
-        std::vector<const void*> dev{rec, out, scratch};
-        for (uint32_t c = 0; c < n_triggers && c < kNormEventsMaxTriggers; c++) {
-            dev.push_back(a.t[c].probe.ring_a);
-            if (a.t[c].probe.flags & kNormMinus) dev.push_back(a.t[c].probe.ring_b);
-        }
-        return defer(s, "history_norm_events", std::move(dev), [=] {
+    if (deferring())
+        return defer_scan(s, "history_norm_events", {rec, out, scratch}, n_triggers, kNormEventsMaxTriggers, [&](uint32_t c, auto& dev) { probe_rings(a.t[c].probe, dev); }, [=] {
             return launch_history_norm_events(a, n_triggers, rec, out, scratch, segments, merge_into, n, period, first_tick, n_samples, every, ring, elem, s);
         });
-    }
     if (!norm_events_launch_ok(a, n_triggers, n, period, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
     if (n == 0) return launch(true);
-    const uint64_t units = n / period * n_triggers;
+    const uint64_t runs = n / period, units = runs * n_triggers;
     if (segments > 1 && !need(live(scratch, scan_scratch_bytes(segments, units, kNormEventsFields)), "norm events scratch records")) return launch(false);
     if (!need(live(rec, events_record_bytes(units)) && live(out, units * kNormEventsPlanes * sizeof(double)), "norm events records or staging")) return launch(false);
     for (uint32_t k = 0; k < n_triggers; k++) {
         const NormEventsTrigger& t = a.t[k];
-        const NormsProbe& p = t.probe;
-        if (!need(live(p.ring_a, ring * n * p.w_a * elem) && (!(p.flags & kNormMinus) || live(p.ring_b, ring * n * p.w_b * elem)), "ring of a trigger's probe")) return launch(false);
-        uint64_t *r = static_cast<uint64_t*>(rec), *sc = static_cast<uint64_t*>(scratch);
-        if (elem == 8) norm_events_of_trigger<double>(t, k, n_triggers, r, out, sc, segments, merge_into, n, period, first_tick, n_samples, every, ring);
-        else norm_events_of_trigger<float>(t, k, n_triggers, r, out, sc, segments, merge_into, n, period, first_tick, n_samples, every, ring);
+        if (!need(probe_live(t.probe, ring, n, elem), "ring of a trigger's probe")) return launch(false);
+        with_elem(elem, [&](auto e) {
+            using E = decltype(e);
+            scan_stages(records_acc<double>(runs, t.mode, [&](uint64_t run) { return static_cast<uint64_t*>(rec) + norm_events_record_index(k, runs, run); },
+                                            [&](uint64_t run) { return out + norm_events_out_index(k, runs, run); }),
+                        runs, runs, segments, merge_into, n_samples,
+                        [&](uint64_t run, uint64_t lo, uint64_t hi, const EventsRecord& start) { return norm_events_walk<E>(start, t, run, n, period, lo, hi, first_tick, every, ring); },
+                        [&](uint32_t seg, uint64_t run) { return static_cast<uint64_t*>(scratch) + norm_events_scratch_index(seg, n_triggers, k, runs, run); });
+        });
     }
     return launch(true);
 }

@@ -1868,6 +1868,94 @@ static int norm_probe_resolve(sixdof_handle* h, const std::string& which, const 
     return SIXDOF_OK;
 }
 
+// What a continuing call has to repeat of one probe: its eight words, and the ring and width of either side as resolved.
+static void norm_probe_sign(const sixdof_norm_probe& p, const NormsProbe& d, History::ScanState& next) {
+    next.signature.insert(next.signature.end(), {p.component_id, p.minus_component_id, p.element, p.minus_element, p.group, p.minus_group, p.count, p.flags});
+    next.rings.push_back(d.ring_a), next.widths.push_back(d.w_a);
+    if (p.flags & SIXDOF_NORM_MINUS) next.rings.push_back(d.ring_b), next.widths.push_back(d.w_b);
+}
+
+// The refusals of every scan per run (sixdof_history_events, sixdof_history_norms, sixdof_history_norm_events), the first of its own
+// checks: `count` of its `noun` outside 1 .. max, no period, rows that are no whole runs.
+static int run_scan_checks(sixdof_handle* h, const std::string& who, size_t count, const char* noun, size_t max, uint32_t period) {
+    const uint64_t n = h->desc.n_entities;
+    if (count == 0 || count > max)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(count) + " " + noun + ", 1 to " + std::to_string(max) + " can be asked for");
+    if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
+    if (n % period != 0)
+        return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+    return SIXDOF_OK;
+}
+
+// The first event of every run per trigger, and the rows of the captured components at it: sixdof_history_events and
+// sixdof_history_norm_events, which differ in the trigger alone.  One walk (and merge) launch covers all triggers, a unit is one
+// (trigger, run); one capture launch behind it covers at most kRingBinMaxComponents captured components.  The accumulator is the
+// record buffer (what the rule continues from) together with the staging buffer (the event planes, rewritten by every call, and the
+// captures, of which a continuing call rewrites only the runs whose event it saw).  What an entry point supplies:
+// resolve(k, which) -> status checks trigger k past its op and mode and fills the walk's arguments; sign(k, next) appends its
+// signature words, rings and widths; walk(segments, merge_into) launches the walk; capture_args() are the triggers as
+// launch_events_capture reads them, asked for once the walk is launched.
+template <class Trigger, class Resolve, class Sign, class Walk, class CaptureArgs>
+static int run_events_read(sixdof_handle* h, const TimeScanSpec& spec, size_t max_triggers, const Trigger* triggers, size_t n_triggers,
+                           const uint64_t* capture_ids, size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
+                           double* event_dst, double* const capture_dst[], uint32_t flags, Resolve resolve, Sign sign, Walk walk, CaptureArgs capture_args) {
+    History& hs = h->hist;
+    History::TimeScan& sc = *spec.scan;
+    const std::string who = spec.who, capture_label = who + " capture";
+    const bool hold = (flags & spec.holds) != 0;
+    const uint64_t n = h->desc.n_entities;
+    const uint32_t nt = static_cast<uint32_t>(n_triggers);
+    return time_scan_read(
+        h, spec, first_tick, n_samples, every, flags,
+        [&](bool&) -> int {
+            if (int rc = run_scan_checks(h, who, n_triggers, "triggers", max_triggers, period); rc != SIXDOF_OK) return rc;
+            if (!triggers || (n_captures && !capture_ids) || (!hold && (!event_dst || (n_captures && !capture_dst))))
+                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
+            for (size_t k = 0; k < n_triggers; k++) {
+                const Trigger& t = triggers[k];
+                const std::string which = who + ": trigger " + std::to_string(k);
+                if (t.op > SIXDOF_EVENT_GE) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown op " + std::to_string(t.op));
+                if (t.mode > SIXDOF_EVENT_CROSSING) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown mode " + std::to_string(t.mode));
+                if (int rc = resolve(k, which); rc != SIXDOF_OK) return rc;
+            }
+            return SIXDOF_OK;
+        },
+        [&](StagedRead& rd, History::ScanState& next, std::vector<uint64_t>& units) -> int {
+            units.push_back(n / period * n_triggers);
+            rd.add_block(hold ? nullptr : event_dst, static_cast<size_t>(units[0]) * kEventsPlanes * sizeof(double));
+            next.signature = {n_triggers, period, n_captures};
+            for (uint32_t k = 0; k < nt; k++) sign(k, next);
+            for (size_t k = 0; k < n_captures; k++) {
+                const int rc = rd.add(capture_ids[k], hold ? nullptr : capture_dst[k], static_cast<size_t>(n) * n_triggers, sizeof(double), kOnlyRecorded, !hold);
+                if (rc != SIXDOF_OK) return rc;
+                next.signature.push_back(capture_ids[k]);
+                next.rings.push_back(rd.parts[1 + k].ring), next.widths.push_back(rd.parts[1 + k].w);
+            }
+            return SIXDOF_OK;
+        },
+        [&](const StagedRead& rd, size_t, uint64_t units, uint32_t segments, bool merge_into) -> int {
+            if (events_record_bytes(units) > sc.rec.bytes()) {   // never for a continuing call: its records are as large as the accumulator's
+                HIP_TRY(h, hipStreamSynchronize(h->stream.get()));   // an earlier call's launches may still use the old buffer
+                HIP_TRY(h, sc.rec.alloc(static_cast<size_t>(events_record_bytes(units))));
+            }
+            hipError_t e = walk(segments, merge_into);
+            if (e != hipSuccess) return h->hip_fail(e, spec.who);
+            const EventsArgs modes = capture_args();
+            for (size_t k0 = 0; k0 < n_captures; k0 += kRingBinMaxComponents) {
+                const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_captures - k0));
+                RingBinArgs c{};
+                for (uint32_t k = 0; k < cnt; k++) {
+                    const StagedRead::Part& p = rd.parts[1 + k0 + k];
+                    c.c[k].ring = p.ring, c.c[k].out_offset = p.offset / sizeof(double), c.c[k].w = static_cast<uint32_t>(p.w);
+                }
+                e = launch_events_capture(modes, nt, c, cnt, sc.rec.get(), sc.stage.get<double>(), merge_into, n, period, first_tick, n_samples, every, hs.ring,
+                                          h->elem_size(), h->stream.get());
+                if (e != hipSuccess) return h->hip_fail(e, capture_label.c_str());
+            }
+            return SIXDOF_OK;
+        });
+}
+
 extern "C" {
 
 // The extremes of every row over the sampled ticks of a range: one walk (and merge) launch per batch of at most
@@ -1918,10 +2006,7 @@ int sixdof_history_extremes(sixdof_handle* h, const uint64_t* component_ids, siz
         });
 } SIXDOF_ABI_CATCH(err_of(h))
 
-// The first event of every run per trigger, and the rows of the captured components at it.  One walk (and merge) launch covers
-// all triggers, a unit is one (trigger, run); one capture launch behind it covers at most kRingBinMaxComponents captured
-// components.  The accumulator is the record buffer (what the rule continues from) together with the staging buffer (the event
-// planes, rewritten by every call, and the captures, of which a continuing call rewrites only the runs whose event it saw).
+// run_events_read on one element of a row.
 int sixdof_history_events(sixdof_handle* h, const sixdof_event_trigger* triggers, size_t n_triggers, const uint64_t* capture_ids,
                           size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                           double* event_dst, double* const capture_dst[], uint32_t flags) try {
@@ -1930,75 +2015,31 @@ int sixdof_history_events(sixdof_handle* h, const sixdof_event_trigger* triggers
     History::TimeScan& sc = hs.events;
     const TimeScanSpec spec{"history_events", SIXDOF_EVENTS_ASYNC, SIXDOF_EVENTS_CONTINUE, SIXDOF_EVENTS_HOLD, "SIXDOF_EVENTS_CONTINUE",
                             "triggers, captures, period, rows and rings", "SIXDOF_EVENTS_SEGMENTS", events_segments, kEventsFields, &sc};
-    const std::string who = spec.who;
-    const bool hold = (flags & SIXDOF_EVENTS_HOLD) != 0;
-    const uint64_t n = h->desc.n_entities;
-    const uint32_t nt = static_cast<uint32_t>(n_triggers);
     EventsArgs a{};
-    return time_scan_read(
-        h, spec, first_tick, n_samples, every, flags,
-        [&](bool&) -> int {
-            if (n_triggers == 0 || n_triggers > SIXDOF_EVENTS_MAX_TRIGGERS)
-                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(n_triggers) + " triggers, 1 to " + std::to_string(SIXDOF_EVENTS_MAX_TRIGGERS) + " can be asked for");
-            if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
-            if (n % period != 0)
-                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
-            if (!triggers || (n_captures && !capture_ids) || (!hold && (!event_dst || (n_captures && !capture_dst))))
-                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
-            for (size_t k = 0; k < n_triggers; k++) {
-                const sixdof_event_trigger& t = triggers[k];
-                const std::string which = who + ": trigger " + std::to_string(k);
-                if (t.op > SIXDOF_EVENT_GE) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown op " + std::to_string(t.op));
-                if (t.mode > SIXDOF_EVENT_CROSSING) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown mode " + std::to_string(t.mode));
-                if (!std::isfinite(t.level)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": the level is not finite");
-                if (t.group >= period) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": group " + std::to_string(t.group) + " is not below period " + std::to_string(period));
-                size_t w = 0;
-                if (!watch_lookup(h, t.component_id, &a.t[k].ring, &w) || !a.t[k].ring) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, which + ": " + kOnlyRecorded);
-                if (t.element >= w) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": element " + std::to_string(t.element) + " is not below the component's width " + std::to_string(w));
-                a.t[k].level = t.level, a.t[k].w = static_cast<uint32_t>(w), a.t[k].element = t.element, a.t[k].group = t.group, a.t[k].op = t.op, a.t[k].mode = t.mode;
-            }
+    return run_events_read(
+        h, spec, SIXDOF_EVENTS_MAX_TRIGGERS, triggers, n_triggers, capture_ids, n_captures, period, first_tick, n_samples, every, event_dst, capture_dst, flags,
+        [&](size_t k, const std::string& which) -> int {
+            const sixdof_event_trigger& t = triggers[k];
+            if (!std::isfinite(t.level)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": the level is not finite");
+            if (t.group >= period) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": group " + std::to_string(t.group) + " is not below period " + std::to_string(period));
+            size_t w = 0;
+            if (!watch_lookup(h, t.component_id, &a.t[k].ring, &w) || !a.t[k].ring) return h->fail(SIXDOF_ERR_COMPONENT_NOT_FOUND, which + ": " + kOnlyRecorded);
+            if (t.element >= w) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": element " + std::to_string(t.element) + " is not below the component's width " + std::to_string(w));
+            a.t[k].level = t.level, a.t[k].w = static_cast<uint32_t>(w), a.t[k].element = t.element, a.t[k].group = t.group, a.t[k].op = t.op, a.t[k].mode = t.mode;
             return SIXDOF_OK;
         },
-        [&](StagedRead& rd, History::ScanState& next, std::vector<uint64_t>& units) -> int {
-            units.push_back(n / period * n_triggers);
-            rd.add_block(hold ? nullptr : event_dst, static_cast<size_t>(units[0]) * kEventsPlanes * sizeof(double));
-            next.signature = {n_triggers, period, n_captures};
-            for (uint32_t k = 0; k < nt; k++) {
-                const sixdof_event_trigger& t = triggers[k];
-                uint64_t level;
-                std::memcpy(&level, &t.level, sizeof(level));
-                next.signature.insert(next.signature.end(), {t.component_id, t.element, t.group, t.op, t.mode, level});
-                next.rings.push_back(a.t[k].ring), next.widths.push_back(a.t[k].w);
-            }
-            for (size_t k = 0; k < n_captures; k++) {
-                const int rc = rd.add(capture_ids[k], hold ? nullptr : capture_dst[k], static_cast<size_t>(n) * n_triggers, sizeof(double), kOnlyRecorded, !hold);
-                if (rc != SIXDOF_OK) return rc;
-                next.signature.push_back(capture_ids[k]);
-                next.rings.push_back(rd.parts[1 + k].ring), next.widths.push_back(rd.parts[1 + k].w);
-            }
-            return SIXDOF_OK;
+        [&](size_t k, History::ScanState& next) {
+            const sixdof_event_trigger& t = triggers[k];
+            uint64_t level;
+            std::memcpy(&level, &t.level, sizeof(level));
+            next.signature.insert(next.signature.end(), {t.component_id, t.element, t.group, t.op, t.mode, level});
+            next.rings.push_back(a.t[k].ring), next.widths.push_back(a.t[k].w);
         },
-        [&](const StagedRead& rd, size_t, uint64_t units, uint32_t segments, bool merge_into) -> int {
-            if (events_record_bytes(units) > sc.rec.bytes()) {   // never for a continuing call: its records are as large as the accumulator's
-                HIP_TRY(h, hipStreamSynchronize(h->stream.get()));   // an earlier call's launches may still use the old buffer
-                HIP_TRY(h, sc.rec.alloc(static_cast<size_t>(events_record_bytes(units))));
-            }
-            hipError_t e = launch_history_events(a, nt, sc.rec.get(), sc.stage.get<double>(), sc.scratch.get(), segments, merge_into, n, period, first_tick, n_samples,
-                                                 every, hs.ring, h->elem_size(), h->stream.get());
-            if (e != hipSuccess) return h->hip_fail(e, "history_events");
-            for (size_t k0 = 0; k0 < n_captures; k0 += kRingBinMaxComponents) {
-                const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_captures - k0));
-                RingBinArgs c{};
-                for (uint32_t k = 0; k < cnt; k++) {
-                    const StagedRead::Part& p = rd.parts[1 + k0 + k];
-                    c.c[k].ring = p.ring, c.c[k].out_offset = p.offset / sizeof(double), c.c[k].w = static_cast<uint32_t>(p.w);
-                }
-                e = launch_events_capture(a, nt, c, cnt, sc.rec.get(), sc.stage.get<double>(), merge_into, n, period, first_tick, n_samples, every, hs.ring,
-                                          h->elem_size(), h->stream.get());
-                if (e != hipSuccess) return h->hip_fail(e, "history_events capture");
-            }
-            return SIXDOF_OK;
-        });
+        [&](uint32_t segments, bool merge_into) {
+            return launch_history_events(a, static_cast<uint32_t>(n_triggers), sc.rec.get(), sc.stage.get<double>(), sc.scratch.get(), segments, merge_into,
+                                         h->desc.n_entities, period, first_tick, n_samples, every, hs.ring, h->elem_size(), h->stream.get());
+        },
+        [&] { return a; });
 } SIXDOF_ABI_CATCH(err_of(h))
 
 // The extremes of a squared vector length or separation per probe and run.  One walk (and merge) launch covers all probes, a unit
@@ -2018,30 +2059,17 @@ int sixdof_history_norms(sixdof_handle* h, const sixdof_norm_probe* probes, size
     return time_scan_read(
         h, spec, first_tick, n_samples, every, flags,
         [&](bool&) -> int {
-            if (n_probes == 0 || n_probes > SIXDOF_NORMS_MAX_PROBES)
-                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(n_probes) + " probes, 1 to " + std::to_string(SIXDOF_NORMS_MAX_PROBES) + " can be asked for");
-            if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
-            if (n % period != 0)
-                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
+            if (int rc = run_scan_checks(h, who, n_probes, "probes", SIXDOF_NORMS_MAX_PROBES, period); rc != SIXDOF_OK) return rc;
             if (!probes || (!hold && !host_dst)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
-            for (size_t k = 0; k < n_probes; k++) {
-                const sixdof_norm_probe& p = probes[k];
-                const std::string which = who + ": probe " + std::to_string(k);
-                if (int rc = norm_probe_resolve(h, which, p, period, a.p[k]); rc != SIXDOF_OK) return rc;
-            }
+            for (size_t k = 0; k < n_probes; k++)
+                if (int rc = norm_probe_resolve(h, who + ": probe " + std::to_string(k), probes[k], period, a.p[k]); rc != SIXDOF_OK) return rc;
             return SIXDOF_OK;
         },
         [&](StagedRead& rd, History::ScanState& next, std::vector<uint64_t>& units) -> int {
             units.push_back(n / period * n_probes);
             rd.add_block(hold ? nullptr : host_dst, static_cast<size_t>(units[0]) * kNormsPlanes * sizeof(double));
             next.signature = {n_probes, period};
-            for (uint32_t k = 0; k < np; k++) {
-                const sixdof_norm_probe& p = probes[k];
-                const bool minus = (p.flags & SIXDOF_NORM_MINUS) != 0;
-                next.signature.insert(next.signature.end(), {p.component_id, p.minus_component_id, p.element, p.minus_element, p.group, p.minus_group, p.count, p.flags});
-                next.rings.push_back(a.p[k].ring_a), next.widths.push_back(a.p[k].w_a);
-                if (minus) next.rings.push_back(a.p[k].ring_b), next.widths.push_back(a.p[k].w_b);
-            }
+            for (uint32_t k = 0; k < np; k++) norm_probe_sign(probes[k], a.p[k], next);
             return SIXDOF_OK;
         },
         [&](const StagedRead&, size_t, uint64_t, uint32_t segments, bool merge_into) -> int {
@@ -2051,10 +2079,8 @@ int sixdof_history_norms(sixdof_handle* h, const sixdof_norm_probe* probes, size
         });
 } SIXDOF_ABI_CATCH(err_of(h))
 
-// The first event of every run per trigger on a squared vector length or separation, and the rows of the captured components at
-// it: sixdof_history_events' shape with the probes of sixdof_history_norms.  One walk (and merge) launch covers all triggers, a unit
-// is one (trigger, run); the capture launches are the events' own, handed the triggers' modes (norm_events_capture_args).  The
-// accumulator is the record buffer together with the staging buffer, as for the events.
+// run_events_read on a squared vector length or separation: the probes of sixdof_history_norms, and the events' own capture launches
+// handed the triggers' modes (norm_events_capture_args).
 int sixdof_history_norm_events(sixdof_handle* h, const sixdof_norm_trigger* triggers, size_t n_triggers, const uint64_t* capture_ids,
                                size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                                double* event_dst, double* const capture_dst[], uint32_t flags) try {
@@ -2063,76 +2089,29 @@ int sixdof_history_norm_events(sixdof_handle* h, const sixdof_norm_trigger* trig
     History::TimeScan& sc = hs.norm_events;
     const TimeScanSpec spec{"history_norm_events", SIXDOF_NORM_EVENTS_ASYNC, SIXDOF_NORM_EVENTS_CONTINUE, SIXDOF_NORM_EVENTS_HOLD, "SIXDOF_NORM_EVENTS_CONTINUE",
                             "triggers, captures, period, rows and rings", "SIXDOF_NORM_EVENTS_SEGMENTS", norm_events_segments, kNormEventsFields, &sc};
-    const std::string who = spec.who;
-    const bool hold = (flags & SIXDOF_NORM_EVENTS_HOLD) != 0;
-    const uint64_t n = h->desc.n_entities;
     const uint32_t nt = static_cast<uint32_t>(n_triggers);
     NormEventsArgs a{};
-    return time_scan_read(
-        h, spec, first_tick, n_samples, every, flags,
-        [&](bool&) -> int {
-            if (n_triggers == 0 || n_triggers > SIXDOF_NORM_EVENTS_MAX_TRIGGERS)
-                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": " + std::to_string(n_triggers) + " triggers, 1 to " + std::to_string(SIXDOF_NORM_EVENTS_MAX_TRIGGERS) + " can be asked for");
-            if (period == 0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": period must be at least 1");
-            if (n % period != 0)
-                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": the " + std::to_string(n) + " rows are no multiple of period " + std::to_string(period));
-            if (!triggers || (n_captures && !capture_ids) || (!hold && (!event_dst || (n_captures && !capture_dst))))
-                return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
-            for (size_t k = 0; k < n_triggers; k++) {
-                const sixdof_norm_trigger& t = triggers[k];
-                const std::string which = who + ": trigger " + std::to_string(k);
-                if (t.op > SIXDOF_EVENT_GE) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown op " + std::to_string(t.op));
-                if (t.mode > SIXDOF_EVENT_CROSSING) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown mode " + std::to_string(t.mode));
-                if (!std::isfinite(t.level_sq) || t.level_sq < 0.0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": the squared level is not finite or is below 0");
-                if (int rc = norm_probe_resolve(h, which, t.probe, period, a.t[k].probe); rc != SIXDOF_OK) return rc;
-                a.t[k].level_sq = t.level_sq, a.t[k].op = t.op, a.t[k].mode = t.mode;
-            }
+    return run_events_read(
+        h, spec, SIXDOF_NORM_EVENTS_MAX_TRIGGERS, triggers, n_triggers, capture_ids, n_captures, period, first_tick, n_samples, every, event_dst, capture_dst, flags,
+        [&](size_t k, const std::string& which) -> int {
+            const sixdof_norm_trigger& t = triggers[k];
+            if (!std::isfinite(t.level_sq) || t.level_sq < 0.0) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": the squared level is not finite or is below 0");
+            if (int rc = norm_probe_resolve(h, which, t.probe, period, a.t[k].probe); rc != SIXDOF_OK) return rc;
+            a.t[k].level_sq = t.level_sq, a.t[k].op = t.op, a.t[k].mode = t.mode;
             return SIXDOF_OK;
         },
-        [&](StagedRead& rd, History::ScanState& next, std::vector<uint64_t>& units) -> int {
-            units.push_back(n / period * n_triggers);
-            rd.add_block(hold ? nullptr : event_dst, static_cast<size_t>(units[0]) * kNormEventsPlanes * sizeof(double));
-            next.signature = {n_triggers, period, n_captures};
-            for (uint32_t k = 0; k < nt; k++) {
-                const sixdof_norm_trigger& t = triggers[k];
-                const sixdof_norm_probe& p = t.probe;
-                uint64_t level;
-                std::memcpy(&level, &t.level_sq, sizeof(level));
-                next.signature.insert(next.signature.end(), {p.component_id, p.minus_component_id, p.element, p.minus_element, p.group, p.minus_group, p.count, p.flags,
-                                                             level, t.op, t.mode});
-                next.rings.push_back(a.t[k].probe.ring_a), next.widths.push_back(a.t[k].probe.w_a);
-                if (p.flags & SIXDOF_NORM_MINUS) next.rings.push_back(a.t[k].probe.ring_b), next.widths.push_back(a.t[k].probe.w_b);
-            }
-            for (size_t k = 0; k < n_captures; k++) {
-                const int rc = rd.add(capture_ids[k], hold ? nullptr : capture_dst[k], static_cast<size_t>(n) * n_triggers, sizeof(double), kOnlyRecorded, !hold);
-                if (rc != SIXDOF_OK) return rc;
-                next.signature.push_back(capture_ids[k]);
-                next.rings.push_back(rd.parts[1 + k].ring), next.widths.push_back(rd.parts[1 + k].w);
-            }
-            return SIXDOF_OK;
+        [&](size_t k, History::ScanState& next) {
+            const sixdof_norm_trigger& t = triggers[k];
+            uint64_t level;
+            std::memcpy(&level, &t.level_sq, sizeof(level));
+            norm_probe_sign(t.probe, a.t[k].probe, next);
+            next.signature.insert(next.signature.end(), {level, t.op, t.mode});
         },
-        [&](const StagedRead& rd, size_t, uint64_t units, uint32_t segments, bool merge_into) -> int {
-            if (events_record_bytes(units) > sc.rec.bytes()) {   // never for a continuing call: its records are as large as the accumulator's
-                HIP_TRY(h, hipStreamSynchronize(h->stream.get()));   // an earlier call's launches may still use the old buffer
-                HIP_TRY(h, sc.rec.alloc(static_cast<size_t>(events_record_bytes(units))));
-            }
-            hipError_t e = launch_history_norm_events(a, nt, sc.rec.get(), sc.stage.get<double>(), sc.scratch.get(), segments, merge_into, n, period, first_tick,
-                                                      n_samples, every, hs.ring, h->elem_size(), h->stream.get());
-            if (e != hipSuccess) return h->hip_fail(e, "history_norm_events");
-            const EventsArgs modes = norm_events_capture_args(a, nt);
-            for (size_t k0 = 0; k0 < n_captures; k0 += kRingBinMaxComponents) {
-                const uint32_t cnt = static_cast<uint32_t>(std::min<size_t>(kRingBinMaxComponents, n_captures - k0));
-                RingBinArgs c{};
-                for (uint32_t k = 0; k < cnt; k++) {
-                    const StagedRead::Part& p = rd.parts[1 + k0 + k];
-                    c.c[k].ring = p.ring, c.c[k].out_offset = p.offset / sizeof(double), c.c[k].w = static_cast<uint32_t>(p.w);
-                }
-                e = launch_events_capture(modes, nt, c, cnt, sc.rec.get(), sc.stage.get<double>(), merge_into, n, period, first_tick, n_samples, every, hs.ring,
-                                          h->elem_size(), h->stream.get());
-                if (e != hipSuccess) return h->hip_fail(e, "history_norm_events capture");
-            }
-            return SIXDOF_OK;
-        });
+        [&](uint32_t segments, bool merge_into) {
+            return launch_history_norm_events(a, nt, sc.rec.get(), sc.stage.get<double>(), sc.scratch.get(), segments, merge_into, h->desc.n_entities, period,
+                                              first_tick, n_samples, every, hs.ring, h->elem_size(), h->stream.get());
+        },
+        [&] { return norm_events_capture_args(a, nt); });
 } SIXDOF_ABI_CATCH(err_of(h))
 
 int sixdof_download_column(sixdof_handle* h, uint64_t component_id) try {

@@ -127,6 +127,17 @@ class _Reduction:
     to_dict: Callable       # (names, raw blocks) -> the dict handed to the caller
 
 
+@dataclass(frozen=True)
+class _Scan:
+    """One scan of the ring across time per run, as HipExec._scan and _stream_scan call it."""
+    fn: str                 # the library entry point
+    continue_flag: int
+    hold_flag: int
+    name: str               # history_<name> / stream_<name>, for the messages
+    captures: bool          # whether it takes a capture list and delivers its blocks
+    to_dict: Callable       # (capture names, raw block, capture blocks) -> the dict handed to the caller
+
+
 class HipExec:
     def __init__(self, world_pos, world_vel, inertia, *, world_accel=None, force=None, entity_ids=None,
                  simulation_time_step: float = 1.0 / 120.0, time_step: Optional[float] = None,
@@ -932,6 +943,45 @@ class HipExec:
             self.sync()
         return time.perf_counter() - t0
 
+    # ---- scans of the ring across time per run: events, norms and norm events -------------------------------------------
+    def _scan_buffers(self, scan: _Scan, n_items: int, capture, period: int):
+        """The raw block, the capture blocks, their pointers and the captured component ids, holding what a range without samples gives."""
+        if not scan.captures:
+            return self._norms_buffer(n_items, period), [], None, None
+        raw, caps, ptrs = self._events_buffers(n_items, capture, period)
+        return raw, caps, ptrs, np.array([L.component_id(n) for n in capture], dtype=np.uint64)
+
+    def _scan_read(self, scan: _Scan, items, comp, period: int, first_tick: int, n_samples: int, every: int, raw, ptrs, flags: int) -> None:
+        """One call of the scan's entry point for the ctypes array `items`; raw None: a held read, nothing is delivered."""
+        captures = (comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp)) if scan.captures else ()
+        rc = getattr(self._lib, scan.fn)(self._h, items, len(items), *captures, period, first_tick, n_samples, every,
+                                         None if raw is None else raw.ctypes.data, *((ptrs,) if scan.captures else ()), flags)
+        if rc != L.OK:
+            _raise(self._h, rc, scan.fn)
+
+    def _scan(self, scan: _Scan, items, capture, first_tick: int, last_tick: int, every: int, period: int) -> dict:
+        """One blocking read of the samples first_tick, first_tick + every, ... <= last_tick."""
+        capture = [capture] if isinstance(capture, str) else list(capture)
+        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
+        raw, caps, ptrs, comp = self._scan_buffers(scan, len(items), capture, period)
+        self._scan_read(scan, items, comp, max(period, 0), first_tick, self._sample_count(first_tick, last_tick, every), every, raw, ptrs, 0)
+        return scan.to_dict(capture, raw, caps)
+
+    def _stream_scan(self, scan: _Scan, items, capture, n_batches: int, ticks_per_batch: int, every: int, period: int, flags: int):
+        """Every batch's samples merged into the accumulator on the device, the last batch's call delivering (_stream_accumulate)."""
+        capture = [capture] if isinstance(capture, str) else list(capture)
+        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
+        n_samples = self._stream_shape(f"stream_{scan.name}", ticks_per_batch, every)
+        if n_batches < 1:
+            raise ValueError(f"stream_{scan.name}: at least one batch")
+        if period < 1:
+            raise ValueError(f"stream_{scan.name}: period must be at least 1")
+        raw, caps, ptrs, comp = self._scan_buffers(scan, len(items), capture, period)
+        wall = self._stream_accumulate(n_batches, ticks_per_batch, every, scan.continue_flag, scan.hold_flag, flags,
+                                       lambda first, last, fl: self._scan_read(scan, items, comp, period, first, n_samples, every, raw if last else None,
+                                                                               ptrs if last else None, fl))
+        return wall, scan.to_dict(capture, raw, caps)
+
     # ---- ring events: the first threshold crossing of every run, and the state there -----------------------------------
     EVENTS_FIELDS = ("tick", "value", "tick_before", "value_before")      # the four planes, in order
 
@@ -965,11 +1015,8 @@ class HipExec:
         caps = [np.full((n_events, self.n, self._recorded_width(name)), np.nan, dtype=np.float64) for name in capture]
         return raw, caps, (C.c_void_p * max(1, len(caps)))(*[a.ctypes.data for a in caps])
 
-    def _events_read(self, triggers, comp, period: int, first_tick: int, n_samples: int, every: int, raw, ptrs, flags: int) -> None:
-        rc = self._lib.sixdof_history_events(self._h, triggers, len(triggers), comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), period, first_tick,
-                                             n_samples, every, None if raw is None else raw.ctypes.data, ptrs, flags)
-        if rc != L.OK:
-            _raise(self._h, rc, "sixdof_history_events")
+    _EVENTS_SCAN = _Scan("sixdof_history_events", L.EVENTS_CONTINUE, L.EVENTS_HOLD, "events", True,
+                         lambda capture, raw, caps: HipExec._events_dict(capture, raw, caps))
 
     def history_events(self, events, capture: Sequence[str], first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> dict:
         """{"tick", "tick_before": int64 [T, runs]; "value", "value_before": f64 [T, runs]; "capture": {name: f64 [T, n, w]}}: per
@@ -978,13 +1025,7 @@ class HipExec:
         and value of the finite sample before — found on the device out of the ring.  capture[name][e, r] is row r of `name` at
         the event tick of r's run for event e.  tick 0 means no event: value and the run's captured rows are then NaN;
         tick_before 0 means no sample before it.  Non-finite samples are skipped.  Stateless: no watch is involved."""
-        triggers = self._event_triggers(events)
-        capture = [capture] if isinstance(capture, str) else list(capture)
-        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
-        raw, caps, ptrs = self._events_buffers(len(triggers), capture, period)
-        comp = np.array([L.component_id(n) for n in capture], dtype=np.uint64)
-        self._events_read(triggers, comp, max(period, 0), first_tick, self._sample_count(first_tick, last_tick, every), every, raw, ptrs, 0)
-        return self._events_dict(capture, raw, caps)
+        return self._scan(self._EVENTS_SCAN, self._event_triggers(events), capture, first_tick, last_tick, every, period)
 
     def stream_events(self, events, capture: Sequence[str], n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, flags: int = 0):
         """history_events over a run longer than the ring: n_batches batches of ticks_per_batch ticks are stepped, and after every
@@ -993,20 +1034,7 @@ class HipExec:
         event.  Nothing crosses the link until the last batch's call delivers.  The ring is read on the compute stream, so a ring
         one batch deep is enough (enabled here unless enable_history already made one at least that large).  Returns (wall time
         in seconds, the dict of history_events); whatever happens, the caller's flags are restored and the handle is drained."""
-        triggers = self._event_triggers(events)
-        capture = [capture] if isinstance(capture, str) else list(capture)
-        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
-        n_samples = self._stream_shape("stream_events", ticks_per_batch, every)
-        if n_batches < 1:
-            raise ValueError("stream_events: at least one batch")
-        if period < 1:
-            raise ValueError("stream_events: period must be at least 1")
-        raw, caps, ptrs = self._events_buffers(len(triggers), capture, period)
-        comp = np.array([L.component_id(n) for n in capture], dtype=np.uint64)
-        wall = self._stream_accumulate(n_batches, ticks_per_batch, every, L.EVENTS_CONTINUE, L.EVENTS_HOLD, flags,
-                                       lambda first, last, fl: self._events_read(triggers, comp, period, first, n_samples, every, raw if last else None,
-                                                                                 ptrs if last else None, fl))
-        return wall, self._events_dict(capture, raw, caps)
+        return self._stream_scan(self._EVENTS_SCAN, self._event_triggers(events), capture, n_batches, ticks_per_batch, every, period, flags)
 
     # ---- ring norms: per-run extremes of a vector's length or of a separation ---------------------------------------------
     NORMS_FIELDS = ("count", "min_sq", "argmin", "max_sq", "argmax", "first_nonfinite")      # the six planes, in order
@@ -1053,10 +1081,7 @@ class HipExec:
         raw[:, 1], raw[:, 3] = np.nan, np.nan
         return raw
 
-    def _norms_read(self, probes, period: int, first_tick: int, n_samples: int, every: int, raw, flags: int) -> None:
-        rc = self._lib.sixdof_history_norms(self._h, probes, len(probes), period, first_tick, n_samples, every, None if raw is None else raw.ctypes.data, flags)
-        if rc != L.OK:
-            _raise(self._h, rc, "sixdof_history_norms")
+    _NORMS_SCAN = _Scan("sixdof_history_norms", L.NORMS_CONTINUE, L.NORMS_HOLD, "norms", False, lambda capture, raw, caps: HipExec._norms_dict(raw))
 
     def history_norms(self, norms, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> dict:
         """{"count", "argmin", "argmax", "first_nonfinite": int64 [P, runs]; "min_sq", "max_sq", "min", "max": f64 [P, runs]}: per
@@ -1065,11 +1090,7 @@ class HipExec:
         the squared norm is finite and the earliest tick at which it is not — reduced on the device out of the ring.  The
         squared norm is formed in f64, left to right, from the ring's elements widened to double; one that overflows counts as
         non-finite.  0 in a tick field means none; count == 0 leaves the extremes NaN.  Stateless: no watch is involved."""
-        probes = self._norm_probes(norms)
-        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
-        raw = self._norms_buffer(len(probes), period)
-        self._norms_read(probes, max(period, 0), first_tick, self._sample_count(first_tick, last_tick, every), every, raw, 0)
-        return self._norms_dict(raw)
+        return self._scan(self._NORMS_SCAN, self._norm_probes(norms), (), first_tick, last_tick, every, period)
 
     def stream_norms(self, norms, n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, flags: int = 0):
         """history_norms over a run longer than the ring: n_batches batches of ticks_per_batch ticks are stepped, and after every
@@ -1078,17 +1099,7 @@ class HipExec:
         delivers.  The ring is read on the compute stream, so a ring one batch deep is enough (enabled here unless enable_history
         already made one at least that large).  Returns (wall time in seconds, the dict of history_norms); whatever happens, the
         caller's flags are restored and the handle is drained."""
-        probes = self._norm_probes(norms)
-        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
-        n_samples = self._stream_shape("stream_norms", ticks_per_batch, every)
-        if n_batches < 1:
-            raise ValueError("stream_norms: at least one batch")
-        if period < 1:
-            raise ValueError("stream_norms: period must be at least 1")
-        raw = self._norms_buffer(len(probes), period)
-        wall = self._stream_accumulate(n_batches, ticks_per_batch, every, L.NORMS_CONTINUE, L.NORMS_HOLD, flags,
-                                       lambda first, last, fl: self._norms_read(probes, period, first, n_samples, every, raw if last else None, fl))
-        return wall, self._norms_dict(raw)
+        return self._stream_scan(self._NORMS_SCAN, self._norm_probes(norms), (), n_batches, ticks_per_batch, every, period, flags)
 
     # ---- ring norm events: the first crossing of a vector's length or of a separation per run, and the state there ------------
     NORM_EVENTS_FIELDS = ("tick", "value_sq", "tick_before", "value_before_sq")      # the four planes, in order
@@ -1121,11 +1132,8 @@ class HipExec:
             t.level_sq, t.op, t.mode = level * level, Event.OPS[e.op], Event.MODES[e.mode]
         return arr
 
-    def _norm_events_read(self, triggers, comp, period: int, first_tick: int, n_samples: int, every: int, raw, ptrs, flags: int) -> None:
-        rc = self._lib.sixdof_history_norm_events(self._h, triggers, len(triggers), comp.ctypes.data_as(C.POINTER(C.c_uint64)), len(comp), period,
-                                                  first_tick, n_samples, every, None if raw is None else raw.ctypes.data, ptrs, flags)
-        if rc != L.OK:
-            _raise(self._h, rc, "sixdof_history_norm_events")
+    _NORM_EVENTS_SCAN = _Scan("sixdof_history_norm_events", L.NORM_EVENTS_CONTINUE, L.NORM_EVENTS_HOLD, "norm_events", True,
+                              lambda capture, raw, caps: HipExec._norm_events_dict(capture, raw, caps))
 
     def history_norm_events(self, events, capture: Sequence[str], first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> dict:
         """{"tick", "tick_before": int64 [T, runs]; "value_sq", "value_before_sq", "value", "value_before": f64 [T, runs]; "capture":
@@ -1135,13 +1143,7 @@ class HipExec:
         history_norms' (f64, left to right); one that is not finite, an overflowing one included, is skipped.  capture[name][e, r]
         is row r of `name` at the event tick of r's run for event e.  tick 0 means no event: the values and the run's captured rows
         are then NaN; tick_before 0 means no sample before it.  Stateless: no watch is involved."""
-        triggers = self._norm_triggers(events)
-        capture = [capture] if isinstance(capture, str) else list(capture)
-        first_tick, last_tick, every, period = int(first_tick), int(last_tick), int(every), int(period)
-        raw, caps, ptrs = self._events_buffers(len(triggers), capture, period)
-        comp = np.array([L.component_id(n) for n in capture], dtype=np.uint64)
-        self._norm_events_read(triggers, comp, max(period, 0), first_tick, self._sample_count(first_tick, last_tick, every), every, raw, ptrs, 0)
-        return self._norm_events_dict(capture, raw, caps)
+        return self._scan(self._NORM_EVENTS_SCAN, self._norm_triggers(events), capture, first_tick, last_tick, every, period)
 
     def stream_norm_events(self, events, capture: Sequence[str], n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, flags: int = 0):
         """history_norm_events over a run longer than the ring: n_batches batches of ticks_per_batch ticks are stepped, and after
@@ -1150,20 +1152,7 @@ class HipExec:
         batch that sees its event.  Nothing crosses the link until the last batch's call delivers.  A ring one batch deep is
         enough (enabled here unless enable_history already made one at least that large).  Returns (wall time in seconds, the
         dict of history_norm_events); whatever happens, the caller's flags are restored and the handle is drained."""
-        triggers = self._norm_triggers(events)
-        capture = [capture] if isinstance(capture, str) else list(capture)
-        n_batches, ticks_per_batch, every, period = int(n_batches), int(ticks_per_batch), int(every), int(period)
-        n_samples = self._stream_shape("stream_norm_events", ticks_per_batch, every)
-        if n_batches < 1:
-            raise ValueError("stream_norm_events: at least one batch")
-        if period < 1:
-            raise ValueError("stream_norm_events: period must be at least 1")
-        raw, caps, ptrs = self._events_buffers(len(triggers), capture, period)
-        comp = np.array([L.component_id(n) for n in capture], dtype=np.uint64)
-        wall = self._stream_accumulate(n_batches, ticks_per_batch, every, L.NORM_EVENTS_CONTINUE, L.NORM_EVENTS_HOLD, flags,
-                                       lambda first, last, fl: self._norm_events_read(triggers, comp, period, first, n_samples, every, raw if last else None,
-                                                                                      ptrs if last else None, fl))
-        return wall, self._norm_events_dict(capture, raw, caps)
+        return self._stream_scan(self._NORM_EVENTS_SCAN, self._norm_triggers(events), capture, n_batches, ticks_per_batch, every, period, flags)
 
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))

@@ -341,15 +341,18 @@ class Campaign:
         out = self.exec.history_extremes(components, first_tick, last_tick, every)
         return {comp: {k: v.reshape(self.n_runs, self.entities_per_run, v.shape[-1]) for k, v in d.items()} for comp, d in out.items()}
 
+    def _captures_by_run(self, out: Dict[str, Any]) -> Dict[str, Any]:
+        """`out` with every captured [event, row, w] block as [event, run, entity-of-run, w]."""
+        out["capture"] = {comp: v.reshape(v.shape[0], self.n_runs, self.entities_per_run, v.shape[-1]) for comp, v in out["capture"].items()}
+        return out
+
     def events(self, events, capture, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
         """When each run reached a condition and its state there, out of the device ring (self.exec.enable_history): the dict of
         Exec.history_events with a run = entities_per_run consecutive rows — "tick", "tick_before", "value", "value_before", "t",
         "t_before", "t_cross": [event, run]; "capture": {component: [event, run, entity-of-run, w]}, every entity of a run taken at
         that run's own event tick (NaN where the run has none).  An Event's `group` is the entity of the run it watches: touchdown,
         apogee, burn-out per run, and the landing dispersion of a campaign in one read."""
-        out = self.exec.history_events(events, capture, first_tick, last_tick, every, period=self.entities_per_run)
-        out["capture"] = {comp: v.reshape(v.shape[0], self.n_runs, self.entities_per_run, v.shape[-1]) for comp, v in out["capture"].items()}
-        return out
+        return self._captures_by_run(self.exec.history_events(events, capture, first_tick, last_tick, every, period=self.entities_per_run))
 
     def norms(self, norms, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
         """Per-run extremes of a vector's length or of a separation, out of the device ring (self.exec.enable_history): the dict of
@@ -364,9 +367,7 @@ class Campaign:
         "tick", "tick_before", "value_sq", "value_before_sq", "value", "value_before", "t", "t_before", "t_cross": [event, run];
         "capture": {component: [event, run, entity-of-run, w]}, every entity of a run taken at that run's own event tick (NaN where
         the run has none).  A Norm's `group` (and minus_group) is the entity of the run it reads."""
-        out = self.exec.history_norm_events(events, capture, first_tick, last_tick, every, period=self.entities_per_run)
-        out["capture"] = {comp: v.reshape(v.shape[0], self.n_runs, self.entities_per_run, v.shape[-1]) for comp, v in out["capture"].items()}
-        return out
+        return self._captures_by_run(self.exec.history_norm_events(events, capture, first_tick, last_tick, every, period=self.entities_per_run))
 
     def result_table(self, names: Sequence[str]) -> np.ndarray:
         """The runs' `el.monte_carlo.result(...)` records as [n_runs, len(names)] (NaN where a run reported nothing)."""

@@ -81,7 +81,7 @@ def _held_events(ex):
     comp = np.array([L.component_id(c) for c in CAPTURE], dtype=np.uint64)
 
     def call():
-        ex._events_read(trig, comp, 1, 1, READ_TICKS, 1, None, None, L.EVENTS_HOLD)
+        ex._scan_read(ex._EVENTS_SCAN, trig, comp, 1, 1, READ_TICKS, 1, None, None, L.EVENTS_HOLD)
         ex.sync()
     return call
 

@@ -103,7 +103,7 @@ def _held_norms(ex, which):
     probes = ex._norm_probes(_norm(which))
 
     def call():
-        ex._norms_read(probes, PERIOD, 1, READ_TICKS, 1, None, L.NORMS_HOLD)
+        ex._scan_read(ex._NORMS_SCAN, probes, None, PERIOD, 1, READ_TICKS, 1, None, None, L.NORMS_HOLD)
         ex.sync()
     return call
 
@@ -115,7 +115,7 @@ def _held_norm_events(ex, event):
     comp = np.array([], dtype=np.uint64)
 
     def call():
-        ex._norm_events_read(trig, comp, PERIOD, 1, READ_TICKS, 1, None, None, L.NORM_EVENTS_HOLD)
+        ex._scan_read(ex._NORM_EVENTS_SCAN, trig, comp, PERIOD, 1, READ_TICKS, 1, None, None, L.NORM_EVENTS_HOLD)
         ex.sync()
     return call
 

@@ -86,7 +86,7 @@ def _held_norms(ex, which):
     probes = ex._norm_probes(_norm(which))
 
     def call():
-        ex._norms_read(probes, PERIOD, 1, READ_TICKS, 1, None, L.NORMS_HOLD)
+        ex._scan_read(ex._NORMS_SCAN, probes, None, PERIOD, 1, READ_TICKS, 1, None, None, L.NORMS_HOLD)
         ex.sync()
     return call
 
@@ -98,7 +98,7 @@ def _held_events(ex, which):
     comp = np.array([], dtype=np.uint64)
 
     def call():
-        ex._events_read(trig, comp, PERIOD, 1, READ_TICKS, 1, None, None, L.EVENTS_HOLD)
+        ex._scan_read(ex._EVENTS_SCAN, trig, comp, PERIOD, 1, READ_TICKS, 1, None, None, L.EVENTS_HOLD)
         ex.sync()
     return call
 
