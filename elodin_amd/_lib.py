@@ -44,6 +44,11 @@ NORMS_MAX_PROBES = 8      # probes one call walks (SIXDOF_NORMS_MAX_PROBES)
 NORM_EVENTS_ASYNC, NORM_EVENTS_CONTINUE, NORM_EVENTS_HOLD = 1, 2, 4   # sixdof_history_norm_events flags
 NORM_EVENTS_PLANES = 4    # tick, value_sq, tick_before, value_before_sq (SIXDOF_NORM_EVENTS_PLANES)
 NORM_EVENTS_MAX_TRIGGERS = 8   # triggers one call walks (SIXDOF_NORM_EVENTS_MAX_TRIGGERS)
+DWELL_ELEMENT, DWELL_NORM_SQ = 0, 1                   # sixdof_dwell_condition.kind
+DWELL_INSIDE, DWELL_OUTSIDE = 4, 5                    # sixdof_dwell_condition.op, after EVENT_LT .. EVENT_GE
+DWELL_ASYNC, DWELL_CONTINUE, DWELL_HOLD = 1, 2, 4     # sixdof_history_dwell flags
+DWELL_PLANES = 12         # count, held, entries, first_held, last_held, prefix_len, prefix_end, suffix_len, suffix_start, longest_len, longest_start, longest_end
+DWELL_MAX_CONDITIONS = 8  # conditions one call walks (SIXDOF_DWELL_MAX_CONDITIONS)
 COVARIANCE_ASYNC = 1      # sixdof_history_covariance flags
 COVARIANCE_MAX_CHANNELS = 6   # channels one call reduces jointly (SIXDOF_COVARIANCE_MAX_CHANNELS)
 COVARIANCE_MAX_PERIOD = 256   # groups one call keeps apart (csrc/covariance_plan.hpp: kCovarianceMaxPeriod)
@@ -99,6 +104,10 @@ class NormProbe(C.Structure):   # sixdof_norm_probe, 40 bytes
 
 class NormTrigger(C.Structure):   # sixdof_norm_trigger, 56 bytes
     _fields_ = [("probe", NormProbe), ("level_sq", C.c_double), ("op", C.c_uint32), ("mode", C.c_uint32)]
+
+
+class DwellCondition(C.Structure):   # sixdof_dwell_condition, 64 bytes
+    _fields_ = [("probe", NormProbe), ("lo", C.c_double), ("hi", C.c_double), ("kind", C.c_uint32), ("op", C.c_uint32)]
 
 
 class CovChannel(C.Structure):   # sixdof_cov_channel, 16 bytes
@@ -188,6 +197,7 @@ SYMBOLS = {
     "sixdof_history_events": (C.c_int, [_H, C.POINTER(EventTrigger), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64,
                                         C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_history_norms": (C.c_int, [_H, C.POINTER(NormProbe), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32]),
+    "sixdof_history_dwell": (C.c_int, [_H, C.POINTER(DwellCondition), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32]),
     "sixdof_history_norm_events": (C.c_int, [_H, C.POINTER(NormTrigger), C.c_size_t, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64,
                                              C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32]),
     "sixdof_history_covariance": (C.c_int, [_H, C.POINTER(CovChannel), C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,

@@ -939,6 +939,27 @@ class Exec:
         (first, last, step), _ = self._sampled_ticks("history_norm_events", first_tick, last_tick, every)
         return self._event_times(evs, dict(self._hip.history_norm_events(evs, caps, first, last, step, period)))
 
+    def history_dwell(self, conditions, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> Dict[str, Any]:
+        """How long and how often each run met a condition: {"count", "held", "entries", "first_held", "last_held", "longest",
+        "longest_start", "longest_end": int64 [D, runs]; "open_at_start", "open_at_end": bool [D, runs]; "fraction", "t_held",
+        "t_longest", "t_first_held", "t_last_held", "t_longest_start", "t_longest_end": f64 [D, runs]} for the D conditions
+        (elodin_amd.Dwell) over world ticks first_tick, first_tick + every, ... <= last_tick, counted on the device out of the ring
+        (enable_history) — time above a load limit, excursions out of a corridor and whether the run ended outside, time inside a
+        keep-out sphere, the longest unbroken stretch above a tumble limit and when it began, the share of a flight in an altitude
+        band.  A run is `period` consecutive executor rows.  count, held and longest are samples, entries stretches of consecutive
+        held samples; a non-finite sample is skipped and a stretch continues across it.  t_held and t_longest are held and longest
+        in seconds (samples x every x the world's time step); the tick fields are world ticks, 0 means none, and the matching t_*
+        (seconds) is NaN."""
+        conds = [conditions] if not isinstance(conditions, (list, tuple)) else list(conditions)
+        for comp in [c for d in conds for c in (getattr(d.of, "component", None), getattr(d.of, "minus", None)) if c is not None]:
+            self._refuse_unrecorded("history_dwell", comp, comp)
+        (first, last, step), _ = self._sampled_ticks("history_dwell", first_tick, last_tick, every)
+        out: Dict[str, Any] = dict(self._hip.history_dwell(conds, first, last, step, period))
+        sample_seconds = float(int(every)) * self._dt
+        out["t_held"], out["t_longest"] = out["held"] * sample_seconds, out["longest"] * sample_seconds
+        return self._world_ticks(out, (("first_held", "t_first_held"), ("last_held", "t_last_held"), ("longest_start", "t_longest_start"),
+                                       ("longest_end", "t_longest_end")))
+
     def _world_ticks(self, out: Dict[str, Any], fields) -> Dict[str, Any]:
         """`out` with every (tick field, seconds field) pair of `fields` filled in: the executor's ticks as world ticks, and their
         time in seconds, NaN where the tick is 0 (none)."""

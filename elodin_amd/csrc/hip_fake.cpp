@@ -43,6 +43,7 @@
 #include "envelope_plan.hpp"
 #include "events_plan.hpp"
 #include "norms_plan.hpp"
+#include "dwell_plan.hpp"
 #include "norm_events_plan.hpp"
 #include "extremes_plan.hpp"
 #include "history_plan.hpp"
@@ -711,7 +712,7 @@ hipError_t launch_history_quantiles(const RingBinArgs& a, uint32_t n_components,
         else quantiles_of_tick<float>(src, n, d.w, period, ranks, h, st, to);
     }));
 }
-// ---- the scans over time: the walk and the merge themselves (extremes_, events_, norms_ and norm_events_kernels.hip), serially ----
+// ---- the scans over time: the walk and the merge themselves (extremes_, events_, norms_, norm_events_ and dwell_kernels.hip), serially ----
 // The two stages of a scan launch in the kernels' segmentation (time_scan.hpp) for `units` units: walk(unit, lo, hi, start) -> record
 // is the kernel's own walk over the samples [lo, hi); slot(segment, unit) is the unit's record in scratch, its fields `stride`
 // apart — with more than one segment every (segment, unit) record goes through the launch's scratch, as on the device.  Record,
@@ -755,6 +756,23 @@ struct PlanesAcc {
 };
 template <class E, class At>
 static PlanesAcc<E, At> planes_acc(uint64_t stride, At at) { return {stride, at}; }
+// The accumulator in the output planes, under dwell_plan.hpp's rule (the dwell): at(unit) is the unit's first plane, the twelve
+// planes `stride` apart.  A continuing one-segment walk starts empty and is merged behind what the planes hold.
+template <class At>
+struct DwellPlanesAcc {
+    using Record = DwellRecord;
+    static constexpr bool kWalksOn = false;
+    uint64_t stride;
+    At at;
+    static Record empty() { return dwell_empty(); }
+    static Record merge(const Record& earlier, const Record& later) { return dwell_merge(earlier, later); }
+    static void store(const Record& r, uint64_t* base, uint64_t s) { dwell_store(r, base, s); }
+    static Record load(const uint64_t* base, uint64_t s) { return dwell_load(base, s); }
+    Record held(uint64_t u) const { return dwell_absorb(at(u), stride); }
+    void emit(const Record& r, uint64_t u) const { dwell_emit(r, at(u), stride); }
+};
+template <class At>
+static DwellPlanesAcc<At> dwell_planes_acc(uint64_t stride, At at) { return {stride, at}; }
 // The accumulator in a record buffer, under events_plan.hpp's rule (the events, the norm events): mine(unit) is the unit's record,
 // at(unit) its first output plane of E, both `runs` apart.  A continuing one-segment walk starts FROM the record, as the kernels do.
 template <class E, class Mine, class At>
@@ -933,6 +951,30 @@ hipError_t launch_history_norm_events(const NormEventsArgs& a, uint32_t n_trigge
                         runs, runs, segments, merge_into, n_samples,
                         [&](uint64_t run, uint64_t lo, uint64_t hi, const EventsRecord& start) { return norm_events_walk<E>(start, t, run, n, period, lo, hi, first_tick, every, ring); },
                         [&](uint32_t seg, uint64_t run) { return static_cast<uint64_t*>(scratch) + norm_events_scratch_index(seg, n_triggers, k, runs, run); });
+        });
+    }
+    return launch(true);
+}
+// dwell_plan.hpp's value, walk (dwell_walk, the function the kernel calls) and rule; a unit is one run of a condition
+hipError_t launch_history_dwell(const DwellArgs& a, uint32_t n_conditions, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n, uint32_t period,
+                                uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s) {
+    if (deferring())
+        return defer_scan(s, "history_dwell", {out, scratch}, n_conditions, kDwellMaxConditions, [&](uint32_t c, auto& dev) { probe_rings(a.c[c].probe, dev); }, [=] {
+            return launch_history_dwell(a, n_conditions, out, scratch, segments, merge_into, n, period, first_tick, n_samples, every, ring, elem, s);
+        });
+    if (!dwell_launch_ok(a, n_conditions, n, period, first_tick, n_samples, every, segments) || ring == 0) return launch(false);
+    if (n == 0) return launch(true);
+    const uint64_t runs = n / period, units = runs * n_conditions;
+    if (segments > 1 && !need(live(scratch, scan_scratch_bytes(segments, units, kDwellFields)), "dwell scratch records")) return launch(false);
+    if (!need(live(out, units * kDwellPlanes * sizeof(double)), "dwell staging")) return launch(false);
+    for (uint32_t k = 0; k < n_conditions; k++) {
+        const DwellCondition& c = a.c[k];
+        if (!need(probe_live(c.probe, ring, n, elem), "ring of a condition's probe")) return launch(false);
+        with_elem(elem, [&](auto e) {
+            using E = decltype(e);
+            scan_stages(dwell_planes_acc(runs, [&](uint64_t run) { return out + dwell_out_index(k, runs, run); }), runs, runs, segments, merge_into, n_samples,
+                        [&](uint64_t run, uint64_t lo, uint64_t hi, const DwellRecord& start) { return dwell_walk<E>(start, c, run, n, period, lo, hi, first_tick, every, ring); },
+                        [&](uint32_t seg, uint64_t run) { return static_cast<uint64_t*>(scratch) + dwell_scratch_index(seg, n_conditions, k, runs, run); });
         });
     }
     return launch(true);

@@ -240,6 +240,15 @@ hipError_t launch_history_norm_events(const NormEventsArgs& a, uint32_t n_trigge
                                       uint64_t n, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem,
                                       hipStream_t s);
 
+// ---- ring dwell: per condition and run, how long and how often a predicate held over the sampled ticks (dwell_kernels.hip) ---
+struct DwellArgs;   // dwell_plan.hpp: the conditions (a norms probe, kind, op, lo, hi) of one launch, at most 8
+// All n_samples samples of the range first_tick, first_tick + every, ... in `segments` time segments (dwell_plan.hpp).  `out`: the
+// twelve planes, [n_conditions][12][runs] doubles with runs = n / period, read first when merge_into (they then hold the samples
+// before this range, and the result covers both); with more than one segment `scratch` holds segments * n_conditions * 12 * runs
+// 64-bit words.  The caller has validated the range (sampled_range_ok, scan_ticks_ok) and the conditions (dwell_launch_ok).
+hipError_t launch_history_dwell(const DwellArgs& a, uint32_t n_conditions, double* out, void* scratch, uint32_t segments, bool merge_into, uint64_t n,
+                                uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every, uint64_t ring, size_t elem, hipStream_t s);
+
 // ---- ring covariances: count, mean vector and co-moment matrix of k channels across the rows of every sampled tick (covariance_kernels.hip) ---
 constexpr uint32_t kCovarianceArgChannels = 6;   // covariance_plan.hpp: kCovarianceMaxChannels
 struct CovarianceChannel {

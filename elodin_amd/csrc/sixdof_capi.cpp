@@ -34,6 +34,7 @@
 #include "envelope_plan.hpp"
 #include "events_plan.hpp"
 #include "norms_plan.hpp"
+#include "dwell_plan.hpp"
 #include "norm_events_plan.hpp"
 #include "extremes_plan.hpp"
 #include "quantile_plan.hpp"
@@ -165,7 +166,7 @@ struct History {
     DeviceBuffer quant_stage, quant_scratch;
     // sixdof_history_covariance: its staging and the stage-1 partial records of one launch; the same rules
     DeviceBuffer cov_stage, cov_partial;
-    // A scan over time (time_scan_read: sixdof_history_extremes, sixdof_history_events, sixdof_history_norms, sixdof_history_norm_events): its staging, which is also the accumulator
+    // A scan over time (time_scan_read: sixdof_history_extremes, sixdof_history_events, sixdof_history_norms, sixdof_history_norm_events, sixdof_history_dwell): its staging, which is also the accumulator
     // a *_CONTINUE call merges into, the segment records of one launch and — the two event readers only — the records its rule continues
     // from; the same rules.  `acc` says what the accumulator holds, if anything.
     struct ScanState {
@@ -179,7 +180,7 @@ struct History {
     struct TimeScan {
         DeviceBuffer stage, scratch, rec;
         ScanState acc;
-    } extremes, events, norms, norm_events;
+    } extremes, events, norms, norm_events, dwell;
     void reset() { *this = History{}; }
 };
 
@@ -516,7 +517,7 @@ void sixdof_destroy(sixdof_handle* h) try {
 int sixdof_bind_columns(sixdof_handle* h, const sixdof_column* cols, size_t n_cols) try {
     if (!h || (!cols && n_cols)) return SIXDOF_ERR_INVALID_ARGUMENT;
     h->bound = h->resident = false;   // until the end of this call: a failed bind leaves the handle unbound
-    h->hist.extremes.acc.valid = h->hist.events.acc.valid = h->hist.norms.acc.valid = h->hist.norm_events.acc.valid = false;   // the rows a scan's accumulator covers may be other rows from here on
+    h->hist.extremes.acc.valid = h->hist.events.acc.valid = h->hist.norms.acc.valid = h->hist.norm_events.acc.valid = h->hist.dwell.acc.valid = false;   // the rows a scan's accumulator covers may be other rows from here on
     HIP_TRY(h, hipSetDevice(h->device));
     h->replay.drop();
     if (h->d_watch_rows) {      // a watch holds rows of the join this call replaces
@@ -1766,7 +1767,7 @@ int sixdof_history_covariance(sixdof_handle* h, const sixdof_cov_channel* channe
 
 }  // extern "C"
 
-// A scan of the ring over time: sixdof_history_extremes, sixdof_history_events, sixdof_history_norms and sixdof_history_norm_events.  Ordering, ring reads and the copy lane exactly
+// A scan of the ring over time: sixdof_history_extremes, sixdof_history_events, sixdof_history_norms, sixdof_history_norm_events and sixdof_history_dwell.  Ordering, ring reads and the copy lane exactly
 // as for sixdof_watch_read above; not through ring_bin_read, whose output and chunk rule are per sample: here ALL samples of the
 // range go into one launch, cut into time segments (time_scan.hpp), and the output is per row or run.  The staging buffer is the
 // accumulator: a call with `continues` merges into what the previous call left there, a call with `holds` delivers nothing.
@@ -1842,7 +1843,7 @@ static int time_scan_read(sixdof_handle* h, const TimeScanSpec& spec, uint64_t f
 
 static const char* const kOnlyRecorded = "only world_pos / world_vel / world_accel / force and the non-window component columns of a generated program are recorded";
 
-// One probe of sixdof_history_norms or sixdof_history_norm_events, checked against the ring and resolved into what the kernels
+// One probe of sixdof_history_norms, sixdof_history_norm_events or sixdof_history_dwell, checked against the ring and resolved into what the kernels
 // see; `which` names it in the messages.
 static int norm_probe_resolve(sixdof_handle* h, const std::string& which, const sixdof_norm_probe& p, uint32_t period, NormsProbe& d) {
     if (p.flags & ~SIXDOF_NORM_MINUS) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": unknown flags " + std::to_string(p.flags));
@@ -1875,7 +1876,7 @@ static void norm_probe_sign(const sixdof_norm_probe& p, const NormsProbe& d, His
     if (p.flags & SIXDOF_NORM_MINUS) next.rings.push_back(d.ring_b), next.widths.push_back(d.w_b);
 }
 
-// The refusals of every scan per run (sixdof_history_events, sixdof_history_norms, sixdof_history_norm_events), the first of its own
+// The refusals of every scan per run (sixdof_history_events, sixdof_history_norms, sixdof_history_norm_events, sixdof_history_dwell), the first of its own
 // checks: `count` of its `noun` outside 1 .. max, no period, rows that are no whole runs.
 static int run_scan_checks(sixdof_handle* h, const std::string& who, size_t count, const char* noun, size_t max, uint32_t period) {
     const uint64_t n = h->desc.n_entities;
@@ -2112,6 +2113,55 @@ int sixdof_history_norm_events(sixdof_handle* h, const sixdof_norm_trigger* trig
                                               first_tick, n_samples, every, hs.ring, h->elem_size(), h->stream.get());
         },
         [&] { return norm_events_capture_args(a, nt); });
+} SIXDOF_ABI_CATCH(err_of(h))
+
+// How long and how often a predicate on an element, a difference or a squared vector length held, per condition and run.  One walk
+// (and merge) launch covers all conditions, a unit is one (condition, run); the accumulator is the staging buffer, as for the norms.
+int sixdof_history_dwell(sixdof_handle* h, const sixdof_dwell_condition* conditions, size_t n_conditions, uint32_t period, uint64_t first_tick,
+                         uint64_t n_samples, uint64_t every, double* host_dst, uint32_t flags) try {
+    if (!h) return SIXDOF_ERR_INVALID_ARGUMENT;
+    History& hs = h->hist;
+    History::TimeScan& sc = hs.dwell;
+    const TimeScanSpec spec{"history_dwell", SIXDOF_DWELL_ASYNC, SIXDOF_DWELL_CONTINUE, SIXDOF_DWELL_HOLD, "SIXDOF_DWELL_CONTINUE",
+                            "conditions, period, rows and rings", "SIXDOF_DWELL_SEGMENTS", dwell_segments, kDwellFields, &sc};
+    const std::string who = spec.who;
+    const bool hold = (flags & SIXDOF_DWELL_HOLD) != 0;
+    const uint64_t n = h->desc.n_entities;
+    const uint32_t nc = static_cast<uint32_t>(n_conditions);
+    DwellArgs a{};
+    return time_scan_read(
+        h, spec, first_tick, n_samples, every, flags,
+        [&](bool&) -> int {
+            if (int rc = run_scan_checks(h, who, n_conditions, "conditions", SIXDOF_DWELL_MAX_CONDITIONS, period); rc != SIXDOF_OK) return rc;
+            if (!conditions || (!hold && !host_dst)) return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, who + ": null argument");
+            for (size_t k = 0; k < n_conditions; k++) {
+                const sixdof_dwell_condition& c = conditions[k];
+                const std::string which = who + ": condition " + std::to_string(k);
+                if (int rc = norm_probe_resolve(h, which, c.probe, period, a.c[k].probe); rc != SIXDOF_OK) return rc;
+                if (const char* fault = dwell_condition_fault(c.kind, c.op, c.probe.count, c.lo, c.hi))
+                    return h->fail(SIXDOF_ERR_INVALID_ARGUMENT, which + ": " + fault + " (kind " + std::to_string(c.kind) + ", op " + std::to_string(c.op) + ")");
+                a.c[k].lo = c.lo, a.c[k].hi = c.hi, a.c[k].kind = c.kind, a.c[k].op = c.op;
+            }
+            return SIXDOF_OK;
+        },
+        [&](StagedRead& rd, History::ScanState& next, std::vector<uint64_t>& units) -> int {
+            units.push_back(n / period * n_conditions);
+            rd.add_block(hold ? nullptr : host_dst, static_cast<size_t>(units[0]) * kDwellPlanes * sizeof(double));
+            next.signature = {n_conditions, period};
+            for (uint32_t k = 0; k < nc; k++) {
+                const sixdof_dwell_condition& c = conditions[k];
+                uint64_t lo, hi;
+                std::memcpy(&lo, &c.lo, sizeof(lo)), std::memcpy(&hi, &c.hi, sizeof(hi));
+                norm_probe_sign(c.probe, a.c[k].probe, next);
+                next.signature.insert(next.signature.end(), {c.kind, c.op, lo, hi});
+            }
+            return SIXDOF_OK;
+        },
+        [&](const StagedRead&, size_t, uint64_t, uint32_t segments, bool merge_into) -> int {
+            hipError_t e = launch_history_dwell(a, nc, sc.stage.get<double>(), sc.scratch.get(), segments, merge_into, n, period, first_tick, n_samples, every, hs.ring,
+                                                h->elem_size(), h->stream.get());
+            return e == hipSuccess ? int(SIXDOF_OK) : h->hip_fail(e, "history_dwell");
+        });
 } SIXDOF_ABI_CATCH(err_of(h))
 
 int sixdof_download_column(sixdof_handle* h, uint64_t component_id) try {

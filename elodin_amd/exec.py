@@ -94,6 +94,32 @@ class NormEvent:
     mode: str = "crossing"
 
 
+@dataclass(frozen=True)
+class Element:
+    """The signed scalar a Dwell looks at: element `element` of `component` in row `group` of every run or, with `minus` (a
+    component name, which may be the same), its difference to element minus_element of `minus` in row minus_group — an altitude, a
+    load factor, a cross-track error between two entities of a run.  minus_element and minus_group default to element and group."""
+    component: str
+    element: int
+    group: int = 0
+    minus: Optional[str] = None
+    minus_element: Optional[int] = None
+    minus_group: Optional[int] = None
+
+
+@dataclass(frozen=True)
+class Dwell:
+    """One condition of HipExec.history_dwell: `of` (an Element or a Norm) meets `op level`, or lies inside / outside the closed
+    band [level, upper].  Levels are in the units of `of`; for a Norm they are finite, not negative, and squared on the host: the
+    device compares squared norm and squared level."""
+    of: object              # an Element or a Norm
+    op: str                 # "<", "<=", ">", ">=", "inside" or "outside"
+    level: float
+    upper: Optional[float] = None   # the band's upper level: "inside" and "outside" only
+
+    OPS = {**Event.OPS, "inside": L.DWELL_INSIDE, "outside": L.DWELL_OUTSIDE}
+
+
 def dispersion_ellipse(cov2, prob: float = 0.99):
     """(semi_major, semi_minor, angle) of the ellipse that holds the share `prob` of a bivariate normal population with the
     2 x 2 covariance `cov2` — the landing footprint out of the x / y block of HipExec.history_covariance's "cov".  Closed-form
@@ -136,6 +162,7 @@ class _Scan:
     name: str               # history_<name> / stream_<name>, for the messages
     captures: bool          # whether it takes a capture list and delivers its blocks
     to_dict: Callable       # (capture names, raw block, capture blocks) -> the dict handed to the caller
+    buffer: Optional[Callable] = None   # a scan without captures: (executor, items, period) -> its raw block; None: the norms'
 
 
 class HipExec:
@@ -947,7 +974,7 @@ class HipExec:
     def _scan_buffers(self, scan: _Scan, n_items: int, capture, period: int):
         """The raw block, the capture blocks, their pointers and the captured component ids, holding what a range without samples gives."""
         if not scan.captures:
-            return self._norms_buffer(n_items, period), [], None, None
+            return (scan.buffer or HipExec._norms_buffer)(self, n_items, period), [], None, None
         raw, caps, ptrs = self._events_buffers(n_items, capture, period)
         return raw, caps, ptrs, np.array([L.component_id(n) for n in capture], dtype=np.uint64)
 
@@ -1153,6 +1180,79 @@ class HipExec:
         enough (enabled here unless enable_history already made one at least that large).  Returns (wall time in seconds, the
         dict of history_norm_events); whatever happens, the caller's flags are restored and the handle is drained."""
         return self._stream_scan(self._NORM_EVENTS_SCAN, self._norm_triggers(events), capture, n_batches, ticks_per_batch, every, period, flags)
+
+    # ---- ring dwell: per run, how long and how often a condition held -------------------------------------------------------
+    DWELL_FIELDS = ("count", "held", "entries", "first_held", "last_held", "prefix_len", "prefix_end", "suffix_len", "suffix_start",
+                    "longest", "longest_start", "longest_end")      # the twelve planes, in order
+
+    @staticmethod
+    def _dwell_dict(raw) -> dict:
+        """A [D, 12, runs] block -> {"count", "held", "entries", "first_held", "last_held", "longest", "longest_start",
+        "longest_end": int64 [D, runs]; "open_at_start", "open_at_end": bool [D, runs]; "fraction": f64 [D, runs]}.  The planes
+        arrive as doubles below 2^53: the conversion is exact.  open_at_start and open_at_end say whether the first and the last
+        finite sample hold; fraction is held / count, NaN where count is 0."""
+        words = {k: raw[:, i].astype(np.int64) for i, k in enumerate(HipExec.DWELL_FIELDS)}
+        out = {k: words[k] for k in ("count", "held", "entries", "first_held", "last_held", "longest", "longest_start", "longest_end")}
+        out["open_at_start"], out["open_at_end"] = words["prefix_len"] > 0, words["suffix_len"] > 0
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["fraction"] = np.where(out["count"] == 0, np.nan, out["held"] / np.maximum(out["count"], 1))
+        return out
+
+    @staticmethod
+    def _dwell_conditions(conditions):
+        """The ctypes array of sixdof_dwell_condition for a list of Dwell — an Element becomes SIXDOF_DWELL_ELEMENT with its levels
+        as they are, a Norm SIXDOF_DWELL_NORM_SQ with squared levels — or its ValueError."""
+        conditions = [conditions] if isinstance(conditions, Dwell) else list(conditions)
+        if not 1 <= len(conditions) <= L.DWELL_MAX_CONDITIONS:
+            raise ValueError(f"history_dwell: {len(conditions)} conditions, 1 to {L.DWELL_MAX_CONDITIONS} can be asked for")
+        arr = (L.DwellCondition * len(conditions))()
+        for c, d in zip(arr, conditions):
+            if d.op not in Dwell.OPS:
+                raise ValueError(f"history_dwell: {d!r}: op is one of {list(Dwell.OPS)}")
+            band = d.op in ("inside", "outside")
+            if band != (d.upper is not None):
+                raise ValueError(f"history_dwell: {d!r}: upper goes with \"inside\" and \"outside\", and only with them")
+            lo, hi = float(d.level), float(d.upper) if band else 0.0
+            if not (math.isfinite(lo) and math.isfinite(hi)) or (band and lo > hi):
+                raise ValueError(f"history_dwell: {d!r}: levels are finite, and level is not above upper")
+            if isinstance(d.of, Norm):
+                if lo < 0.0 or hi < 0.0 or not (math.isfinite(lo * lo) and math.isfinite(hi * hi)):
+                    raise ValueError(f"history_dwell: {d!r}: the levels of a Norm are not negative, and their squares are finite")
+                norm, c.kind, lo, hi = d.of, L.DWELL_NORM_SQ, lo * lo, hi * hi
+            elif isinstance(d.of, Element):
+                e = d.of
+                norm, c.kind = Norm(e.component, e.element, 1, e.group, e.minus, e.minus_element, e.minus_group), L.DWELL_ELEMENT
+            else:
+                raise ValueError(f"history_dwell: {d!r}: `of` is an Element or a Norm")
+            HipExec._norm_probe_fill(c.probe, norm, "history_dwell")
+            c.lo, c.hi, c.op = lo, hi, Dwell.OPS[d.op]
+        return arr
+
+    def _dwell_buffer(self, n_conditions: int, period: int) -> np.ndarray:
+        """The [D, 12, runs] block, holding what a range without samples reduces to: nothing counted, no ticks."""
+        return np.zeros((n_conditions, L.DWELL_PLANES, self.n // max(period, 1)), dtype=np.float64)
+
+    _DWELL_SCAN = _Scan("sixdof_history_dwell", L.DWELL_CONTINUE, L.DWELL_HOLD, "dwell", False, lambda capture, raw, caps: HipExec._dwell_dict(raw),
+                        lambda self, n_conditions, period: self._dwell_buffer(n_conditions, period))
+
+    def history_dwell(self, conditions, first_tick: int, last_tick: int, every: int = 1, period: int = 1) -> dict:
+        """{"count", "held", "entries", "first_held", "last_held", "longest", "longest_start", "longest_end": int64 [D, runs];
+        "open_at_start", "open_at_end": bool [D, runs]; "fraction": f64 [D, runs]}: per Dwell and run (period consecutive rows;
+        runs = n // period), over the ticks first_tick, first_tick + every, ... <= last_tick, how long and how often the condition
+        held — counted on the device out of the ring.  count is the samples at which the value is finite (the others are skipped:
+        a stretch continues across them), held those at which the condition holds, entries the maximal stretches of consecutive
+        held samples, longest the length in samples of the EARLIEST stretch of maximal length, from tick longest_start to tick
+        longest_end.  0 in a tick field means none.  Stateless: no watch is involved."""
+        return self._scan(self._DWELL_SCAN, self._dwell_conditions(conditions), (), first_tick, last_tick, every, period)
+
+    def stream_dwell(self, conditions, n_batches: int, ticks_per_batch: int, every: int = 1, period: int = 1, flags: int = 0):
+        """history_dwell over a run longer than the ring: n_batches batches of ticks_per_batch ticks are stepped, and after every
+        batch its samples — every `every`-th tick, ending on the batch's last — are merged into the accumulator on the device
+        (SIXDOF_DWELL_HOLD, SIXDOF_DWELL_CONTINUE from the second batch on); a stretch that spans a batch boundary is one stretch.
+        Nothing crosses the link until the last batch's call delivers.  A ring one batch deep is enough (enabled here unless
+        enable_history already made one at least that large).  Returns (wall time in seconds, the dict of history_dwell); whatever
+        happens, the caller's flags are restored and the handle is drained."""
+        return self._stream_scan(self._DWELL_SCAN, self._dwell_conditions(conditions), (), n_batches, ticks_per_batch, every, period, flags)
 
     def set_flags(self, flags: int):
         self._lib.sixdof_set_flags(self._h, int(flags))

@@ -369,6 +369,15 @@ class Campaign:
         the run has none).  A Norm's `group` (and minus_group) is the entity of the run it reads."""
         return self._captures_by_run(self.exec.history_norm_events(events, capture, first_tick, last_tick, every, period=self.entities_per_run))
 
+    def dwell(self, conditions, first_tick: int, last_tick: int, every: int = 1) -> Dict[str, Any]:
+        """How long and how often each run met a condition, out of the device ring (self.exec.enable_history): the dict of
+        Exec.history_dwell with a run = entities_per_run consecutive rows — "count", "held", "entries", "first_held", "last_held",
+        "longest", "longest_start", "longest_end", "open_at_start", "open_at_end", "fraction", "t_held", "t_longest",
+        "t_first_held", "t_last_held", "t_longest_start", "t_longest_end": [condition, run].  The `group` (and minus_group) of a
+        Dwell's Element or Norm is the entity of the run it reads: time above a limit, excursions out of a corridor, time inside
+        a keep-out sphere of two entities of a run."""
+        return self.exec.history_dwell(conditions, first_tick, last_tick, every, period=self.entities_per_run)
+
     def result_table(self, names: Sequence[str]) -> np.ndarray:
         """The runs' `el.monte_carlo.result(...)` records as [n_runs, len(names)] (NaN where a run reported nothing)."""
         out = np.full((self.n_runs, len(names)), np.nan)

@@ -691,6 +691,77 @@ int sixdof_history_norm_events(sixdof_handle* h, const sixdof_norm_trigger* trig
                                size_t n_captures, uint32_t period, uint64_t first_tick, uint64_t n_samples, uint64_t every,
                                double* event_dst, double* const capture_dst[], uint32_t flags);
 
+/* ---- ring dwell: per run, how long and how often a condition held -------------------------------------------------------------
+ * The event readers answer WHEN something first happened, the extremes and the norms WHAT the extreme was.  A results table asks
+ * as often HOW LONG and HOW OFTEN: the time above a dynamic-pressure or load limit, how many times a vehicle left its corridor
+ * and whether it was still outside at the end, how long chaser and target stayed inside a keep-out sphere, the longest unbroken
+ * stretch with |omega| above a tumble limit and when it began, the share of a flight spent in an altitude band.
+ *
+ * A run is `period` consecutive rows (n_entities % period == 0; runs = n_entities / period).  A condition is a probe — the struct
+ * of sixdof_history_norms, read the same way — a kind, an op and two levels.  SIXDOF_DWELL_ELEMENT: probe.count must be 1, and the
+ * value of a sample is the signed scalar v = a_0, or a_0 - b_0 with SIXDOF_NORM_MINUS: every ring element widened to double first
+ * (exact for an f32 handle), one subtraction, no FMA contraction.  SIXDOF_DWELL_NORM_SQ: v is exactly the SQUARED norm s that
+ * sixdof_history_norms forms of the probe, and lo and hi are SQUARED levels, not below 0.  The predicate is an IEEE compare:
+ * SIXDOF_EVENT_LT .. SIXDOF_EVENT_GE: v op lo, and hi must be 0; SIXDOF_DWELL_INSIDE: lo <= v && v <= hi; SIXDOF_DWELL_OUTSIDE:
+ * v < lo || v > hi; both with lo <= hi.  Levels are finite.  A sample is finite exactly when v is (an overflowing difference or
+ * square is not); a non-finite sample is skipped as the events skip it: it neither holds nor fails, and a stretch continues
+ * across it.  Nothing stops early: every sample counts.
+ *
+ * Samples are the ticks first_tick, first_tick + every, ... (n_samples of them), all in the ring.  host_dst is
+ * [n_conditions][SIXDOF_DWELL_PLANES][runs] doubles, plane-major.  Ticks are counts of completed ticks, so 0 means "none";
+ * lengths are counted in finite samples:
+ *   plane 0   count           finite samples
+ *   plane 1   held            finite samples at which the predicate holds
+ *   plane 2   entries         maximal stretches of consecutive (finite) held samples
+ *   plane 3   first_held      the first tick at which it holds
+ *   plane 4   last_held       the last tick at which it holds
+ *   plane 5   prefix_len      the stretch that begins at the first finite sample; 0: the first finite sample does not hold
+ *   plane 6   prefix_end      its last tick
+ *   plane 7   suffix_len      the stretch that ends at the last finite sample; 0: the last finite sample does not hold
+ *   plane 8   suffix_start    its first tick
+ *   plane 9   longest_len     the EARLIEST stretch of maximal length
+ *   plane 10  longest_start   its first tick
+ *   plane 11  longest_end     its last tick
+ * The rule, for one finite sample (h, t) after the others: before = count, count++; if h: held++; if suffix_len == 0: entries++,
+ * suffix_start = t; first_held = first_held ? first_held : t; last_held = t; suffix_len++; if prefix_len == before: prefix_len++,
+ * prefix_end = t; if suffix_len > longest_len (strictly): longest = (suffix_len, suffix_start, t); otherwise suffix_len = 0,
+ * suffix_start = 0.  And for two records, a earlier and b later (an empty side returns the other): the counts add; joined =
+ * a.suffix_len > 0 && b.prefix_len > 0; entries = a.entries + b.entries - joined; first_held = a's or else b's; last_held = b's
+ * or else a's; the prefix is a's unless a.prefix_len == a.count, then (a.count + b.prefix_len, b.prefix_len ? b.prefix_end :
+ * a.prefix_end); the suffix is b's unless b.suffix_len == b.count, then (a.suffix_len + b.count, a.suffix_len ? a.suffix_start :
+ * b.suffix_start); the longest is a's, then the joined stretch (a.suffix_len + b.prefix_len, a.suffix_start, b.prefix_end) if
+ * joined and strictly longer, then b's if strictly longer.  All of it is integer, exact and associative in time order, and there
+ * are no atomics, so every output is bit-identical however the range is cut into time segments (SIXDOF_DWELL_SEGMENTS in the
+ * environment forces a count; 0 or unset: the library's choice), launches or calls.  Every word is below 2^53: a range whose last
+ * sampled tick is 2^53 or more is refused.
+ * SIXDOF_DWELL_HOLD, SIXDOF_DWELL_CONTINUE and SIXDOF_DWELL_ASYNC behave as SIXDOF_NORMS_HOLD, _CONTINUE and _ASYNC: the
+ * accumulator is the call's staging buffer, and a continuing call is accepted only if the previous call succeeded with the same
+ * conditions field for field (lo and hi compared by their bits) and the same period, ring bases, widths and row count are
+ * unchanged, no sixdof_set_history or sixdof_bind_columns came since, and first_tick is above the last tick accumulated;
+ * otherwise SIXDOF_ERR_INVALID_ARGUMENT and the accumulator stays as it was.
+ * n_samples = 0 is a no-op that leaves the accumulator alone.  SIXDOF_ERR_INVALID_ARGUMENT, with nothing copied and the
+ * accumulator as it was: everything sixdof_history_norms refuses (n_conditions in the place of n_probes, at most
+ * SIXDOF_DWELL_MAX_CONDITIONS), an unknown kind or op, count != 1 with SIXDOF_DWELL_ELEMENT, a level that is not finite, hi != 0
+ * with a one-sided op, lo > hi, a level below 0 with SIXDOF_DWELL_NORM_SQ.  A component the ring does not record:
+ * SIXDOF_ERR_COMPONENT_NOT_FOUND.  A call that fails in the runtime leaves the ring as it was and the accumulator invalid, as for
+ * sixdof_history_extremes. */
+typedef struct sixdof_dwell_condition {   /* 64 bytes */
+    sixdof_norm_probe probe;              /* as for sixdof_history_norms */
+    double lo, hi;                        /* finite; SQUARED and >= 0 with SIXDOF_DWELL_NORM_SQ */
+    uint32_t kind, op;                    /* SIXDOF_DWELL_ELEMENT or _NORM_SQ; SIXDOF_EVENT_LT .. _GE, SIXDOF_DWELL_INSIDE or _OUTSIDE */
+} sixdof_dwell_condition;
+#define SIXDOF_DWELL_ELEMENT 0u
+#define SIXDOF_DWELL_NORM_SQ 1u
+#define SIXDOF_DWELL_INSIDE  4u
+#define SIXDOF_DWELL_OUTSIDE 5u
+#define SIXDOF_DWELL_ASYNC    1u
+#define SIXDOF_DWELL_CONTINUE 2u
+#define SIXDOF_DWELL_HOLD     4u
+#define SIXDOF_DWELL_PLANES   12
+#define SIXDOF_DWELL_MAX_CONDITIONS 8
+int sixdof_history_dwell(sixdof_handle* h, const sixdof_dwell_condition* conditions, size_t n_conditions, uint32_t period,
+                         uint64_t first_tick, uint64_t n_samples, uint64_t every, double* host_dst, uint32_t flags);
+
 /* ---- ring covariances: how quantities vary TOGETHER across the rows, over time ---------------------------------------------
  * The landing footprint ellipse, the 6 x 6 position / velocity dispersion, whether touchdown speed goes with lateral miss: joint
  * moments.  The envelope's mean and m2 are the diagonal of this matrix; the off-diagonals cannot be recovered from them.
